@@ -11,6 +11,7 @@ all-reduce (N>1, native communicator on a comm stream overlapping backward),
 SGD-momentum + weight-decay update, BN moving averages.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--model cifar_resnet50]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Without torchrun, `--gpus N` (N > 1) spawns the N rank processes itself before
@@ -19,6 +20,13 @@ MASTER_PORT, as torchrun sets them) and relays rank 0's line; it fails if any
 rank fails.  Rank 0 prints ONE JSON line.  `--model imagenet_resnet50` measures
 BASELINE config 4 (128 images per GPU, weak scaling, baseline 0.93 stp/s),
 `--model imagenet_resnet101` config 5 (256 per GPU).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full`
+adds what takes steps of its own: the per-phase HIP-event timing (`phase_ms`, taken over
+`--phase-steps` extra steps after the timed region).  `--dump-outputs DIR` writes what
+the last timed step left with its caller -- the updated weights, the momentum, the BN
+moving statistics and the step's scalars -- as float32 / float64 `DIR/<name>.npy`; the
+inputs and the initial weights are seeded, so two builds can be compared output for output.
 
 `--device cpu` runs the fp32 PyTorch CPU trainer (gloo for N > 1): a plumbing
 check of this contract for hosts without a GPU, never a headline number.
@@ -89,9 +97,15 @@ def parse(argv=None):
                     help="all-reduce bucket size (MiB); 0 = auto (~4 buckets, <= 25 MiB)")
     ap.add_argument("--allreduce-dtype", default="fp32", choices=("fp32", "bf16"),
                     help="gradient all-reduce precision (bf16 halves the xGMI bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs steps of its own: the per-phase timing "
+                         "(--phase-steps); a plain run only times --steps steps")
     ap.add_argument("--phase-steps", type=int, default=5,
-                    help="extra steps after the timed region with per-phase HIP-event timing "
-                         "(forward / backward / exposed all-reduce / optimizer); 0 = skip")
+                    help="with --full: extra steps after the timed region with per-phase HIP-event "
+                         "timing (forward / backward / exposed all-reduce / optimizer); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (weights, momentum, "
+                         "BN moving statistics, scalars) as DIR/<name>.npy")
     ap.add_argument("--step-timeout", type=float, default=300.0,
                     help="watchdog: abort the communicator and exit 3 when no step completes for "
                          "this many seconds (first step: 3x), or on a communicator async error")
@@ -166,6 +180,32 @@ def dtr_env() -> dict:
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("DTR_")}
 
 
+DUMP_MAX_ELEMS = 4 << 20   # per array: 3 float32 arrays + the scalars stay under 64 MB
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(path: str, arrays: dict, scalars: dict) -> None:
+    """--dump-outputs: one .npy per array (float32; an array of more than DUMP_MAX_ELEMS
+    elements is cut to a fixed, seeded sample of that many, in index order) and the
+    step's scalars as float64 `metrics.npy`, in the order of `metrics_names.txt`."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1)
+        if a.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            idx = np.sort(rng.choice(a.numel(), DUMP_MAX_ELEMS, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
+    names = sorted(scalars)
+    np.save(os.path.join(path, "metrics.npy"),
+            np.array([float(scalars[k]) for k in names], dtype=np.float64))
+    with open(os.path.join(path, "metrics_names.txt"), "w") as fh:
+        fh.write("\n".join(names) + "\n")
+
+
 def run_cpu(args, dataset, size, per_rank, global_batch, world):
     import torch
 
@@ -196,6 +236,9 @@ def run_cpu(args, dataset, size, per_rank, global_batch, world):
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     ctx.all_reduce_max(el)
     m = be.metrics()
+    if args.dump_outputs and ctx.is_chief:
+        dump_outputs(args.dump_outputs, {"weights": be.store.master, "momentum": be.mom,
+                                         "bn_moving_stats": be.store.stats}, m)
     return ctx, float(el.item()), m, {"dtype": "fp32", "device": "cpu"}, None
 
 
@@ -280,9 +323,12 @@ def run_gpu(args, dataset, size, per_rank, global_batch, world):
     else:
         os.environ["DTR_TUNE"] = base_tune
     m = eng.metrics()
-    # per-phase timing, outside the timed region (not part of `value`)
+    if args.dump_outputs and ctx.is_chief:   # before the phase steps move the weights on
+        dump_outputs(args.dump_outputs, {"weights": eng.params.master, "momentum": eng.mom,
+                                         "bn_moving_stats": eng.params.stats}, m)
+    # --full: per-phase timing, outside the timed region (not part of `value`)
     phases = None
-    if args.phase_steps > 0 and not use_graph:
+    if args.full and args.phase_steps > 0 and not use_graph:
         acc = {}
         for _ in range(args.phase_steps):
             for k, v in eng.step_timed().items():

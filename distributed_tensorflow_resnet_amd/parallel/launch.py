@@ -36,7 +36,33 @@ def _spawn(nproc, script, args, port, addr, extra_env):
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         procs.append(subprocess.Popen([sys.executable, script] + list(args), env=env,
                                       start_new_session=True))
+        _live.append(procs[-1])
     return procs
+
+
+_live: list = []   # every rank process spawned so far, for _stop_ranks
+
+
+def _stop_ranks(signum, _frame):
+    """The launcher itself is told to stop (launch/stop.sh, Ctrl-C, scancel).  Every rank
+    runs in a session of its own, so the signal does not reach it: terminate the ranks'
+    process groups here, or they would outlive the job."""
+    for p in _live:
+        if p.poll() is None:
+            try:
+                os.killpg(p.pid, signal.SIGTERM)
+            except ProcessLookupError:
+                pass
+    deadline = time.time() + 20
+    for p in _live:
+        try:
+            p.wait(timeout=max(0.1, deadline - time.time()))
+        except subprocess.TimeoutExpired:
+            try:
+                os.killpg(p.pid, signal.SIGKILL)
+            except ProcessLookupError:
+                pass
+    sys.exit(128 + signum)
 
 
 def _wait(procs, poll_s=0.5):
@@ -77,6 +103,8 @@ def main(argv=None) -> int:
     ap.add_argument("args", nargs=argparse.REMAINDER)
     a = ap.parse_args(argv)
     rc = 0
+    for sig in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+        signal.signal(sig, _stop_ranks)
     for attempt in range(a.max_restarts + 1):
         extra = {"DTR_RESTART_ATTEMPT": str(attempt)}
         if attempt > 0:

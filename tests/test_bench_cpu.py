@@ -34,6 +34,32 @@ def test_bench_self_spawns_ranks_and_reports_process_group():
         assert key in out
 
 
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32 / float64 .npy, and
+    two runs with the same arguments start from the same inputs: identical files."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench(["--device", "cpu", "--gpus", "1", "--model", "cifar_resnet20", "--batch", "4",
+                    "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["bn_moving_stats.npy", "metrics.npy", "metrics_names.txt",
+                         "momentum.npy", "weights.npy"]
+        dumps.append({f: np.load(tmp_path / d / f) for f in files if f.endswith(".npy")})
+    a, b = dumps
+    names = (tmp_path / "a" / "metrics_names.txt").read_text().split()
+    assert a["metrics.npy"].dtype == np.float64 and len(names) == a["metrics.npy"].size
+    assert a["metrics.npy"][names.index("global_step")] == 3      # warmup + steps
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+    assert a["weights.npy"].ndim == 1 and np.abs(a["momentum.npy"]).sum() > 0
+
+
 def test_bench_spawn_fails_when_a_rank_fails():
     # an indivisible global batch makes every rank exit non-zero
     r = _bench(["--device", "cpu", "--gpus", "2", "--model", "cifar_resnet20", "--batch", "7",

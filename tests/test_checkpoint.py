@@ -1,7 +1,6 @@
 """TF tensor-bundle checkpoint compatibility (CPU).  Fixtures: the reference's own
-checkpoint indexes (test/resnet50-cifar-ckpt-20190218/*.index; the .data blobs
+checkpoint indexes (tests/golden/resnet50-cifar-ckpt-20190218/*.index; the .data blobs
 were withheld upstream, so values are synthetic and only the layout is pinned)."""
-import glob
 import os
 
 import numpy as np
@@ -14,8 +13,10 @@ from distributed_tensorflow_resnet_amd.utils import crc32c
 from distributed_tensorflow_resnet_amd.utils import tensor_bundle as tb
 from distributed_tensorflow_resnet_amd.utils.checkpoint import Saver, state_to_tf, tf_to_state
 
-REF_DIR = "/root/reference/test/resnet50-cifar-ckpt-20190218"
-REF_INDEXES = sorted(glob.glob(os.path.join(REF_DIR, "model.ckpt-*.index")))
+import golden_files
+
+REF_INDEXES = golden_files.INDEXES   # stored with the tests (tests/golden/README.md)
+assert len(REF_INDEXES) == 5, REF_INDEXES
 needs_ref = pytest.mark.skipif(not REF_INDEXES, reason="reference checkpoint fixtures absent")
 
 
@@ -29,7 +30,7 @@ def test_crc32c_known_values():
 
 
 @needs_ref
-@pytest.mark.parametrize("path", REF_INDEXES)
+@pytest.mark.parametrize("path", REF_INDEXES, ids=os.path.basename)
 def test_index_rebuild_is_byte_identical(path):
     buf = open(path, "rb").read()
     header, entries = tb.read_index(path)

@@ -86,7 +86,7 @@ def test_bench_self_spawn_two_ranks_native_shm(gpu):
     env = dict(os.environ, DTR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **SHM)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "3",
-                        "--model", "cifar_resnet20"], cwd=ROOT, env=env, capture_output=True,
+                        "--model", "cifar_resnet20", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

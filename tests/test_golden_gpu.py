@@ -17,10 +17,9 @@ from distributed_tensorflow_resnet_amd.utils import graphdef as gd
 from distributed_tensorflow_resnet_amd.utils.checkpoint import tf_to_state
 from distributed_tensorflow_resnet_amd.utils.tf_interp import Interpreter
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-REF_PB = "/root/reference/test/resnet50-cifar-ckpt-20190218/resnet50_cifar_frozen_model_eval.pb"
-if not os.path.exists(REF_PB):   # the GPU box sees only this repo: the fixture copy
-    REF_PB = os.path.join(_HERE, "fixtures", "resnet50_cifar_frozen_model_eval.pb")
+import golden_files
+
+REF_PB = golden_files.frozen_pb()   # stored with the tests (tests/golden/README.md)
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not os.path.exists(REF_PB), reason="reference .pb absent")]
 

@@ -21,13 +21,13 @@ from distributed_tensorflow_resnet_amd.utils import graphdef as gd
 from distributed_tensorflow_resnet_amd.utils.checkpoint import tf_to_state
 from distributed_tensorflow_resnet_amd.utils.tf_interp import Interpreter
 
-REF_DIR = "/root/reference/test/resnet50-cifar-ckpt-20190218"
-REF_EVAL_META = os.path.join(REF_DIR, "resnet50_cifar_eval_graph.meta")
-REF_PB = os.path.join(REF_DIR, "resnet50_cifar_frozen_model_eval.pb")
-if not os.path.exists(REF_PB):   # copy kept with the tests (tests/fixtures/README.md)
-    REF_PB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures",
-                          "resnet50_cifar_frozen_model_eval.pb")
-REF_META = os.path.join(REF_DIR, "model.ckpt-107738.meta")
+import golden_files
+
+# the reference's own artefacts, stored with the tests (tests/golden/README.md)
+REF_DIR = golden_files.CKPT_DIR
+REF_EVAL_META = golden_files.EVAL_META
+REF_PB = golden_files.frozen_pb()
+REF_META = golden_files.train_meta()
 needs_pb = pytest.mark.skipif(not os.path.exists(REF_PB), reason="reference frozen graph absent")
 
 

@@ -58,6 +58,16 @@ def test_start_and_stop_background_run(tmp_path):
             alive = False
         assert not alive
     assert not glob.glob(str(tmp_path / "*.pid"))
+    # the ranks run in sessions of their own: the launcher must have taken them down too
+    left = []
+    for pid in filter(str.isdigit, os.listdir("/proc")):
+        try:
+            cmd = open(f"/proc/{pid}/cmdline", "rb").read()
+        except OSError:
+            continue
+        if str(tmp_path).encode() in cmd:
+            left.append((int(pid), cmd.replace(b"\0", b" ")[:200]))
+    assert not left, left
 
 
 def test_gpu_shared_by_ranks(monkeypatch):

@@ -109,6 +109,40 @@ def opt_tile(R: int, K: int, splits: int, cslab: int, C: int, taps: int, nosplit
     return TR, TC
 
 
+def sgd_tiles_work(seg_arr, seg_names, slabs, gptr: int, names=None, nosplit=(64, 64)):
+    """The work map of the one-launch optimizer (csrc/optim.hip sgd_tiles_kernel): per
+    parameter segment its slab (split-K partials still to be summed, or none: the
+    gradient is in `grad`, at device address gptr) and its first workgroup; weights with
+    bf16 copies or slabs go in tiles of their HWIO master (opt_tile), other tensors in
+    1024-element chunks.  `names`: only those segments get workgroups (a bucket's pack
+    launch).  Returns the OptWork table (numpy, OPTW_DTYPE) and blk_seg (a list)."""
+    work = np.zeros(len(seg_arr), dtype=OPTW_DTYPE)
+    blk = []
+    for i, (rec, name) in enumerate(zip(seg_arr, seg_names)):
+        if names is not None and name not in names:
+            continue
+        d = slabs.get(name)
+        taps, C, K = int(rec["kh"] * rec["kw"]), int(rec["C"]), int(rec["K"])
+        tiled = d is not None or rec["bf_ohwi"] >= 0 or rec["bf_hwio"] >= 0
+        part, splits, kslab, cslab = 0, 0, 0, 0
+        if d is not None:
+            part, grad, splits, kslab, Kv, dtaps, cslab, Cv = d
+            assert (grad, Kv, dtaps, Cv) == (gptr + 4 * int(rec["offset"]), K, taps, C), name
+            assert kslab >= K and cslab >= C and part % 16 == 0, name
+        tr = tc = 0
+        if tiled:
+            assert taps * C * K == rec["numel"], name
+            tr, tc = opt_tile(taps * C, K, splits, cslab or C, C, taps, nosplit)
+            n = _ceil(taps * C, tr) * _ceil(K, tc)
+        else:
+            n = _ceil(int(rec["numel"]), 1024)
+        work[i] = (part, len(blk), splits, kslab, cslab, int(tiled), tr, tc)
+        blk += [i] * n
+    assert not set(slabs) - set(seg_names), "slab without a parameter segment"
+    assert names is None or not set(slabs) - set(names), "slab outside the packed segments"
+    return work, blk
+
+
 @dataclass
 class LRSchedule:
     """Piecewise LR evaluated on the device (see csrc/optim.h LrSchedule)."""
@@ -1370,37 +1404,10 @@ class Engine:
         self._emit_optimizer(plan)
 
     def _sgd_tiles_work(self, slabs, names=None, nosplit=(64, 64)):
-        """The work map of the one-launch optimizer (csrc/optim.hip sgd_tiles_kernel): per
-        parameter segment its slab (split-K partials still to be summed, or none: the
-        gradient is in `grad`) and its first workgroup; weights with bf16 copies or slabs
-        go in tiles of their HWIO master (opt_tile), other tensors in 1024-element chunks.
-        `names`: only those segments get workgroups (a bucket's pack launch)."""
-        work = np.zeros(self.nseg, dtype=OPTW_DTYPE)
-        blk = []
-        gptr = self.grad.data_ptr()
-        for i, (rec, name) in enumerate(zip(self.seg_arr, self.seg_names)):
-            if names is not None and name not in names:
-                continue
-            d = slabs.get(name)
-            taps, C, K = int(rec["kh"] * rec["kw"]), int(rec["C"]), int(rec["K"])
-            tiled = d is not None or rec["bf_ohwi"] >= 0 or rec["bf_hwio"] >= 0
-            part, splits, kslab, cslab = 0, 0, 0, 0
-            if d is not None:
-                part, grad, splits, kslab, Kv, dtaps, cslab, Cv = d
-                assert (grad, Kv, dtaps, Cv) == (gptr + 4 * int(rec["offset"]), K, taps, C), name
-                assert kslab >= K and cslab >= C and part % 16 == 0, name
-            tr = tc = 0
-            if tiled:
-                assert taps * C * K == rec["numel"], name
-                tr, tc = opt_tile(taps * C, K, splits, cslab or C, C, taps, nosplit)
-                n = _ceil(taps * C, tr) * _ceil(K, tc)
-            else:
-                n = _ceil(int(rec["numel"]), 1024)
-            work[i] = (part, len(blk), splits, kslab, cslab, int(tiled), tr, tc)
-            blk += [i] * n
+        """sgd_tiles_work for this engine's segments, as device tensors."""
+        work, blk = sgd_tiles_work(self.seg_arr, self.seg_names, slabs, self.grad.data_ptr(),
+                                   names, nosplit)
         assert OPTW_DTYPE.itemsize == self.nat.opt_work_bytes()
-        assert not set(slabs) - set(self.seg_names), "slab without a parameter segment"
-        assert names is None or not set(slabs) - set(names), "slab outside the packed segments"
         wt = torch.from_numpy(work.view(np.uint8).copy()).to(self.device)
         bt = torch.tensor(blk, dtype=torch.int32, device=self.device)
         self._keep += [wt, bt]

@@ -131,6 +131,47 @@ def test_optimizer_step_and_pack(gpu, monkeypatch):
 
 
 @pytest.mark.parametrize("persist", [0, 1])
+def test_optimizer_three_steps_match_fp64_recurrence(gpu, monkeypatch, persist):
+    """Three training steps through either optimizer path (sgd_pack + ohwi_pack; the
+    persistent step's one-launch sgd_tiles summing the slabs) against the fp64
+    SGD-momentum recurrence (tests/optim_oracle.py) applied to the step's own gradient:
+    steps 1 and 2 start from a non-zero accumulator.  The whole bf16 weight buffer must be
+    the packed copies of the master after every step."""
+    import optim_oracle as oo
+
+    monkeypatch.setenv("DTR_TUNE", f"persist={persist},opt_fused=1")
+    spec = cifar_spec(8)
+    eng, _, _, _ = _make(spec, 16, gpu)
+    assert eng.persist == (persist == 1)
+    if persist:
+        assert eng.opt_fused and "gsum" in eng.seg   # sgd_tiles sums the slabs itself
+    sched = eng.sched
+    for step in range(3):
+        w0, m0 = eng.params.master.clone(), eng.mom.clone()
+        assert int(eng.gstep.item()) == step
+        eng.step()
+        torch.cuda.synchronize()
+        if persist:
+            assert not eng.persist_error()
+        if step:
+            assert float(m0.abs().max()) > 0
+        lr = oo.f32(oo.lr_reference(sched, step))
+        assert eng.metrics()["lr"] == lr
+        n = eng.params.n_train
+        w_ref, m_ref, B = oo.sgd_reference(w0[:n], eng.grad[:n], m0[:n], lr, oo.f32(eng.momentum),
+                                           oo.f32(eng.wd), 1.0, eng.use_momentum)
+        ew = (eng.params.master[:n].double() - w_ref).abs()
+        em = (eng.mom[:n].double() - m_ref).abs()
+        print(f"step {step}: max err/B master {float((ew / B.clamp_min(1e-300)).max()):.3f} "
+              f"mom {float((em / B.clamp_min(1e-300)).max()):.3f}")
+        assert bool((ew <= B).all()), (step, float(ew.max()))
+        assert bool((em <= B).all()), (step, float(em.max()))
+        assert torch.equal(eng.wbf, oo.expected_wbf(eng.seg_arr, eng.params.master,
+                                                    eng.wbf.numel()))
+    assert int(eng.gstep.item()) == 3
+
+
+@pytest.mark.parametrize("persist", [0, 1])
 def test_graph_replay_matches_eager(gpu, monkeypatch, persist):
     """(persist: the persistent step, whose one-launch optimizer's global_step ticket
     re-arms across graph replays)"""

@@ -519,6 +519,31 @@ static Launch mk_prn(int mode, std::vector<ptr_t> p, std::vector<int> n, std::ve
   throw std::invalid_argument("prn: mode 0 (forward), 1 (backward) or 2 (head folds)");
 }
 
+// Persistent inference forward (cifar_persist.hip prn_infer): one launch, one workgroup per
+// image, moving-average BatchNorm; fp32 logits [N][kpad] (columns >= classes 0) and,
+// when `pooled` is non-zero, the pooled features [N][64].
+static Launch mk_prn_infer(ptr_t blocks, ptr_t bns, ptr_t x_in, ptr_t stem_w, ptr_t dense_w,
+                           ptr_t dense_b, ptr_t logits, ptr_t pooled, int nblocks, int N,
+                           int classes, int kpad, float eps) {
+  PrnInferArgs a{};
+  a.blocks = P<const PrnBlock>(blocks);
+  a.bns = P<const PrnBn>(bns);
+  a.x_in = P<const bf16>(x_in);
+  a.stem_w = P<const bf16>(stem_w);
+  a.dense_w = P<const bf16>(dense_w);
+  a.dense_b = P<const float>(dense_b);
+  a.logits = P<float>(logits);
+  a.pooled = P<bf16>(pooled);
+  a.nblocks = nblocks;
+  a.N = N;
+  a.classes = classes;
+  a.kpad = kpad;
+  a.eps = eps;
+  if (!prn_infer_supported(nblocks, classes, kpad) || N < 1)
+    throw std::invalid_argument("prn_infer: unsupported shape");
+  return [a](hipStream_t s) { prn_infer(a, s); };
+}
+
 static Launch mk_prn_bucket_wait(ptr_t bar, int bucket, long long target, ptr_t err) {
   return [=](hipStream_t s) { prn_bucket_wait(P<unsigned>(bar), bucket, (unsigned)target, P<int>(err), s); };
 }
@@ -1191,6 +1216,9 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "head_fused", mk_head_fused);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
+  def_op(m, plan, "prn_infer", mk_prn_infer);
+  m.def("prn_infer_supported", &prn_infer_supported,
+        "whether the persistent inference forward covers (blocks, classes, kpad); any batch");
   m.def("prn_set_probe", [](ptr_t p) { prn_set_probe(P<long long>(p)); },
         "diagnostics: image 0 of the persistent launches records (tag, wall clock) pairs here");
   m.def("prn_supported", &prn_supported, "whether the persistent CIFAR step covers (N, slices, blocks, classes, kpad)");

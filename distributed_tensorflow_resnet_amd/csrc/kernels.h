@@ -333,6 +333,28 @@ void prn_bucket_wait(unsigned* bar, int bucket, unsigned target, int* err, hipSt
 // item kind of a conv (stage of its output, kernel size, stride; stem = 8 input channels)
 int prn_item_kind(int cin, int cout, int ksize, int stride);
 
+// Persistent inference forward (moving-average BatchNorm): the whole CIFAR network in ONE
+// launch, one 512-thread workgroup per image, activations in LDS and registers from the
+// stem to the logits.  Without batch statistics the images are independent: no grid
+// barrier, no atomics, no co-residency -- any N (more images than CUs are more
+// workgroups).  Of PrnBn it reads gamma / beta / mmean / mvar only, of PrnBlock w1f / w2f /
+// wpf / stage / stride / bn1 / bn2; it stores the logits (and, optionally, the pooled
+// features) and nothing else.
+struct PrnInferArgs {
+  const PrnBlock* blocks;
+  const PrnBn* bns;          // [2 * nblocks + 1], PrnArgs::bns' order
+  const bf16* x_in;          // [N][32][32][8] input images (channels 3..7 zero)
+  const bf16* stem_w;        // OHWI [16][3][3][8]
+  const bf16* dense_w;       // OHWI [kpad][64] bf16
+  const float* dense_b;      // [classes]
+  float* logits;             // [N][kpad] fp32, columns >= classes written as 0
+  bf16* pooled;              // optional [N][64] pooled features (nullptr: not stored)
+  int nblocks, N, classes, kpad;
+  float eps;
+};
+bool prn_infer_supported(int nblocks, int classes, int kpad);   // 3n blocks, classes <= kpad <= 128
+void prn_infer(const PrnInferArgs& a, hipStream_t s);
+
 struct WgradArgs {
   const bf16* dy;           // [N,Ho,Wo,K]
   const bf16* x;            // [N,H,W,C] (pre-BN tensor if pre_scale given)

@@ -1922,22 +1922,39 @@ class Engine:
         self.repack()
 
     # ------------------------------------------------------------------ eval
-    def build_eval_plan(self, batch: int):
-        """Forward-only plan in inference mode (BN from moving statistics)."""
-        if batch in self.eval_plans:
-            return self.eval_plans[batch]
-        ev = _EvalPlan(self, batch)
-        self.eval_plans[batch] = ev
-        return ev
+    def build_eval_plan(self, batch: int, persist: bool | None = None):
+        """Forward-only plan in inference mode (BN from moving statistics).  ``persist``:
+        True the one-launch persistent forward (train/persist.py PersistInfer; ValueError
+        with the reason where the network is not covered), False the launch-per-layer
+        plan, None by tune ``persist_eval`` (1: persistent wherever supported, else
+        quietly per-layer; -1 auto: the same -- it is the faster plan at every measured
+        batch, profiles/cifar_persist_infer.md -- except that tune persist=0 keeps meaning
+        "the launch-per-layer engine"; 0: per-layer)."""
+        from . import persist as _persist
+        if persist is None:
+            pe = tune.get("persist_eval")
+            if pe == 0 or (pe < 0 and tune.get("persist") == 0):
+                persist = False
+            else:
+                persist = _persist.infer_check(self) == ""
+        elif persist:
+            reason = _persist.infer_check(self)
+            if reason:
+                raise ValueError(f"persistent eval plan unsupported: {reason}")
+        key = (batch, "persistent" if persist else "per-layer")
+        if key not in self.eval_plans:
+            self.eval_plans[key] = _EvalPlan(self, batch, persist=bool(persist))
+        return self.eval_plans[key]
 
 
 class _EvalPlan:
     """Inference forward (resnet_cifar_main.py:361-421 evaluate()): batch-norm
     with moving statistics, no statistics update, softmax probabilities."""
 
-    def __init__(self, eng: Engine, N: int):
+    def __init__(self, eng: Engine, N: int, persist: bool = False):
         self.eng = eng
         self.N = N
+        self.kind = "persistent" if persist else "per-layer"
         nat, spec, dev = eng.nat, eng.spec, eng.device
         H, W = spec.image_h, spec.image_w
         self.img_u8 = torch.zeros((N, 3, H, W), dtype=torch.uint8, device=dev)
@@ -1953,6 +1970,25 @@ class _EvalPlan:
         if not eng.stem_s2d:   # raw uint8 CIFAR records (run(raw_u8=True))
             self.input_plan.cifar_augment(self.img_u8.data_ptr(), self.x_in.data_ptr(), N, H, W,
                                           eng.cpad_in, 4, 0, 0, 0, 0, 0, 0)
+        if persist:
+            # ONE launch from the images to the fp32 logits (no per-BN scale / shift
+            # buffer, no activation tensor: nothing the training plan owns is written)
+            from .persist import PersistInfer
+            self.prn = PersistInfer(eng)
+            self.prn.record(p, self.x_in, self.logits, N, BN_EPS)
+            self._bufs = []
+        else:
+            self._record_layers(p)
+        sp = self.scalars.data_ptr()
+        p.softmax_xent(self.logits.data_ptr(), eng.kpad, self.labels.data_ptr(), N,
+                       spec.num_classes, sp, sp + 4, 0, 0, 1.0, self.probs.data_ptr(),
+                       self.xent_ws.data_ptr())
+
+    def _record_layers(self, p):
+        """The launch-per-layer forward: bn_eval per BatchNorm, conv_gemm per conv, pool,
+        dense -> self.logits."""
+        eng, N = self.eng, self.N
+        nat, spec, dev = eng.nat, eng.spec, eng.device
         st = spec.stem
         stem = eng.convs[st.name]
         bufs = []
@@ -1998,10 +2034,6 @@ class _EvalPlan:
                          self.pooled.data_ptr(), N, x.shape[1] * x.shape[2], F)
         p.conv_gemm(0, self.pooled.data_ptr(), eng.dense_ohwi, 0, self.logits.data_ptr(), 0, 0, 0,
                     eng.dense_bias, spec.num_classes, 0, 0, eng._dense_geom(N), [], [], [], [], [], BN_DECAY, BN_EPS, 1)
-        sp = self.scalars.data_ptr()
-        p.softmax_xent(self.logits.data_ptr(), eng.kpad, self.labels.data_ptr(), N,
-                       spec.num_classes, sp, sp + 4, 0, 0, 1.0, self.probs.data_ptr(),
-                       self.xent_ws.data_ptr())
         self._bufs = bufs
 
     def _conv(self, p, c, x, out, pre, residual=None):
@@ -2012,9 +2044,10 @@ class _EvalPlan:
     def run(self, images=None, labels=None, raw_u8: bool = True):
         """Returns (loss_sum, correct, probs[N, classes]) for one eval batch.
 
-        NOTE: shares the per-BN scale/shift buffers with the training plan, so
-        it must not run concurrently with a training step (the evaluator runs
-        in its own process, like the reference's side-car)."""
+        NOTE: the per-layer plan shares the per-BN scale/shift buffers with the
+        training plan, so it must not run concurrently with a training step (the
+        evaluator runs in its own process, like the reference's side-car).  The
+        persistent plan writes only this plan's own logits / probabilities."""
         st = torch.cuda.current_stream().cuda_stream
         if images is not None:
             if raw_u8:

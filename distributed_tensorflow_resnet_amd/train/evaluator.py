@@ -31,6 +31,8 @@ class GPUInference:
         self.engine = Engine(spec, batch_size, weight_decay=0.0, lr_schedule=constant_lr(0.0),
                              device=device, use_graph=False)
         self.plan = self.engine.build_eval_plan(batch_size)
+        # "persistent" (one prn_infer launch + softmax) or "per-layer" (tune persist_eval)
+        self.eval_path = self.plan.kind
 
     def load(self, tensors):
         tf_to_state(tensors, self.engine.params, None, strict=True)
@@ -110,6 +112,9 @@ class SidecarEvaluator:
         self.best = 0.0
         self.last_prefix = None
         self.history = []
+        path = getattr(model, "eval_path", None)
+        if path is not None:
+            log(f"INFO:tensorflow:eval forward path: {path}")
 
     def run(self, max_polls: int | None = None):
         polls = 0

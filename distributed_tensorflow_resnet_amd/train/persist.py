@@ -30,6 +30,21 @@ image group) while the backward's dgrad chain continues.  The step is then:
 
 Selected by the engine (tune ``persist``: -1 auto = per-rank batch <= AUTO_MAX_BATCH on a supported
 CIFAR spec, 0 off, 1 on when supported).
+
+Inference (PersistInfer, the ``prn_infer`` plan op): with moving-average BatchNorm there
+are no batch statistics, so nothing crosses images -- one workgroup per image runs the
+whole network from the stem to the fp32 logits in LDS and registers, with no grid
+barrier, no atomic and no stored tensor but the logits.  No co-residency, hence no batch
+limit (more images than CUs are more workgroups), and up to 128 padded classes
+(CIFAR-100).  Its tables are built from the engine's BatchNorm parameters and forward
+weights alone (infer_check / shape_check decide; the training step's check() does not
+matter), and the eval plan is two launches: prn_infer, then the per-layer plan's
+softmax_xent.  Selected by ``Engine.build_eval_plan`` (tune ``persist_eval``: -1 auto = on
+wherever supported unless tune persist=0, 0 off, 1 on wherever supported).  It is the
+faster plan at every measured eval batch (MI355X, CIFAR RN50 eval batch, per-layer /
+persistent: bs1 371 / 169 us, bs16 376 / 175, bs100 450 / 178, bs128 455 / 180, bs512
+947 / 356; RN20 bs100 204 / 76; profiles/cifar_persist_infer.md), so auto is not
+batch-aware.
 """
 from __future__ import annotations
 
@@ -105,13 +120,12 @@ def fwd_slices_for(N: int, cus: int, override: int = -1) -> int:
     return 2 if 2 * N + 16 <= cus else 1
 
 
-def check(eng) -> str:
-    """'' when the persistent kernels cover this engine's network, batch and device, else
-    the reason they do not: the network shape here, every host-side limit of the three
-    launches (slices, grids within the CUs, the head folds' LDS) and the co-residency of
-    both grids by the occupancy API in one native predicate (prn_check)."""
-    spec, nat = eng.spec, eng.nat
-    if not spec.dataset.startswith("cifar") or spec.maxpool or eng.stem_s2d:
+def shape_check(spec, stem_s2d: bool = False) -> str:
+    """'' when `spec` is the network the persistent kernels are written for (CIFAR ResNet
+    v2: 32x32 input, 3x3/1 -> 16 stem, 3 stages of building blocks at 16/32/64 channels,
+    a projection on each stage's first block, stride 2 on the first block of stages 2 and
+    3), else the reason it is not.  Host only: no device, no native extension."""
+    if not spec.dataset.startswith("cifar") or spec.maxpool or stem_s2d:
         return "not a CIFAR network"
     if spec.image_h != 32 or spec.image_w != 32 or spec.dense_in != 64:
         return "not a 32x32 CIFAR ResNet v2"
@@ -129,6 +143,19 @@ def check(eng) -> str:
         first = i % n == 0
         if (b.proj is not None) != first or b.stride != (2 if first and stage else 1):
             return "projection / stride layout is not the CIFAR v2 one"
+    return ""
+
+
+def check(eng) -> str:
+    """'' when the persistent kernels cover this engine's network, batch and device, else
+    the reason they do not: the network shape (shape_check), every host-side limit of the
+    three launches (slices, grids within the CUs, the head folds' LDS) and the co-residency
+    of both grids by the occupancy API in one native predicate (prn_check)."""
+    spec, nat = eng.spec, eng.nat
+    reason = shape_check(spec, eng.stem_s2d)
+    if reason:
+        return reason
+    nb = len(spec.blocks)
     cus = nat.cu_count()   # this process's CUs (its CU mask, apply_cu_partition)
     # (at least 16 CUs left for the weight-gradient workgroups, beside the overlap
     # plan's reserve for the comm stream; the backward slices by what is left)
@@ -374,3 +401,63 @@ class PersistStep:
         ints += list(BUCKET_OF_STAGE) if self.overlap else [-1, -1, -1]
         floats = [1.0 / eng.global_batch, bn_decay, bn_eps]
         return ptrs, ints, floats
+
+
+def infer_check(eng) -> str:
+    """'' when the persistent inference forward (prn_infer) covers this engine's network,
+    else the reason: the network shape (shape_check) or the native predicate's limits.
+    No batch, slice or CU limit: its workgroups are independent."""
+    reason = shape_check(eng.spec, eng.stem_s2d)
+    if reason:
+        return reason
+    if not eng.nat.prn_infer_supported(len(eng.spec.blocks), eng.spec.num_classes, eng.kpad):
+        return (f"unsupported head ({eng.spec.num_classes} classes padded to {eng.kpad}: "
+                "classes <= padded classes <= 128)")
+    return ""
+
+
+class PersistInfer:
+    """Descriptor tables of the persistent inference forward for one Engine: the PRN_BN /
+    PRN_BLOCK layouts of the training step, filled from ``eng.bns`` and the convs' OHWI
+    weights alone (the kernel reads gamma / beta / moving mean / moving variance and the
+    forward weights; every other pointer field stays 0).  Independent of PersistStep: an
+    engine whose training batch the persistent step does not cover still evaluates here,
+    at any eval batch."""
+
+    def __init__(self, eng):
+        reason = infer_check(eng)
+        if reason:
+            raise ValueError(reason)
+        self.eng = eng
+        nat, spec = eng.nat, eng.spec
+        sizes = nat.prn_struct_bytes()
+        assert sizes[:2] == [PRN_BN.itemsize, PRN_BLOCK.itemsize], sizes
+        blocks = spec.blocks
+        self.nblocks = len(blocks)
+        order = [bn for b in blocks for bn in b.bns] + [spec.final_bn]
+        bn_rows = np.zeros(len(order), dtype=PRN_BN)
+        for r, bs in zip(bn_rows, order):
+            e = eng.bns[bs.name]
+            r["gamma"], r["beta"], r["mmean"], r["mvar"] = e.gamma, e.beta, e.mmean, e.mvar
+        rows = np.zeros(self.nblocks, dtype=PRN_BLOCK)
+        for i, (r, b) in enumerate(zip(rows, blocks)):
+            r["w1f"] = eng.convs[b.convs[0].name].ohwi
+            r["w2f"] = eng.convs[b.convs[1].name].ohwi
+            if b.proj is not None:
+                r["wpf"] = eng.convs[b.proj.name].ohwi
+            r["stage"], r["stride"] = _stage(b), b.stride
+            r["bn1"], r["bn2"] = 2 * i, 2 * i + 1
+        self.bn_dev = self._dev(bn_rows)
+        self.block_dev = self._dev(rows)
+
+    def _dev(self, arr):
+        return torch.from_numpy(arr.view(np.uint8).copy()).to(self.eng.device)
+
+    def record(self, plan, x_in, logits, N: int, eps: float, pooled=None):
+        """Record the one launch into `plan`: images `x_in` [N][32][32][8] bf16 -> fp32
+        `logits` [N][kpad] (and, optionally, the bf16 pooled features [N][64])."""
+        eng, spec = self.eng, self.eng.spec
+        return plan.prn_infer(self.block_dev.data_ptr(), self.bn_dev.data_ptr(), x_in.data_ptr(),
+                              eng.convs[spec.stem.name].ohwi, eng.dense_ohwi, eng.dense_bias,
+                              logits.data_ptr(), 0 if pooled is None else pooled.data_ptr(),
+                              self.nblocks, N, spec.num_classes, eng.kpad, eps)

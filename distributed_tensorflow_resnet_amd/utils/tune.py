@@ -65,6 +65,14 @@ ENGINE = {
     "opt_fused": (1, "the persistent step's optimizer as ONE launch (split-K slab sums on "
                      "one GPU, SGD-momentum, both bf16 weight copies: sgd_tiles) instead of "
                      "the grouped slab reduce + sgd_pack + ohwi_pack"),
+    "persist_eval": (-1, "inference forward of the CIFAR networks (Engine.build_eval_plan: the "
+                         "evaluator, the predict tools, FrozenModel) as ONE persistent launch, "
+                         "one workgroup per image, plus the softmax launch, instead of ~105 "
+                         "per-layer launches: -1 auto = on wherever the network is supported "
+                         "(any batch, up to 128 padded classes) unless persist=0, 0 off, 1 on "
+                         "wherever supported (RN50 eval batch 450 -> 178 us at bs100, 371 -> "
+                         "169 us at bs1, 947 -> 356 us at bs512: "
+                         "profiles/cifar_persist_infer.md)"),
     "mat_bn_minc": (256, "... and from this many channels (ImageNet stages 3-4: +1.3 %)"),
 }
 

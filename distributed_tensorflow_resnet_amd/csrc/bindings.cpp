@@ -669,6 +669,23 @@ static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cp
   };
 }
 
+static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_t out,
+                                        ptr_t labels_out, ptr_t pos, int N, int H, int W, int Cpad,
+                                        long records, int rank, int world, int shuffle,
+                                        unsigned long long key_seed, int pad,
+                                        unsigned long long seed, int train, ptr_t crop_log,
+                                        ptr_t idx_log, ptr_t zero, long zero_bytes) {
+  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
+  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
+    throw std::invalid_argument("cifar_augment_resident: null buffer");
+  return [=](hipStream_t s) {
+    cifar_augment_resident(P<const uint8_t>(records_u8), P<const int>(labels_all), P<bf16>(out),
+                           P<int>(labels_out), P<const long long>(pos), N, H, W, Cpad, records,
+                           rank, world, shuffle, key_seed, pad, seed, train, P<int>(crop_log),
+                           P<int>(idx_log), P<void>(zero), zero_bytes, s);
+  };
+}
+
 static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
                                   unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
                                   long zero_bytes, int s2d) {
@@ -1241,6 +1258,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "memset", mk_memset);
   def_op(m, plan, "delay", mk_delay);
   def_op(m, plan, "cifar_augment", mk_cifar_augment);
+  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);

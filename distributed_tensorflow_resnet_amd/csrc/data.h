@@ -7,6 +7,19 @@ namespace dtr {
 void cifar_augment(const uint8_t* img, bf16* out, int N, int H, int W, int Cpad, int pad,
                    unsigned long long seed, const long long* gstep, int train, int* crop_log,
                    void* zero, long zero_bytes, hipStream_t s);   // zero: optional buffer to clear
+// cifar_augment on a device-resident split: workgroup n picks record
+// resident_index(key_seed, *pos, n, N, records, rank, world, shuffle) (data/cifar.py),
+// writes its label into labels_out[n] (and the index into idx_log[n] when given) and
+// augments it exactly as cifar_augment does with gstep = pos.  32x32, Cpad 8 only.
+void cifar_augment_resident(const uint8_t* records_u8, const int* labels_all, bf16* out,
+                            int* labels_out, const long long* pos, int N, int H, int W, int Cpad,
+                            long records, int rank, int world, int shuffle,
+                            unsigned long long key_seed, int pad, unsigned long long seed,
+                            int train, int* crop_log, int* idx_log, void* zero, long zero_bytes,
+                            hipStream_t s);
+// the argument checks of the above (std::invalid_argument), for plan recording
+void cifar_augment_resident_check(int N, int H, int W, int Cpad, long records, int rank,
+                                  int world, long zero_bytes);
 void imagenet_u8_pack(const uint8_t* img, bf16* out, int N, int H, int W,
                       unsigned long long seed, const long long* gstep, int train, void* zero,
                       long zero_bytes, int s2d,

@@ -29,22 +29,23 @@ __device__ __forceinline__ unsigned long long splitmix(unsigned long long x) {
 // per-image statistics, and writes each pixel as ONE 16-B NHWC row (3 channels +
 // zero padding).  Optionally zeroes a buffer in the same launch (the step's
 // BatchNorm accumulators), so the step needs no separate memset.
+//
+// cifar_augment_image is the body shared by cifar_augment_kernel (record n of a
+// batch buffer) and cifar_augment_resident_kernel (a record the workgroup picks
+// from the resident split): `src` is the image's 3072-B record, `step` the value
+// the crop/flip hash is keyed with.
 template <int CPAD>
-__global__ void __launch_bounds__(256)
-cifar_augment_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int pad,
-                     unsigned long long seed, const long long* gstep, int train, int* crop_log,
-                     uint4* __restrict__ zero, long zero_vec) {
+__device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ src,
+                                                    bf16* __restrict__ out, int n, int pad,
+                                                    unsigned long long seed,
+                                                    unsigned long long step, int train,
+                                                    int* crop_log, uint8_t* im, float* red) {
   constexpr int H = 32, W = 32, HW = H * W, CHW = 3 * HW, PPT = HW / 256;
-  __shared__ __attribute__((aligned(16))) uint8_t im[CHW];
-  __shared__ float red[8];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  for (long i = blockIdx.x * 256L + tid; i < zero_vec; i += (long)gridDim.x * 256)
-    zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  const int tid = threadIdx.x;
   if (tid < CHW / 16)
-    reinterpret_cast<uint4*>(im)[tid] = reinterpret_cast<const uint4*>(img + (long)n * CHW)[tid];
+    reinterpret_cast<uint4*>(im)[tid] = reinterpret_cast<const uint4*>(src)[tid];
   int oy = pad, ox = pad, flip = 0;
   if (train) {
-    const unsigned long long step = gstep ? (unsigned long long)*gstep : 0ull;
     const unsigned long long h = splitmix(seed ^ splitmix(step * 0x100000001B3ull + n));
     oy = (int)(h % (2 * pad + 1));
     ox = (int)((h >> 16) % (2 * pad + 1));
@@ -96,6 +97,104 @@ cifar_augment_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, in
     for (int c = 0; c < 3; ++c) r[c] = (bf16)((v[k][c] - mean) * inv);
     *reinterpret_cast<bf16x8*>(o + (long)p * CPAD) = r;
   }
+}
+
+template <int CPAD>
+__global__ void __launch_bounds__(256)
+cifar_augment_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int pad,
+                     unsigned long long seed, const long long* gstep, int train, int* crop_log,
+                     uint4* __restrict__ zero, long zero_vec) {
+  constexpr int CHW = 3 * 32 * 32;
+  __shared__ __attribute__((aligned(16))) uint8_t im[CHW];
+  __shared__ float red[8];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  for (long i = blockIdx.x * 256L + tid; i < zero_vec; i += (long)gridDim.x * 256)
+    zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
+  cifar_augment_image<CPAD>(img + (long)n * CHW, out, n, pad, seed, step, train, crop_log, im,
+                            red);
+}
+
+// ---- device-resident split: the workgroup picks its own record ----------------------
+// Batch position n of step `step` reads record resident_record(...) of the split: each
+// epoch (S = (records / world) / batch steps, the tail dropped) is one keyed permutation
+// of the record indices, cut into disjoint rank shards.  The permutation is a balanced
+// 4-round Feistel network over 2*hb bits with cycle walking; data/cifar.py
+// resident_index is the specification this must equal for every input.  Unshuffled
+// (the evaluator), a single rank also visits the tail batch, whose positions past the
+// end read the batch's first record.  Every operand is uniform over the workgroup.
+__device__ __forceinline__ unsigned resident_feistel(unsigned long long key, unsigned x, int hb) {
+  const unsigned mask = (1u << hb) - 1u;
+  unsigned L = x >> hb, R = x & mask;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const unsigned F =
+        (unsigned)splitmix(key ^ ((unsigned long long)(r + 1) << 40) ^ (unsigned long long)R) & mask;
+    const unsigned t = L ^ F;
+    L = R;
+    R = t;
+  }
+  return (L << hb) | R;
+}
+
+__device__ __forceinline__ int resident_record(unsigned long long step, int n, int batch,
+                                               int records, int rank, int world, int shuffle,
+                                               unsigned long long key_seed) {
+  const unsigned ur = (unsigned)records, ub = (unsigned)batch;
+  const unsigned S = (ur / (unsigned)world) / ub;               // host: S >= 1
+  const unsigned per_rank = S * ub;
+  // unshuffled on one rank: the epoch also has the tail batch
+  const unsigned steps = (!shuffle && world == 1) ? (ur + ub - 1u) / ub : S;
+  unsigned long long epoch;
+  unsigned k;
+  if ((step >> 32) == 0) {   // the usual case: one 32-bit division
+    const unsigned s32 = (unsigned)step;
+    epoch = s32 / steps;
+    k = s32 - (unsigned)epoch * steps;
+  } else {
+    epoch = step / steps;
+    k = (unsigned)(step - epoch * steps);
+  }
+  const unsigned first = (unsigned)rank * per_rank + k * ub;    // the batch's first position
+  unsigned p = first + (unsigned)n;
+  if (p >= ur) p = first < ur ? first : 0u;                     // tail batch (unshuffled)
+  if (!shuffle) return (int)p;
+  const unsigned r1 = ur - 1u;
+  const int bits = r1 ? 32 - __builtin_clz(r1) : 0;
+  const int hb = bits > 1 ? (bits + 1) >> 1 : 1;
+  const unsigned long long key = splitmix(key_seed ^ splitmix(epoch));
+  unsigned x = p;
+  do {
+    x = resident_feistel(key, x, hb);
+  } while (x >= ur);   // p < records and the network is a bijection: the walk returns
+  return (int)x;
+}
+
+__global__ void __launch_bounds__(256)
+cifar_augment_resident_kernel(const uint8_t* __restrict__ records_u8,
+                              const int* __restrict__ labels_all, bf16* __restrict__ out,
+                              int* __restrict__ labels_out, const long long* pos, int records,
+                              int rank, int world, int shuffle, unsigned long long key_seed,
+                              int pad, unsigned long long seed, int train, int* crop_log,
+                              int* idx_log, uint4* __restrict__ zero, long zero_vec) {
+  constexpr int CHW = 3 * 32 * 32;
+  __shared__ __attribute__((aligned(16))) uint8_t im[CHW];
+  __shared__ float red[8];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  // the one global read the record address waits for; the same value in every lane
+  const unsigned long long raw = pos ? (unsigned long long)*pos : 0ull;
+  for (long i = blockIdx.x * 256L + tid; i < zero_vec; i += (long)gridDim.x * 256)
+    zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)raw);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(raw >> 32));
+  const unsigned long long step = ((unsigned long long)hi << 32) | lo;
+  const int idx = resident_record(step, n, (int)gridDim.x, records, rank, world, shuffle, key_seed);
+  if (tid == 0) {
+    labels_out[n] = labels_all[idx];
+    if (idx_log) idx_log[n] = idx;
+  }
+  cifar_augment_image<8>(records_u8 + (long)idx * CHW, out, n, pad, seed, step, train, crop_log,
+                         im, red);
 }
 
 // Generic-shape fallback (any H, W, Cpad): one element per thread iteration.
@@ -170,6 +269,36 @@ void cifar_augment(const uint8_t* img, bf16* out, int N, int H, int W, int Cpad,
     hipLaunchKernelGGL(cifar_augment_generic_kernel, dim3(N), dim3(256), 0, s, img, out, H, W,
                        Cpad, pad, seed, gstep, train, crop_log, z, zv);
   DTR_CHECK_LAUNCH();
+}
+
+void cifar_augment_resident(const uint8_t* records_u8, const int* labels_all, bf16* out,
+                            int* labels_out, const long long* pos, int N, int H, int W, int Cpad,
+                            long records, int rank, int world, int shuffle,
+                            unsigned long long key_seed, int pad, unsigned long long seed,
+                            int train, int* crop_log, int* idx_log, void* zero, long zero_bytes,
+                            hipStream_t s) {
+  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
+  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
+    throw std::invalid_argument("cifar_augment_resident: null buffer");
+  if (reinterpret_cast<uintptr_t>(records_u8) % 16)
+    throw std::invalid_argument("cifar_augment_resident: records not 16-B aligned");
+  hipLaunchKernelGGL(cifar_augment_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
+                     labels_all, out, labels_out, pos, (int)records, rank, world, shuffle ? 1 : 0,
+                     key_seed, pad, seed, train, crop_log, idx_log, reinterpret_cast<uint4*>(zero),
+                     zero ? zero_bytes / 16 : 0);
+  DTR_CHECK_LAUNCH();
+}
+
+void cifar_augment_resident_check(int N, int H, int W, int Cpad, long records, int rank,
+                                  int world, long zero_bytes) {
+  if (H != 32 || W != 32 || Cpad != 8)
+    throw std::invalid_argument("cifar_augment_resident: only 32x32 images with Cpad 8");
+  if (N < 1 || world < 1) throw std::invalid_argument("cifar_augment_resident: batch, world >= 1");
+  if (rank < 0 || rank >= world) throw std::invalid_argument("cifar_augment_resident: rank >= world");
+  if (records >= (1L << 31)) throw std::invalid_argument("cifar_augment_resident: records >= 2^31");
+  if (records < (long)N * world)
+    throw std::invalid_argument("cifar_augment_resident: records < batch * world");
+  if (zero_bytes % 16) throw std::invalid_argument("cifar_augment_resident: zero_bytes % 16 != 0");
 }
 
 __global__ void pad_channels_kernel(const float* __restrict__ x, bf16* __restrict__ out, long npix,

@@ -141,6 +141,93 @@ class CifarData:
             epoch += 1
 
 
+# ---------------------------------------------------------------- resident split
+# The device-resident input (csrc/data.hip cifar_augment_resident_kernel) keeps the
+# whole split on the GPU and lets every workgroup pick its own record.  The functions
+# below are the specification of that choice: the kernel must equal resident_index for
+# every input.  The order is a pure function of (key_seed, step), so a resumed run
+# continues the same epoch at the same position.
+_M64 = (1 << 64) - 1
+
+
+def splitmix(x: int) -> int:
+    """The 64-bit finalizer of csrc/data.hip (splitmix64's output function)."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def resident_half_bits(records: int) -> int:
+    """Half width of the Feistel network: its 2*hb-bit domain covers `records`."""
+    return max(1, -(-(records - 1).bit_length() // 2))
+
+
+def resident_key(key_seed: int, epoch: int) -> int:
+    return splitmix((key_seed & _M64) ^ splitmix(epoch & _M64))
+
+
+def resident_perm(key: int, p: int, records: int) -> int:
+    """Position p < records -> record index: a balanced 4-round Feistel network over
+    2*hb bits, walked until the output falls inside [0, records) (cycle walking keeps
+    it a bijection of the records; the domain is at most 4x the record count)."""
+    if not 0 <= p < records:
+        raise ValueError(f"position {p} outside [0, {records})")
+    hb = resident_half_bits(records)
+    mask = (1 << hb) - 1
+    x = p
+    while True:
+        left, right = x >> hb, x & mask
+        for r in range(4):
+            f = splitmix(key ^ ((r + 1) << 40) ^ right) & mask
+            left, right = right, left ^ f
+        x = (left << hb) | right
+        if x < records:
+            return x
+
+
+def resident_steps_per_epoch(records: int, batch: int, world: int = 1) -> int:
+    """Batches per rank per epoch; the tail is dropped, as in CifarData.batches."""
+    s = (records // world) // batch
+    if s == 0:
+        raise ValueError(f"{records} records < batch {batch} x world {world}")
+    return s
+
+
+def resident_index(key_seed: int, step: int, n: int, batch: int, records: int, rank: int = 0,
+                   world: int = 1, shuffle: bool = True) -> int:
+    """Record read by batch position `n` of step `step` on `rank`.
+
+    Every epoch of S = (records // world) // batch steps is one permutation of the
+    records, keyed by (key_seed, epoch) and the same on every rank; rank r owns its
+    positions [r*S*batch, (r+1)*S*batch).  ``shuffle=False`` returns the position
+    itself; a single rank then also visits the tail batch (ceil(records / batch) steps
+    per epoch), whose positions at or past the end of the split read the batch's first
+    record -- how the evaluator pads a short last batch."""
+    if not (0 <= n < batch and 0 <= rank < world and step >= 0):
+        raise ValueError("need 0 <= n < batch, 0 <= rank < world, step >= 0")
+    if records >= 1 << 31:
+        raise ValueError("records must be < 2**31")
+    s = resident_steps_per_epoch(records, batch, world)
+    per_rank = s * batch
+    steps = -(-records // batch) if (not shuffle and world == 1) else s
+    epoch, k = divmod(step, steps)
+    first = rank * per_rank + k * batch
+    p = first + n
+    if p >= records:   # tail batch (unshuffled, one rank)
+        p = first
+    if not shuffle:
+        return p
+    return resident_perm(resident_key(key_seed, epoch), p, records)
+
+
+def resident_batch(key_seed: int, step: int, batch: int, records: int, rank: int = 0,
+                   world: int = 1, shuffle: bool = True) -> np.ndarray:
+    """resident_index for n = 0..batch-1 -> int64 [batch]."""
+    return np.array([resident_index(key_seed, step, n, batch, records, rank, world, shuffle)
+                     for n in range(batch)], dtype=np.int64)
+
+
 def synthetic_batches(batch_size: int, num_classes: int = 10, seed: int = 0):
     """Endless random uint8 CIFAR-shaped records (for --synthetic)."""
     g = torch.Generator().manual_seed(seed)

@@ -291,3 +291,41 @@ def cifar_augment(img_u8, cpad=8, pad=4, seed=0, gstep=None, train=True, log_cro
     native().cifar_augment(img_u8.data_ptr(), out.data_ptr(), N, H, W, cpad, pad, seed,
                            _ptr(gstep), int(train), _ptr(log), 0, 0, _stream())
     return (out, log) if log_crops else out
+
+
+def cifar_augment_resident(records_u8, labels_all, pos, batch, cpad=8, pad=4, seed=0, key_seed=0,
+                           rank=0, world=1, shuffle=True, train=True, zero=None, log_crops=False,
+                           log_index=False):
+    """cifar_augment on a device-resident split: batch position n reads record
+    data.cifar.resident_index(key_seed, pos, n, batch, records, rank, world, shuffle).
+
+    records_u8 [M,3,32,32] uint8, labels_all [M] int32, pos [1] int64 (the step), all on
+    the GPU; ``zero``: an optional buffer cleared in the same launch.  Returns (out bf16
+    [batch,32,32,cpad], labels int32 [batch]) followed by the crop log [batch,3] and the
+    index log [batch] (int32) when asked for."""
+    if records_u8.dtype != torch.uint8 or not records_u8.is_cuda or records_u8.dim() != 4 \
+            or not records_u8.is_contiguous():
+        raise ValueError("records must be a contiguous uint8 GPU tensor [M,3,H,W]")
+    M, _, H, W = records_u8.shape
+    if labels_all.dtype != torch.int32 or not labels_all.is_cuda or labels_all.numel() != M \
+            or not labels_all.is_contiguous():
+        raise ValueError("labels must be a contiguous int32 GPU tensor [M]")
+    if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() != 1:
+        raise ValueError("pos must be an int64 GPU tensor [1]")
+    dev = records_u8.device
+    out = torch.empty((batch, H, W, cpad), device=dev, dtype=BF16)
+    labels = torch.empty(batch, device=dev, dtype=torch.int32)
+    crops = torch.zeros((batch, 3), device=dev, dtype=torch.int32) if log_crops else None
+    idx = torch.zeros(batch, device=dev, dtype=torch.int32) if log_index else None
+    zbytes = zero.numel() * zero.element_size() if zero is not None else 0
+    native().cifar_augment_resident(records_u8.data_ptr(), labels_all.data_ptr(), out.data_ptr(),
+                                    labels.data_ptr(), pos.data_ptr(), batch, H, W, cpad, M, rank,
+                                    world, int(bool(shuffle)), key_seed & (2 ** 64 - 1), pad, seed,
+                                    int(train), _ptr(crops), _ptr(idx), _ptr(zero), zbytes,
+                                    _stream())
+    res = (out, labels)
+    if log_crops:
+        res += (crops,)
+    if log_index:
+        res += (idx,)
+    return res

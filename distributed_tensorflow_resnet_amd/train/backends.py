@@ -214,8 +214,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  lr_schedule, optimizer: str = "mom", seed: int = 0, dist_ctx=None,
                  bucket_mb: float | None = None, use_graph: bool = False, global_batch=None,
                  input_mode: str = "auto", data_seed: int = 1234,
-                 allreduce_dtype: str = "fp32"):
-    """device: gpu | cpu | auto."""
+                 allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0):
+    """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
+    (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
         device = "gpu" if torch.cuda.is_available() else "cpu"
     if device == "gpu":
@@ -227,8 +228,11 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      optimizer=optimizer, device=torch.device("cuda", local), dist_ctx=dist_ctx,
                      bucket_mb=bucket_mb, seed=seed, input_mode=input_mode,
                      global_batch=global_batch, use_graph=use_graph, data_seed=data_seed,
-                     allreduce_dtype=allreduce_dtype)
+                     allreduce_dtype=allreduce_dtype, resident=resident,
+                     shuffle_seed=shuffle_seed)
         return GPUBackend(eng, use_graph=use_graph)
+    if resident is not None:
+        raise ValueError("a device-resident split needs the GPU backend")
     return CPUBackend(spec, batch_size, weight_decay=weight_decay, lr_schedule=lr_schedule,
                       optimizer=optimizer, seed=seed, dist_ctx=dist_ctx,
                       global_batch=global_batch, allreduce_dtype=allreduce_dtype)

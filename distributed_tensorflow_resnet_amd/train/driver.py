@@ -103,8 +103,34 @@ def _eval_batches_factory(flags, spec):
                                      workers=flags.num_parallel_calls)
 
 
+def resident_requested(flags, spec, device: str, data_path: str) -> bool:
+    """--resident_data is honoured for real CIFAR data on the GPU; elsewhere it is
+    ignored with a log line."""
+    if not flags.resident_data:
+        return False
+    why = ("not a CIFAR dataset" if not spec.dataset.startswith("cifar") else
+           "not on the GPU" if device != "gpu" else
+           "--synthetic" if flags.synthetic else
+           "no data path" if not data_path else "")
+    if why:
+        H.log(f"[flags] --resident_data ignored: {why}")
+    return not why
+
+
 def run_eval(flags, spec, device: str):
     model = make_inference(spec, flags.eval_batch_size, device)
+    if resident_requested(flags, spec, device, flags.eval_data_path):
+        from ..data.cifar import CifarData
+
+        data = CifarData(flags.eval_data_path, spec.dataset, train=False)
+        # the batches the host loader yields: the tail that fills no batch is dropped
+        full = len(data) // flags.eval_batch_size * flags.eval_batch_size
+        if full:
+            model.attach(data.images[:full], data.labels[:full])
+            H.log(f"INFO:tensorflow:resident eval data: {full} records, "
+                  f"{full // flags.eval_batch_size} batches, {full * 3072} bytes on the device")
+        else:
+            H.log(f"[flags] --resident_data ignored: {len(data)} eval records fill no batch")
     ev = SidecarEvaluator(model, _eval_batches_factory(flags, spec), flags.train_dir,
                           flags.eval_dir or None, flags.eval_batch_count, flags.eval_once,
                           flags.eval_interval_secs,
@@ -177,17 +203,35 @@ def main(argv=None, kind: str = "cifar") -> int:
     sched = lr_values_scaled(scaled(sched, flags.lr_schedule_scale), flags.lr_value_scale)
     # real ImageNet on the GPU: uint8 crops from the workers, flip/mean/bf16 pack on device
     u8 = device == "gpu" and spec.dataset == "imagenet" and not flags.synthetic
+    # --resident_data: the whole CIFAR split on the device, shuffled there by (--seed,
+    # global_step) -- the same seed on every rank, so the rank shards are disjoint
+    resident = None
+    if resident_requested(flags, spec, device, flags.train_data_path):
+        from ..data.cifar import CifarData
+
+        data = CifarData(flags.train_data_path, spec.dataset, train=True)
+        resident = (data.images, data.labels)
     backend = make_backend(spec, flags.batch_size, device=device, weight_decay=flags.weight_decay,
                            lr_schedule=sched, optimizer=flags.optimizer, seed=flags.seed,
                            dist_ctx=dp_ctx, bucket_mb=flags.bucket_mb, use_graph=flags.use_graph,
                            data_seed=1234 + rank, allreduce_dtype=flags.allreduce_dtype,
-                           input_mode="imagenet_u8" if u8 else "auto")
+                           input_mode=("imagenet_u8" if u8 else
+                                       "cifar_resident" if resident is not None else "auto"),
+                           resident=resident, shuffle_seed=flags.seed)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason
-    it = _train_batches(flags, spec, rank, world, u8=u8)
+    stop_step = flags.train_steps
+    it = None if resident is not None else _train_batches(flags, spec, rank, world, u8=u8)
     feeder = None
-    if it is None:
+    if resident is not None:
+        # no feeder: the step's input launch reads the split; --num_epochs, which ends the
+        # host loader's iterator, becomes a stop step
+        stop_step = min(flags.train_steps, flags.num_epochs * eng.steps_per_epoch)
+        H.log(f"INFO:tensorflow:resident data: {eng.records} records, "
+              f"{eng.steps_per_epoch} steps per epoch, {eng.records * 3072} bytes on the "
+              f"device; stopping at step {stop_step}")
+    elif it is None:
         if device == "gpu":
             backend.engine.fill_synthetic(seed=flags.seed + rank)
         else:
@@ -206,7 +250,7 @@ def main(argv=None, kind: str = "cifar") -> int:
     hooks = [H.LearningRateSetterHook(sched),
              H.LoggingTensorHook(flags.log_every, prec_key),
              H.StepCounterHook(100, gb, writer),
-             H.StopAtStepHook(flags.train_steps)]
+             H.StopAtStepHook(stop_step)]
     chief_hooks = []
     if writer is not None:
         chief_hooks.append(H.SummarySaverHook(writer, flags.summary_every,

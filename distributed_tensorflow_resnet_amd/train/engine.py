@@ -239,6 +239,25 @@ class _Conv:
     name: str = ""
 
 
+def upload_resident(split, spec: ModelSpec, device):
+    """(images uint8 [M,3,32,32], labels [M]) as host arrays or tensors -> the device
+    copies the resident input kernel reads: contiguous uint8 records + int32 labels."""
+    images, labels = split
+    images = torch.as_tensor(images)
+    labels = torch.as_tensor(labels)
+    if images.dtype != torch.uint8 or images.dim() != 4 or \
+            tuple(images.shape[1:]) != (3, spec.image_h, spec.image_w) or \
+            (spec.image_h, spec.image_w) != (32, 32):
+        raise ValueError("resident split: images must be uint8 [M,3,32,32], got "
+                         f"{images.dtype} {tuple(images.shape)}")
+    if labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+        raise ValueError("resident split: one label per image")
+    if not 0 < images.shape[0] < 2 ** 31:
+        raise ValueError("resident split: need 0 < records < 2**31")
+    return (images.to(device).contiguous(),
+            labels.to(device=device, dtype=torch.int32).contiguous())
+
+
 class Engine:
     """Owns all device state of one data-parallel rank."""
 
@@ -248,7 +267,8 @@ class Engine:
                  seed: int = 0,
                  input_mode: str = "auto", global_batch: int | None = None,
                  use_graph: bool = False, data_seed: int = 1234, fork_wgrad: bool | None = None,
-                 allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None):
+                 allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None,
+                 resident=None, shuffle_seed: int = 0):
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
@@ -297,6 +317,23 @@ class Engine:
         if input_mode == "auto":
             input_mode = "cifar_u8" if spec.dataset.startswith("cifar") else "nhwc"
         self.input_mode = input_mode
+        # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
+        # the device and the step's input launch picks its own records through the keyed
+        # permutation of global_step (data/cifar.py resident_index; csrc/data.hip).  Uploaded
+        # once, here, because the plan holds fixed pointers.  ``shuffle_seed`` is the job's,
+        # the same on every rank (disjoint rank shards); data_seed keeps seeding the crops.
+        self.rank = dist_ctx.rank if dist_ctx is not None else 0
+        self.shuffle_seed = int(shuffle_seed)
+        self.records_u8 = self.labels_all = None
+        if input_mode == "cifar_resident":
+            if resident is None:
+                raise ValueError("input_mode='cifar_resident' needs resident=(images, labels)")
+            self.records_u8, self.labels_all = upload_resident(resident, spec, self.device)
+            from ..data.cifar import resident_steps_per_epoch
+            self.records = int(self.records_u8.shape[0])
+            self.steps_per_epoch = resident_steps_per_epoch(self.records, batch_size, self.world)
+        elif resident is not None:
+            raise ValueError("resident= is only for input_mode='cifar_resident'")
         self.kpad = _ceil(spec.num_classes, 16) * 16
         self.cpad_in = 8
         # ImageNet stem as a space-to-depth 4x4/1 conv over [N, H/2, W/2, 16] (data.hip
@@ -1166,6 +1203,17 @@ class Engine:
         return t
 
     # ------------------------------------------------------------------ plan
+    def _record_resident_input(self, plan, zero):
+        """The step's input launch in cifar_resident mode: in place of cifar_augment, with
+        the same `zero` arguments; records and labels are picked on the device from
+        global_step, so the step (and its hipGraph) needs nothing from the host."""
+        spec = self.spec
+        plan.cifar_augment_resident(
+            self.records_u8.data_ptr(), self.labels_all.data_ptr(), self.x_in.data_ptr(),
+            self.labels.data_ptr(), self.gstep.data_ptr(), self.N, spec.image_h, spec.image_w,
+            self.cpad_in, self.records, self.rank, self.world, 1,
+            self.shuffle_seed & (2 ** 64 - 1), 4, self.data_seed, 1, 0, 0, *zero)
+
     def _build_train_plan(self):
         if self.persist:
             return self._build_persist_plan()
@@ -1180,13 +1228,15 @@ class Engine:
         # kernel (no extra launch), else by a memset
         zero = (self.bn_acc.data_ptr(), self.bn_acc.numel() * 8) \
             if (self.bn_acc_on or self.bn_bacc_on) else (0, 0)
-        if zero[0] and self.input_mode not in ("cifar_u8", "imagenet_u8"):
+        if zero[0] and self.input_mode not in ("cifar_u8", "cifar_resident", "imagenet_u8"):
             plan.memset(*zero)
         # ---- input
         if self.input_mode == "cifar_u8":
             plan.cifar_augment(self.img_u8.data_ptr(), self.x_in.data_ptr(), N, spec.image_h,
                                spec.image_w, self.cpad_in, 4, self.data_seed,
                                self.gstep.data_ptr(), 1, 0, *zero)
+        elif self.input_mode == "cifar_resident":
+            self._record_resident_input(plan, zero)
         elif self.input_mode == "imagenet_u8":
             plan.imagenet_u8_pack(self.img_u8.data_ptr(), self.x_in.data_ptr(), N, spec.image_h,
                                   spec.image_w, self.data_seed, self.gstep.data_ptr(), 1, *zero,
@@ -1501,6 +1551,8 @@ class Engine:
             plan.cifar_augment(self.img_u8.data_ptr(), self.x_in.data_ptr(), N, spec.image_h,
                                spec.image_w, self.cpad_in, 4, self.data_seed,
                                self.gstep.data_ptr(), 1, 0, *zero)
+        elif self.input_mode == "cifar_resident":
+            self._record_resident_input(plan, zero)
         else:
             plan.memset(*zero)
         ptrs, ints, floats = self.prn.args(self.prn_pool, self.prn_bar, BN_DECAY, BN_EPS, fwd=True)
@@ -1855,6 +1907,7 @@ class Engine:
     # ------------------------------------------------------------------ io
     def set_batch(self, images, labels):
         """Copy a host/device batch into the static input buffers."""
+        self._no_host_input("set_batch")
         if self.input_mode in ("cifar_u8", "imagenet_u8"):
             self.img_u8.copy_(images, non_blocking=True)
         else:
@@ -1864,7 +1917,14 @@ class Engine:
             self.x_in.copy_(x, non_blocking=True)
         self.labels.copy_(labels.to(torch.int32), non_blocking=True)
 
+    def _no_host_input(self, what: str):
+        if self.input_mode == "cifar_resident":
+            raise RuntimeError(
+                f"{what}: input_mode='cifar_resident' takes no batches from the host -- the "
+                "plan reads its records and labels from the device-resident split")
+
     def fill_synthetic(self, seed: int = 0):
+        self._no_host_input("fill_synthetic")
         g = torch.Generator(device="cpu").manual_seed(seed)
         if self.input_mode in ("cifar_u8", "imagenet_u8"):
             self.img_u8.copy_(torch.randint(0, 256, tuple(self.img_u8.shape), generator=g,
@@ -1967,6 +2027,7 @@ class _EvalPlan:
         p = nat.Plan()
         self.plan = p
         self.input_plan = nat.Plan()
+        self.resident_plan = None   # attach(): the input plan of a device-resident split
         if not eng.stem_s2d:   # raw uint8 CIFAR records (run(raw_u8=True))
             self.input_plan.cifar_augment(self.img_u8.data_ptr(), self.x_in.data_ptr(), N, H, W,
                                           eng.cpad_in, 4, 0, 0, 0, 0, 0, 0)
@@ -1983,6 +2044,38 @@ class _EvalPlan:
         p.softmax_xent(self.logits.data_ptr(), eng.kpad, self.labels.data_ptr(), N,
                        spec.num_classes, sp, sp + 4, 0, 0, 1.0, self.probs.data_ptr(),
                        self.xent_ws.data_ptr())
+
+    def attach(self, images, labels):
+        """Keep a whole eval split (uint8 [M,3,32,32] + labels) on the device:
+        run_resident(i) then scores batch i with no per-batch image copy.  The resident
+        input plan reads the batch index from `batch_pos`, an int64 counter this plan
+        owns, unshuffled -- positions at or past the end of the split (the tail batch)
+        read the batch's first record, the padding GPUInference.run gives a short batch."""
+        eng, N = self.eng, self.N
+        if eng.stem_s2d:
+            raise ValueError("resident eval split: CIFAR records only")
+        self.records_u8, self.labels_all = upload_resident((images, labels), eng.spec, eng.device)
+        self.records = int(self.records_u8.shape[0])
+        self.batch_pos = torch.zeros(1, dtype=torch.int64, device=eng.device)
+        self.resident_plan = eng.nat.Plan()
+        self.resident_plan.cifar_augment_resident(
+            self.records_u8.data_ptr(), self.labels_all.data_ptr(), self.x_in.data_ptr(),
+            self.labels.data_ptr(), self.batch_pos.data_ptr(), N, eng.spec.image_h,
+            eng.spec.image_w, eng.cpad_in, self.records, 0, 1, 0, 0, 4, 0, 0, 0, 0, 0, 0)
+
+    @property
+    def resident_batches(self) -> int:
+        """Batches of the attached split, the tail batch included."""
+        return -(-self.records // self.N)
+
+    def run_resident(self, batch_index: int):
+        """run() on batch `batch_index` of the attached split (see attach)."""
+        if not 0 <= batch_index < self.resident_batches:
+            raise IndexError(f"batch {batch_index} of {self.resident_batches}")
+        st = torch.cuda.current_stream().cuda_stream
+        self.batch_pos.fill_(batch_index)   # a device fill: no synchronous copy
+        self.resident_plan.run(0, self.resident_plan.size(), st, 0)
+        return self.run()
 
     def _record_layers(self, p):
         """The launch-per-layer forward: bn_eval per BatchNorm, conv_gemm per conv, pool,

@@ -60,6 +60,34 @@ class GPUInference:
                                              labels.to(self.engine.device), raw_u8=raw)
         return loss, correct, probs
 
+    # ---- device-resident eval split (CIFAR): no per-batch image copy
+    def attach(self, images, labels):
+        """Upload a whole eval split (uint8 [M,3,32,32] + labels) once; evaluate_checkpoint
+        then scores it through run_resident."""
+        self.plan.attach(images, labels)
+
+    @property
+    def attached(self) -> bool:
+        return self.plan.resident_plan is not None
+
+    def resident_batch_sizes(self):
+        """Valid rows of every batch of the attached split (the last may be short)."""
+        M, full = self.plan.records, self.engine.N
+        return [min(full, M - i * full) for i in range(self.plan.resident_batches)]
+
+    def run_resident(self, batch_index: int, n_valid: int):
+        """run() on batch `batch_index` of the attached split, `n_valid` rows of it real
+        (the plan pads a short last batch with the batch's first record)."""
+        loss, correct, probs = self.plan.run_resident(batch_index)
+        full = self.engine.N
+        if n_valid < full:   # as run(): loss / correct from the valid rows' probabilities
+            p = probs[:n_valid].float()
+            y = self.plan.labels[:n_valid].long()
+            loss = float(-torch.log(p.gather(1, y[:, None]).clamp_min(1e-30)).sum())
+            correct = float((p.argmax(1) == y).sum())
+            return loss, correct, probs[:n_valid]
+        return loss, correct, probs
+
 
 class CPUInference:
     def __init__(self, spec, batch_size: int):
@@ -82,11 +110,20 @@ def make_inference(spec, batch_size: int, device: str = "auto"):
 
 
 def evaluate_checkpoint(model, prefix: str, batches, eval_batch_count: int):
-    """Restore `prefix`, score up to eval_batch_count batches -> (precision, loss, step)."""
+    """Restore `prefix`, score up to eval_batch_count batches -> (precision, loss, step).
+    A model with an attached device-resident split (GPUInference.attach) scores that
+    split's batches, in order, instead of `batches()`."""
     tensors = tb.read_bundle(prefix)
     model.load(tensors)
     step = int(tensors.get("global_step", 0))
     total = correct = loss = 0.0
+    if getattr(model, "attached", False):   # the split already lives on the device
+        for i, n in enumerate(model.resident_batch_sizes()[:eval_batch_count]):
+            l, c, _ = model.run_resident(i, n)
+            loss += l
+            correct += c
+            total += n
+        return (correct / max(total, 1.0)), (loss / max(total, 1.0)), step
     for i, (x, y) in enumerate(batches()):
         if i >= eval_batch_count:
             break

@@ -9,6 +9,7 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --resnet_size      (reference hard-codes 50, resnet_model.py:72,74 -- defect #8)
   --dtype            bf16 (GPU compute) | fp32 (CPU path)
   --synthetic        synthetic data of the dataset's shape
+  --resident_data    CIFAR split resident on the GPU, shuffled on the device
   --bucket_mb        gradient all-reduce bucket size
   --device           auto | gpu | cpu
   --use_graph        capture the training step in a hipGraph
@@ -131,6 +132,11 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
     p.add_argument("--device", default="auto", choices=("auto", "gpu", "cpu"))
     p.add_argument("--dtype", default="bf16", choices=("bf16", "fp32"))
     p.add_bool("synthetic", False, "Synthetic data of the dataset's shape.")
+    p.add_bool("resident_data", False,
+               "CIFAR on the GPU, real data: keep the whole split on the device and let the "
+               "step's input launch pick its records through a keyed permutation of "
+               "global_step (no per-step host work; the order is a function of --seed and "
+               "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
     p.add_argument("--optimizer", default="mom", choices=("mom", "sgd"))
     p.add_argument("--bucket_mb", type=float, default=0.0,

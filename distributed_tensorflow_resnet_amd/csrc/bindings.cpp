@@ -16,6 +16,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -26,6 +27,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "comm.h"
@@ -468,49 +470,64 @@ static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, floa
   return [a](hipStream_t s) { head_fused(a, s); };
 }
 
-// Persistent small-batch CIFAR step (cifar_persist.hip).  mode 0: forward launch, 1:
-// backward launch.  ptrs = [blocks, bns, x_in, stem_w, pool_acc, bar, err, dense_w,
-// dense_b, labels, pooled, dlogits, ws, dpool, dx0, items]; ints = [nblocks, nitems, N, P,
-// classes, kpad, update_moving, wgrad_wgs, fault_bar, overlap, bucket of stage 0, 1, 2];
-// floats = [grad_scale, momentum, eps].
-static Launch mk_prn(int mode, std::vector<ptr_t> p, std::vector<int> n, std::vector<float> f) {
-  if (p.size() != 20 || n.size() != 13 || f.size() != 3)
-    throw std::invalid_argument("prn: 20 pointers, 13 ints, 3 floats");
+// Persistent small-batch CIFAR step (prn_fwd.hip, prn_bwd.hip).  mode 0: forward launch,
+// 1: backward launch, 2: head folds.  `args` is keyed by the PrnArgs member names
+// (pointers as integers; bucket_of_stage a 3-sequence) plus wgrad_wgs, the backward's
+// weight-gradient workgroups; probe and shards are set by the launch functions.  A
+// missing key and a key that is no PrnArgs member both raise, naming the key.
+static Launch mk_prn(int mode, py::dict args) {
+  std::vector<std::string> known;
+  auto get = [&](const char* key) -> py::object {
+    if (!args.contains(key)) throw std::invalid_argument(std::string("prn: missing key '") + key + "'");
+    known.push_back(key);
+    return args[key];
+  };
   PrnArgs a{};
-  a.blocks = P<const PrnBlock>(p[0]);
-  a.bns = P<const PrnBn>(p[1]);
-  a.x_in = P<const bf16>(p[2]);
-  a.stem_w = P<const bf16>(p[3]);
-  a.pool_acc = P<double>(p[4]);
-  a.bar = P<unsigned>(p[5]);
-  a.err = P<int>(p[6]);
-  a.dense_w = P<const bf16>(p[7]);
-  a.dense_b = P<const float>(p[8]);
-  a.labels = P<const int>(p[9]);
-  a.pooled = P<bf16>(p[10]);
-  a.dlogits = P<bf16>(p[11]);
-  a.ws = P<float>(p[12]);
-  a.dpool = P<float>(p[13]);
-  a.dx0 = P<bf16>(p[14]);
-  a.items = P<const PrnItem>(p[15]);
-  a.loss_sum = P<float>(p[16]);
-  a.correct = P<float>(p[17]);
-  a.dbias = P<float>(p[18]);
-  a.dense_grad = P<float>(p[19]);
-  a.nblocks = n[0];
-  a.nitems = n[1];
-  a.N = n[2];
-  a.P = n[3];
-  a.classes = n[4];
-  a.kpad = n[5];
-  a.update_moving = n[6];
-  const int wgs = n[7];
-  a.fault_bar = n[8];
-  a.overlap = n[9];
-  for (int i = 0; i < 3; ++i) a.bucket_of_stage[i] = n[10 + i];
-  a.grad_scale = f[0];
-  a.momentum = f[1];
-  a.eps = f[2];
+#define PRN_PTR(name) a.name = P<std::remove_pointer_t<decltype(a.name)>>(get(#name).cast<ptr_t>())
+#define PRN_VAL(name) a.name = get(#name).cast<decltype(a.name)>()
+  PRN_PTR(blocks);
+  PRN_PTR(bns);
+  PRN_PTR(x_in);
+  PRN_PTR(stem_w);
+  PRN_PTR(pool_acc);
+  PRN_PTR(bar);
+  PRN_PTR(err);
+  PRN_PTR(dense_w);
+  PRN_PTR(dense_b);
+  PRN_PTR(labels);
+  PRN_PTR(pooled);
+  PRN_PTR(dlogits);
+  PRN_PTR(ws);
+  PRN_PTR(dpool);
+  PRN_PTR(loss_sum);
+  PRN_PTR(correct);
+  PRN_PTR(dbias);
+  PRN_PTR(dense_grad);
+  PRN_PTR(dx0);
+  PRN_PTR(items);
+  PRN_VAL(nblocks);
+  PRN_VAL(nitems);
+  PRN_VAL(N);
+  PRN_VAL(P);
+  PRN_VAL(classes);
+  PRN_VAL(kpad);
+  PRN_VAL(grad_scale);
+  PRN_VAL(momentum);
+  PRN_VAL(eps);
+  PRN_VAL(update_moving);
+  PRN_VAL(overlap);
+  PRN_VAL(fault_bar);
+#undef PRN_PTR
+#undef PRN_VAL
+  const auto bos = get("bucket_of_stage").cast<std::vector<int>>();
+  if (bos.size() != 3) throw std::invalid_argument("prn: bucket_of_stage needs 3 entries");
+  for (int i = 0; i < 3; ++i) a.bucket_of_stage[i] = bos[i];
+  const int wgs = get("wgrad_wgs").cast<int>();
+  for (auto kv : args) {   // (every key read above exists, so any other is unknown)
+    const std::string key = py::str(kv.first);
+    if (std::find(known.begin(), known.end(), key) == known.end())
+      throw std::invalid_argument("prn: unknown key '" + key + "' (not a PrnArgs member)");
+  }
   if (!prn_supported(a.N, a.P, a.nblocks, a.classes, a.kpad))
     throw std::invalid_argument("prn: unsupported shape");
   if (mode == 0) return [a](hipStream_t s) { prn_forward(a, s); };
@@ -519,7 +536,7 @@ static Launch mk_prn(int mode, std::vector<ptr_t> p, std::vector<int> n, std::ve
   throw std::invalid_argument("prn: mode 0 (forward), 1 (backward) or 2 (head folds)");
 }
 
-// Persistent inference forward (cifar_persist.hip prn_infer): one launch, one workgroup per
+// Persistent inference forward (prn_infer.hip): one launch, one workgroup per
 // image, moving-average BatchNorm; fp32 logits [N][kpad] (columns >= classes 0) and,
 // when `pooled` is non-zero, the pooled features [N][64].
 static Launch mk_prn_infer(ptr_t blocks, ptr_t bns, ptr_t x_in, ptr_t stem_w, ptr_t dense_w,

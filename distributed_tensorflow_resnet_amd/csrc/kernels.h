@@ -212,7 +212,7 @@ void conv_ring(const GemmArgs& a, int mode, int flags, dim3 grid, hipStream_t s)
 bool conv_gemm_uses_ring(const GemmArgs& a, int mode);
 int conv_gemm_bn(int M, int Ncol);   // column tile of the kernel conv_gemm() picks
 
-// ---- Persistent small-batch CIFAR step (cifar_persist.hip) ----
+// ---- Persistent small-batch CIFAR step (prn_device.h, prn_fwd.hip, prn_bwd.hip, prn_infer.hip) ----
 // The whole CIFAR ResNet v2 (6n+2, building blocks, 16/32/64 channels on 32/16/8 maps;
 // resnet_model_official.py:217-278) forward in ONE launch and its backward in ONE
 // launch.  Each image is split into P row slices, one 512-thread workgroup per slice,
@@ -277,7 +277,7 @@ struct PrnArgs {
   unsigned* bar;             // [prn_bar_words()], 128-B aligned: sharded arrival counters
                              // (forward, backward), the backward readiness count and the
                              // weight-gradient item queue, each on its own lines -- zeroed
-                             // every step (cifar_persist.hip PRN_FWD .. PRN_QUEUE)
+                             // every step (prn_device.h PRN_FWD .. PRN_QUEUE)
   int* err;                  // set when a barrier wait times out
   const bf16* dense_w;       // [64][kpad] bf16 HWIO
   const float* dense_b;

@@ -69,7 +69,7 @@ OPT_TILE_LOADS = 2048   # a sgd_tiles workgroup's slab loads: <= 8 16-byte loads
 
 
 class PersistentStepError(RuntimeError):
-    """A persistent CIFAR launch's grid barrier timed out (csrc/cifar_persist.hip: every
+    """A persistent CIFAR launch's grid barrier timed out (csrc/prn_device.h: every
     wait is bounded, a timed-out workgroup sets the error flag and exits).  The step's
     results are invalid; the driver exits with code 3 so parallel/launch.py restarts the
     job from the last good checkpoint, on the per-layer plan."""
@@ -379,7 +379,7 @@ class Engine:
                           else None)
         self._build_weight_layout()
         self._alloc_activations()
-        # Persistent small-batch CIFAR step (train/persist.py, csrc/cifar_persist.hip): the
+        # Persistent small-batch CIFAR step (train/persist.py, csrc/prn_*.hip): the
         # forward and the backward each as ONE launch (tune persist: -1 auto = per-rank
         # batch <= AUTO_MAX_BATCH on a supported CIFAR network, 0 off, 1 whenever supported)
         from . import persist as _persist
@@ -1555,9 +1555,8 @@ class Engine:
             self._record_resident_input(plan, zero)
         else:
             plan.memset(*zero)
-        ptrs, ints, floats = self.prn.args(self.prn_pool, self.prn_bar, BN_DECAY, BN_EPS, fwd=True)
-        plan.prn(0, ptrs, ints, floats)
-        ptrs, ints, floats = self.prn.args(self.prn_pool, self.prn_bar, BN_DECAY, BN_EPS)
+        plan.prn(0, self.prn.args(self.prn_pool, self.prn_bar, BN_DECAY, BN_EPS, fwd=True))
+        args = self.prn.args(self.prn_pool, self.prn_bar, BN_DECAY, BN_EPS)
         self.seg["fwd"] = (b0, plan.size())
 
         b1 = plan.size()
@@ -1570,7 +1569,7 @@ class Engine:
         self._reduce_main = True   # the slab reduces run on the main stream
         self._produced.add(self.dense_name)
         if self.prn.overlap:
-            early = self._emit_persist_overlap(plan, ptrs, ints, floats)
+            early = self._emit_persist_overlap(plan, args)
             self.seg["bwd"] = (b1, plan.size())
             if self.opt_fused:   # the rest: the last bucket's segments
                 self._emit_optimizer(plan, fused_slabs={}, gin=self._packed_gin(),
@@ -1578,10 +1577,10 @@ class Engine:
             else:
                 self._emit_optimizer(plan)
             return
-        plan.prn(1, ptrs, ints, floats)
+        plan.prn(1, args)
         # the head's batch folds (loss, precision, dense bias and weight gradients): one
         # workgroup on the main stream -- no side stream, no fork/join events
-        plan.prn(2, ptrs, ints, floats)
+        plan.prn(2, args)
         # every slab is complete when the backward launch ends, and that launch holds
         # every CU (nothing can overlap it): ONE grouped reduce of all the slabs, then
         # (world > 1) ONE all-reduce of the whole gradient -- the per-bucket launches of
@@ -1618,7 +1617,7 @@ class Engine:
             self._emit_reduce(plan, list(slabs))
             self.seg["gsum"] = (b4, plan.size())
 
-    def _emit_persist_overlap(self, plan, ptrs, ints, floats):
+    def _emit_persist_overlap(self, plan, args):
         """World > 1: the persistent backward launch on the main stream, and on the comm
         stream (forked before it): the head's batch folds, then per gradient bucket but the
         last, in the order the backward completes them (persist.bucket_ranges), a one-wave
@@ -1639,10 +1638,10 @@ class Engine:
         plan.record(fork)
         plan.use_stream(2)
         plan.wait(fork)
-        plan.prn(2, ptrs, ints, floats)        # head folds (loss, precision, dense grads)
+        plan.prn(2, args)        # head folds (loss, precision, dense grads)
         plan.use_stream(0)
         bwd_op = plan.size()
-        plan.prn(1, ptrs, ints, floats)        # backward: dgrad chain + weight gradients
+        plan.prn(1, args)        # backward: dgrad chain + weight gradients
         err = self.prn.err.data_ptr()
         ranges = bucket_ranges(self)
 

@@ -1,4 +1,4 @@
-"""Persistent small-batch CIFAR step: descriptor tables + plan ops (csrc/cifar_persist.hip).
+"""Persistent small-batch CIFAR step: descriptor tables + plan ops (csrc/prn_*.hip).
 
 At the per-rank batches of the strong-scaling headline config (global batch 128 over
 4-8 GPUs = 16-32 images per rank; reference README.md:16-22, resnet_cifar_main.py:326-340)
@@ -228,6 +228,54 @@ def _stage(b) -> int:
     return int(math.log2(b.cout // 16))
 
 
+def _dev(eng, arr):
+    """A host descriptor table as device bytes."""
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(eng.device)
+
+
+def bn_table(eng, train: bool):
+    """PRN_BN rows: block i's two BatchNorms at 2i, 2i + 1, the final BN last.  Inference
+    reads gamma / beta and the moving statistics only; ``train`` adds the batch statistics,
+    the gradients and the fp64 accumulators to the same rows."""
+    spec = eng.spec
+    order = [bn for b in spec.blocks for bn in b.bns] + [spec.final_bn]
+    rows = np.zeros(len(order), dtype=PRN_BN)
+    for r, bs in zip(rows, order):
+        e = eng.bns[bs.name]
+        r["gamma"], r["beta"], r["mmean"], r["mvar"] = e.gamma, e.beta, e.mmean, e.mvar
+        if train:
+            r["mean"], r["rstd"] = e.mean.data_ptr(), e.rstd.data_ptr()
+            r["scale"], r["shift"] = e.scale.data_ptr(), e.shift.data_ptr()
+            r["dgamma"], r["dbeta"] = e.dgamma, e.dbeta
+            r["acc"], r["bacc"] = e.acc.data_ptr(), e.bacc.data_ptr()
+    return rows
+
+
+def block_table(eng, step=None):
+    """PRN_BLOCK rows.  Inference reads the forward weights, stage, stride and the two
+    BatchNorm indices only; with ``step`` (a PersistStep) the rows also carry the saved
+    activations, the dgrad weights and the step's published backward gradients."""
+    blocks = eng.spec.blocks
+    rows = np.zeros(len(blocks), dtype=PRN_BLOCK)
+    for i, (r, b) in enumerate(zip(rows, blocks)):
+        c1, c2 = eng.convs[b.convs[0].name], eng.convs[b.convs[1].name]
+        cp = eng.convs[b.proj.name] if b.proj is not None else None
+        r["w1f"], r["w2f"] = c1.ohwi, c2.ohwi
+        if cp is not None:
+            r["wpf"] = cp.ohwi
+        r["stage"], r["stride"] = _stage(b), b.stride
+        r["bn1"], r["bn2"] = 2 * i, 2 * i + 1
+        if step is not None:
+            r["x"], r["h1"], r["out"] = (eng.X[i].data_ptr(), eng.H1[i].data_ptr(),
+                                         eng.X[i + 1].data_ptr())
+            r["w1b"], r["w2b"] = c1.hwio, c2.hwio
+            if cp is not None:
+                r["wpb"] = cp.hwio
+            r["dout"], r["dh1"] = step.dout[i].data_ptr(), step.dh1[i].data_ptr()
+            r["da2"], r["da1"] = step.da2[i].data_ptr(), step.da1[i].data_ptr()
+    return rows
+
+
 class PersistStep:
     """Device tables and buffers of the persistent step for one Engine."""
 
@@ -236,20 +284,9 @@ class PersistStep:
         nat, spec, N, dev = eng.nat, eng.spec, eng.N, eng.device
         sizes = nat.prn_struct_bytes()
         assert sizes == [PRN_BN.itemsize, PRN_BLOCK.itemsize, PRN_ITEM.itemsize], sizes
-        blocks = spec.blocks
-        nb = len(blocks)
+        nb = len(spec.blocks)
         self.nblocks = nb
-        # BatchNorm table: block i's two BNs at 2i, 2i + 1, the final BN last
-        order = [bn for b in blocks for bn in b.bns] + [spec.final_bn]
-        bn_rows = np.zeros(len(order), dtype=PRN_BN)
-        for r, bs in zip(bn_rows, order):
-            e = eng.bns[bs.name]
-            r["gamma"], r["beta"], r["mmean"], r["mvar"] = e.gamma, e.beta, e.mmean, e.mvar
-            r["mean"], r["rstd"] = e.mean.data_ptr(), e.rstd.data_ptr()
-            r["scale"], r["shift"] = e.scale.data_ptr(), e.shift.data_ptr()
-            r["dgamma"], r["dbeta"] = e.dgamma, e.dbeta
-            r["acc"], r["bacc"] = e.acc.data_ptr(), e.bacc.data_ptr()
-        self.bn_dev = self._dev(bn_rows)
+        self.bn_dev = _dev(eng, bn_table(eng, train=True))
         self.cus = nat.cu_count()   # this process's CUs (its CU mask)
         self.overlap = bool(getattr(eng, "persist_overlap", False))
         # the backward grid leaves the overlap plan's reserve to the comm stream
@@ -271,24 +308,8 @@ class PersistStep:
         none = torch.empty(0, dtype=eng.X[0].dtype, device=dev)
         self.da2 = [torch.empty_like(eng.H1[i]) if self.P > 1 else none for i in range(nb)]
         self.da1 = [torch.empty_like(eng.X[i]) if self.P > 1 else none for i in range(nb)]
-        rows = np.zeros(nb, dtype=PRN_BLOCK)
-        for i, (r, b) in enumerate(zip(rows, blocks)):
-            c1, c2 = eng.convs[b.convs[0].name], eng.convs[b.convs[1].name]
-            r["x"], r["h1"], r["out"] = (eng.X[i].data_ptr(), eng.H1[i].data_ptr(),
-                                         eng.X[i + 1].data_ptr())
-            r["w1f"], r["w2f"], r["w1b"], r["w2b"] = c1.ohwi, c2.ohwi, c1.hwio, c2.hwio
-            if b.proj is not None:
-                cp = eng.convs[b.proj.name]
-                r["wpf"], r["wpb"] = cp.ohwi, cp.hwio
-            r["dout"], r["dh1"] = self.dout[i].data_ptr(), self.dh1[i].data_ptr()
-            r["da2"], r["da1"] = self.da2[i].data_ptr(), self.da1[i].data_ptr()
-            r["stage"], r["stride"] = _stage(b), b.stride
-            r["bn1"], r["bn2"] = 2 * i, 2 * i + 1
-        self.block_dev = self._dev(rows)
+        self.block_dev = _dev(eng, block_table(eng, step=self))
         self._build_items()
-
-    def _dev(self, arr):
-        return torch.from_numpy(arr.view(np.uint8).copy()).to(self.eng.device)
 
     def _build_items(self):
         """Weight-gradient work items in the order the backward publishes their dy
@@ -360,7 +381,7 @@ class PersistStep:
                     self.bucket_items[BUCKET_OF_STAGE[st]] += 1
                 items.append(r)
         self.items = np.array(items, dtype=PRN_ITEM)
-        self.item_dev = self._dev(self.items)
+        self.item_dev = _dev(eng, self.items)
         reserve = OVERLAP_RESERVE_CUS if self.overlap else 0
         self.wgrad_wgs = max(1, min(self.cus - N * self.P - reserve, len(items)))
         self.convs = [c[0] for c in convs]
@@ -383,24 +404,27 @@ class PersistStep:
 
     def args(self, pool_ptr: int, bar_ptr: int, bn_decay: float, bn_eps: float,
              fwd: bool = False):
-        """Plan-op arguments of the forward (fwd) or backward launch."""
+        """Plan-op arguments of the forward (fwd) or backward / head-fold launch: one dict
+        keyed by the PrnArgs member names, plus wgrad_wgs."""
         eng, spec = self.eng, self.eng.spec
-        ptrs = [self.block_dev.data_ptr(), self.bn_dev.data_ptr(), eng.x_in.data_ptr(),
-                eng.convs[spec.stem.name].ohwi, pool_ptr,
-                bar_ptr, self.err.data_ptr(), eng.dense_hwio, eng.dense_bias,
-                eng.labels.data_ptr(), eng.pooled.data_ptr(), eng.dlogits.data_ptr(),
-                eng.xent_ws.data_ptr(), self.dpool.data_ptr(), self.dx0.data_ptr(),
-                self.item_dev.data_ptr()]
         # backward / head-fold launches: the head's batch folds' outputs (loss, precision,
         # dense bias and weight gradients; prn_head)
         sp = eng.scalars.data_ptr()
-        ptrs += [0, 0, 0, 0] if fwd else [sp, sp + 4, eng.dense_bias_grad, eng.dense_grad]
-        ints = [self.nblocks, len(self.items), eng.N, self.P_fwd if fwd else self.P,
-                spec.num_classes, eng.kpad, 1,
-                self.wgrad_wgs, self.fault_bar if fwd else -1, int(self.overlap and not fwd)]
-        ints += list(BUCKET_OF_STAGE) if self.overlap else [-1, -1, -1]
-        floats = [1.0 / eng.global_batch, bn_decay, bn_eps]
-        return ptrs, ints, floats
+        return dict(
+            blocks=self.block_dev.data_ptr(), nblocks=self.nblocks, bns=self.bn_dev.data_ptr(),
+            x_in=eng.x_in.data_ptr(), stem_w=eng.convs[spec.stem.name].ohwi, pool_acc=pool_ptr,
+            bar=bar_ptr, err=self.err.data_ptr(), dense_w=eng.dense_hwio,
+            dense_b=eng.dense_bias, labels=eng.labels.data_ptr(), pooled=eng.pooled.data_ptr(),
+            dlogits=eng.dlogits.data_ptr(), ws=eng.xent_ws.data_ptr(),
+            dpool=self.dpool.data_ptr(),
+            loss_sum=0 if fwd else sp, correct=0 if fwd else sp + 4,
+            dbias=0 if fwd else eng.dense_bias_grad, dense_grad=0 if fwd else eng.dense_grad,
+            dx0=self.dx0.data_ptr(), items=self.item_dev.data_ptr(), nitems=len(self.items),
+            N=eng.N, P=self.P_fwd if fwd else self.P, classes=spec.num_classes, kpad=eng.kpad,
+            grad_scale=1.0 / eng.global_batch, momentum=bn_decay, eps=bn_eps, update_moving=1,
+            overlap=int(self.overlap and not fwd),
+            bucket_of_stage=tuple(BUCKET_OF_STAGE) if self.overlap else (-1, -1, -1),
+            fault_bar=self.fault_bar if fwd else -1, wgrad_wgs=self.wgrad_wgs)
 
 
 def infer_check(eng) -> str:
@@ -432,26 +456,9 @@ class PersistInfer:
         nat, spec = eng.nat, eng.spec
         sizes = nat.prn_struct_bytes()
         assert sizes[:2] == [PRN_BN.itemsize, PRN_BLOCK.itemsize], sizes
-        blocks = spec.blocks
-        self.nblocks = len(blocks)
-        order = [bn for b in blocks for bn in b.bns] + [spec.final_bn]
-        bn_rows = np.zeros(len(order), dtype=PRN_BN)
-        for r, bs in zip(bn_rows, order):
-            e = eng.bns[bs.name]
-            r["gamma"], r["beta"], r["mmean"], r["mvar"] = e.gamma, e.beta, e.mmean, e.mvar
-        rows = np.zeros(self.nblocks, dtype=PRN_BLOCK)
-        for i, (r, b) in enumerate(zip(rows, blocks)):
-            r["w1f"] = eng.convs[b.convs[0].name].ohwi
-            r["w2f"] = eng.convs[b.convs[1].name].ohwi
-            if b.proj is not None:
-                r["wpf"] = eng.convs[b.proj.name].ohwi
-            r["stage"], r["stride"] = _stage(b), b.stride
-            r["bn1"], r["bn2"] = 2 * i, 2 * i + 1
-        self.bn_dev = self._dev(bn_rows)
-        self.block_dev = self._dev(rows)
-
-    def _dev(self, arr):
-        return torch.from_numpy(arr.view(np.uint8).copy()).to(self.eng.device)
+        self.nblocks = len(spec.blocks)
+        self.bn_dev = _dev(eng, bn_table(eng, train=False))
+        self.block_dev = _dev(eng, block_table(eng))
 
     def record(self, plan, x_in, logits, N: int, eps: float, pooled=None):
         """Record the one launch into `plan`: images `x_in` [N][32][32][8] bf16 -> fp32

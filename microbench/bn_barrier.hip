@@ -1,5 +1,5 @@
 // BatchNorm grid-barrier microbenchmark (MI355X): the persistent CIFAR step's per-BN
-// round trip (csrc/cifar_persist.hip bn_sums / grid_arrive / grid_wait / acc_read) in
+// round trip (csrc/prn_device.h bn_sums / grid_arrive / grid_wait / acc_read) in
 // isolation, to choose its arrival / poll scheme by measurement.
 //
 // One 512-thread workgroup per CU (as the persistent kernels), G = 64 / 128 / 256.  Per

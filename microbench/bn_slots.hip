@@ -1,5 +1,5 @@
 // BatchNorm grid barrier: memory-side fp64 atomics + counter (the persistent CIFAR step's
-// scheme since round 5: csrc/cifar_persist.hip bn_sums / grid_arrive / grid_wait / acc_read)
+// scheme since round 5: csrc/prn_device.h bn_sums / grid_arrive / grid_wait / acc_read)
 // against tagged slots, where the partial sums ARE the arrival:
 //   atom   threads c < ch add (s1, s2) into fp64 replica blockIdx % 4 (no return), every
 //          wave drains (vmcnt(0)), lane 0 adds 1 to its shard (8 lines), lanes 0-7 of wave 0

@@ -1,4 +1,4 @@
-"""Phase timeline of the persistent CIFAR launches (csrc/cifar_persist.hip): image 0's
+"""Phase timeline of the persistent CIFAR launches (csrc/prn_fwd.hip, csrc/prn_bwd.hip): image 0's
 lane 0 stamps the wall clock (100 MHz) at every phase boundary; this prints, per
 phase transition, the mean and total time over all blocks of the forward and of the
 backward launch.  python scripts/prn_probe.py [batch] [resnet_size]"""

@@ -5,42 +5,16 @@ A spill inside these kernels is a memory round trip on the critical path of a la
 whose cost is already its round trips (`profiles/cifar_persist_v2.md`: removing the
 backward's 9-43 spills took bs32 0.631 -> 0.611 ms).
 
-Uses the compiler's kernel-resource-usage remarks (scripts/reg_usage.py does the same).
+Uses the compiler's kernel-resource-usage remarks (tests/kernel_resources.py).
 """
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "distributed_tensorflow_resnet_amd", "csrc", "cifar_persist.hip")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import kernel_resources as kr
 
 
-def _resources(src):
-    cmd = [CLANG, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only",
-           "-c", "-x", "hip", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    rows, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark: +([A-Za-z /\[\]]+?): (\S+) \[", line)
-        if not m:
-            continue
-        k, v = m.group(1).strip(), m.group(2)
-        if k == "Function Name":
-            cur = rows.setdefault(v, {})
-        elif cur is not None:
-            cur[k] = v
-    return rows
-
-
-@pytest.mark.skipif(not os.path.exists(CLANG) and shutil.which("hipcc") is None,
-                    reason="no ROCm compiler")
+@pytest.mark.skipif(not kr.have_compiler(), reason="no ROCm compiler")
 def test_persistent_kernels_have_no_spills():
-    rows = _resources(SRC)
+    rows = kr.prn_resources()
     prn = {n: r for n, r in rows.items() if "prn_fwd_kernel" in n or "prn_bwd_kernel" in n}
     assert len(prn) == 6, sorted(rows)   # forward and backward at 1, 2 and 4 slices
     for name, r in prn.items():

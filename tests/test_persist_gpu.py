@@ -1,4 +1,4 @@
-"""Persistent small-batch CIFAR step (csrc/cifar_persist.hip, train/persist.py) against
+"""Persistent small-batch CIFAR step (csrc/prn_fwd.hip, csrc/prn_bwd.hip, train/persist.py) against
 the launch-per-layer engine and the fp32 autograd oracle of the same network."""
 import pytest
 import torch

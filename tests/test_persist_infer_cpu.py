@@ -2,14 +2,12 @@
 predicate, the kernel's compile-time register budget and its tuning key."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+import kernel_resources as kr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "distributed_tensorflow_resnet_amd", "csrc", "cifar_persist.hip")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 
 def test_shape_predicate():
@@ -24,29 +22,9 @@ def test_shape_predicate():
     assert shape_check(cifar_spec(8), stem_s2d=True) != ""
 
 
-def _resources(src):
-    """tests/test_kernel_resources_cpu.py's recipe: the compiler's resource remarks."""
-    cmd = [CLANG, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only",
-           "-c", "-x", "hip", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    rows, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark: +([A-Za-z /\[\]]+?): (\S+) \[", line)
-        if not m:
-            continue
-        k, v = m.group(1).strip(), m.group(2)
-        if k == "Function Name":
-            cur = rows.setdefault(v, {})
-        elif cur is not None:
-            cur[k] = v
-    return rows
-
-
-@pytest.mark.skipif(not os.path.exists(CLANG) and shutil.which("hipcc") is None,
-                    reason="no ROCm compiler")
+@pytest.mark.skipif(not kr.have_compiler(), reason="no ROCm compiler")
 def test_inference_kernel_resources():
-    rows = _resources(SRC)
+    rows = kr.prn_resources()
     inf = {n: r for n, r in rows.items() if "prn_infer_kernel" in n}
     assert len(inf) == 1, sorted(rows)
     (name, r), = inf.items()
@@ -68,3 +46,38 @@ def test_tune_key():
     assert m, "README.md 'Knobs' has no persist_eval row"
     assert m.group(1) == str(tune.ENGINE["persist_eval"][0])
     assert tune.ENGINE["persist_eval"][0] == -1
+
+
+def _prn_args():
+    """A PrnArgs dict (train/persist.py PersistStep.args' keys) with a valid shape and null
+    pointers: recorded into a Plan, never run."""
+    ptrs = ("blocks", "bns", "x_in", "stem_w", "pool_acc", "bar", "err", "dense_w", "dense_b",
+            "labels", "pooled", "dlogits", "ws", "dpool", "loss_sum", "correct", "dbias",
+            "dense_grad", "dx0", "items")
+    args = {k: 0 for k in ptrs}
+    args.update(nblocks=3, nitems=0, N=4, P=2, classes=10, kpad=16, grad_scale=0.25,
+                momentum=0.9, eps=1e-5, update_moving=1, overlap=0,
+                bucket_of_stage=(-1, -1, -1), fault_bar=-1, wgrad_wgs=1)
+    return args
+
+
+def test_prn_args_are_named():
+    """Plan.prn takes one dict keyed by the PrnArgs member names: a complete dict records
+    an op; a missing key and an unknown key each raise, naming the key."""
+    from distributed_tensorflow_resnet_amd import _C
+
+    plan = _C.Plan()
+    for mode in (0, 1, 2):
+        n = plan.size()
+        plan.prn(mode, _prn_args())
+        assert plan.size() == n + 1
+    n = plan.size()
+    short = _prn_args()
+    del short["dense_grad"]
+    with pytest.raises(ValueError, match="dense_grad"):
+        plan.prn(1, short)
+    extra = _prn_args()
+    extra["fault_barr"] = 3
+    with pytest.raises(ValueError, match="fault_barr"):
+        plan.prn(0, extra)
+    assert plan.size() == n

@@ -1,4 +1,4 @@
-"""The one-launch persistent inference forward (csrc/cifar_persist.hip prn_infer_kernel,
+"""The one-launch persistent inference forward (csrc/prn_infer.hip prn_infer_kernel,
 train/persist.py PersistInfer, Engine.build_eval_plan(batch, persist=True)): against the
 fp32 oracle and the reference's trained graph, its exact properties (images independent,
 no atomics: bit-equal rows whatever the batch), the shared loss / precision tail, that it

@@ -651,6 +651,38 @@ static Launch mk_sgd_tiles(ptr_t master, ptr_t grad, ptr_t mom, float init,
   };
 }
 
+static Launch mk_lars_norms(ptr_t master, ptr_t grad, ptr_t segs, ptr_t lsegs, ptr_t blk_seg,
+                            int nblocks, ptr_t part) {
+  if ((master | grad) & 15)
+    throw std::invalid_argument("lars_norms: master and grad must be 16-byte aligned");
+  return [=](hipStream_t s) {
+    lars_norms(P<const float>(master), P<const float>(grad), P<const ParamSeg>(segs),
+               P<const LarsSeg>(lsegs), P<const int>(blk_seg), nblocks, P<double>(part), s);
+  };
+}
+
+static Launch mk_lars_trust(ptr_t part, ptr_t lsegs, int nseg, float eeta, float wd,
+                            float epsilon, float grad_scale, ptr_t trust, ptr_t wn, ptr_t gn) {
+  return [=](hipStream_t s) {
+    lars_trust(P<const double>(part), P<const LarsSeg>(lsegs), nseg, eeta, wd, epsilon,
+               grad_scale, P<float>(trust), P<float>(wn), P<float>(gn), s);
+  };
+}
+
+static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float momentum, float wd, float grad_scale,
+                                  ptr_t segs, int nseg, ptr_t trust, ptr_t bf, ptr_t lr_out) {
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+  return [=](hipStream_t s) {
+    lars_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
+                     P<const long long>(gstep), momentum, wd, grad_scale,
+                     P<const ParamSeg>(segs), nseg, P<const float>(trust), P<bf16>(bf),
+                     P<float>(lr_out), s);
+  };
+}
+
 static Launch mk_step_increment(ptr_t gstep) {
   return [=](hipStream_t s) { step_increment(P<long long>(gstep), s); };
 }
@@ -1269,6 +1301,9 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "sgd_update_pack", mk_sgd_update_pack);
   def_op(m, plan, "ohwi_pack", mk_ohwi_pack);
   def_op(m, plan, "sgd_tiles", mk_sgd_tiles);
+  def_op(m, plan, "lars_norms", mk_lars_norms);
+  def_op(m, plan, "lars_trust", mk_lars_trust);
+  def_op(m, plan, "lars_update_pack", mk_lars_update_pack);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);
   def_op(m, plan, "fill", mk_fill);
@@ -1366,6 +1401,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("param_seg_bytes", []() { return (int)sizeof(ParamSeg); });
   m.def("wg_desc_bytes", []() { return (int)sizeof(WgReduceDesc); });
   m.def("opt_work_bytes", []() { return (int)sizeof(OptWork); });
+  m.def("lars_seg_bytes", []() { return (int)sizeof(LarsSeg); });
+  m.attr("LARS_CHUNK") = (int)LARS_CHUNK;
   m.def("device_count", &hip_device_count);
   m.def("cu_count", &device_cus,
         "CUs this process dispatches to on the current device (the set bits of its CU mask, "

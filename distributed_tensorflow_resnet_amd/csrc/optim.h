@@ -45,6 +45,29 @@ void sgd_tiles(float* master, float* grad, float* mom, const LrSchedule& s, long
                const ParamSeg* segs, const OptWork* work, const int* blk_seg, int nblocks,
                bf16* bf, float* lr_out, unsigned* ticket, const bf16* gin, bf16* gout, int pack,
                hipStream_t st);
+// LARS (lars.hip): per-tensor trust ratios from a deterministic segmented reduction.
+constexpr int LARS_CHUNK = 4096;   // elements of a segment summed by one workgroup
+struct LarsSeg {
+  long long chunk0;        // first workgroup (chunk) of the segment in lars_norms' grid
+  int nchunks;             // ceil(numel / LARS_CHUNK)
+  int skip;                // 1: not adapted (trust = 1)
+};
+// part[b] = (sum w^2, sum g^2) over chunk b (fp64), blk_seg[b] = its segment.  master and
+// grad must be 16-byte aligned (the aligned body is read in 16-byte loads).
+void lars_norms(const float* master, const float* grad, const ParamSeg* segs,
+                const LarsSeg* lsegs, const int* blk_seg, int nblocks, double* part,
+                hipStream_t st);
+// Per segment: wn = ||w||, gn = |grad_scale| ||g|| from its chunks' partials in chunk
+// order; trust = eeta wn / (gn + wd wn + epsilon), or exactly 1 for a skipped segment or
+// a zero norm.
+void lars_trust(const double* part, const LarsSeg* lsegs, int nseg, float eeta, float wd,
+                float epsilon, float grad_scale, float* trust, float* wn, float* gn,
+                hipStream_t st);
+// sgd_update_pack's update with momentum, at the rate lr * trust[segment].
+void lars_update_pack(float* master, const float* grad, float* mom, long n, const LrSchedule& s,
+                      const long long* gstep, float momentum, float wd, float grad_scale,
+                      const ParamSeg* segs, int nseg, const float* trust, bf16* bf,
+                      float* lr_out, hipStream_t st);
 void step_increment(long long* gstep, hipStream_t s);
 int l2_workspace_floats();
 void l2_half_sum(const float* v, long n, float* ws, float* out, hipStream_t s);

@@ -9,7 +9,8 @@ Eager (define-by-run) re-statement for the CPU/fp32 path and for API users:
 cost = softmax_cross_entropy(onehot, logits) + wd * sum(l2_loss(v) for all
 trainables) -- including BN gamma/beta and the dense bias (resnet_model.py:78-86);
 'mom' = tf.train.MomentumOptimizer(lr, 0.9) (accum = 0.9*accum + g; v -= lr*accum),
-'sgd' = GradientDescent.  Labels may be one-hot (reference) or class indices.
+'sgd' = GradientDescent, 'lars' = 'mom' at a per-variable rate lr * trust (layer-wise
+adaptive rate scaling, csrc/lars.hip).  Labels may be one-hot (reference) or class indices.
 `resnet_size` is a real argument here (the reference hard-codes 50, defect #8).
 The MI355X training path is train/engine.py (same math, HIP kernels).
 """
@@ -23,6 +24,7 @@ import torch.nn.functional as F
 from . import resnet_model_official
 
 HParams = namedtuple("HParams", "num_classes, lrn_rate, weight_decay_rate, optimizer")
+LARS_EETA = 0.001   # the 'lars' optimizer's trust coefficient (train/engine.py lars_eeta)
 
 
 class ResNet:
@@ -82,17 +84,29 @@ class ResNet:
         with torch.no_grad():
             for v in vs:
                 g = v.grad
-                if self.hps.optimizer == "mom":
+                if self.hps.optimizer in ("mom", "lars"):
                     acc = self._slots.get(id(v))
                     if acc is None:
                         acc = torch.zeros_like(v)
                         self._slots[id(v)] = acc
                     acc.mul_(0.9).add_(g)
-                    v.sub_(self.lrn_rate * acc)
+                    v.sub_(self.lrn_rate * self._lars_trust(v, g) * acc)
                 else:
                     v.sub_(self.lrn_rate * g)
         self.global_step += 1
         return self.global_step
+
+    def _lars_trust(self, v, g) -> float:
+        """'lars': the trust ratio eeta * |v| / (|g^| + wd * |v|) of one variable (eeta =
+        0.001; g^ = g - wd * v, the gradient before the cost's l2 term); 1 for rank-1
+        variables (BN gamma / beta, biases), zero norms and the other optimizers."""
+        if self.hps.optimizer != "lars" or v.dim() <= 1:
+            return 1.0
+        wd = self.hps.weight_decay_rate
+        wn, gn = float(v.norm()), float((g - wd * v).norm())
+        if wn <= 0 or gn <= 0:
+            return 1.0
+        return LARS_EETA * wn / (gn + wd * wn)
 
     def precision(self) -> float:
         y = self.labels.argmax(1) if self.labels.dim() == 2 else self.labels

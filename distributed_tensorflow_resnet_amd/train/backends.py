@@ -82,6 +82,9 @@ class GPUBackend:
         eng.sync_from_params()
         self._host_step = gs
 
+    def lars_summary(self):
+        return self.engine.lars_summary()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -93,7 +96,8 @@ class CPUBackend:
     def __init__(self, spec: ModelSpec, batch_size: int, *, weight_decay: float, lr_schedule,
                  optimizer: str = "mom", momentum: float = 0.9, seed: int = 0, dist_ctx=None,
                  global_batch: int | None = None, threads: int = 0,
-                 allreduce_dtype: str = "fp32"):
+                 allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
+                 lars_epsilon: float = 0.0, lars_skip: str = "vectors"):
         # intra-op threads: DTR_CPU_THREADS, default 1 -- on small containers the
         # OpenMP pool's spin-waits oversubscribe the CPU quota (measured here: one
         # 8x32x32x16 conv fwd+bwd 1.2 ms on 1 thread, 612 ms on 8)
@@ -111,7 +115,15 @@ class CPUBackend:
         self.mom = torch.zeros(self.store.n_train)
         self.wd = weight_decay
         self.momentum = momentum
-        self.use_momentum = optimizer == "mom"
+        if optimizer not in ("mom", "sgd", "lars"):
+            raise ValueError(f"optimizer must be mom, sgd or lars, got {optimizer!r}")
+        if lars_skip not in ("vectors", "none"):
+            raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
+        self.lars = optimizer == "lars"
+        self.lars_eeta, self.lars_epsilon = float(lars_eeta), float(lars_epsilon)
+        self.lars_skip = lars_skip
+        self._lars_state = None
+        self.use_momentum = optimizer in ("mom", "lars")
         self.sched = lr_schedule
         self.step_count = 0
         self.gen = torch.Generator().manual_seed(seed + 97 * (dist_ctx.rank if dist_ctx else 0))
@@ -154,7 +166,10 @@ class CPUBackend:
         lr = self.sched.at(self.step_count)
         with torch.no_grad():
             gp = g + self.wd * master
-            if self.use_momentum:
+            if self.lars:
+                self.mom.mul_(self.momentum).add_(gp)
+                master.sub_(lr * self._lars_trust(master, g) * self.mom)
+            elif self.use_momentum:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self.mom)
             else:
@@ -171,6 +186,36 @@ class CPUBackend:
         self._last = {"global_step": self.step_count, "cross_entropy": loss_sum / n,
                       "cost": loss_sum / n + self.wd * l2, "precision": correct / n, "lr": lr,
                       "l2": l2}
+
+    def _lars_trust(self, master, g):
+        """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
+        per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
+        before decay; exactly 1 for a skipped tensor or a zero norm."""
+        trust = torch.ones_like(master)
+        self._lars_state = {}
+        for s in self.store.train_slots:
+            w, gs = master[s.offset:s.offset + s.numel], g[s.offset:s.offset + s.numel]
+            wn, gn = float(torch.linalg.vector_norm(w)), float(torch.linalg.vector_norm(gs))
+            t = 1.0
+            skipped = self.lars_skip == "vectors" and len(s.shape) == 1
+            if not skipped and wn > 0 and gn > 0:
+                t = self.lars_eeta * wn / (gn + self.wd * wn + self.lars_epsilon)
+            trust[s.offset:s.offset + s.numel] = t
+            self._lars_state[s.name] = (wn, gn, t, skipped)
+        return trust
+
+    def lars_state(self):
+        """{tensor name: (wn, gn, trust)} of the last step (None: not lars, or no step yet)."""
+        if self._lars_state is None:
+            return None
+        return {n: v[:3] for n, v in self._lars_state.items()}
+
+    def lars_summary(self):
+        if self._lars_state is None:
+            return None
+        from .engine import lars_trust_summary
+
+        return lars_trust_summary({n: v[:3] for n, v in self._lars_state.items() if not v[3]})
 
     def metrics(self):
         return dict(self._last)
@@ -214,7 +259,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  lr_schedule, optimizer: str = "mom", seed: int = 0, dist_ctx=None,
                  bucket_mb: float | None = None, use_graph: bool = False, global_batch=None,
                  input_mode: str = "auto", data_seed: int = 1234,
-                 allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0):
+                 allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0,
+                 lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
+                 lars_skip: str = "vectors"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -229,10 +276,12 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      bucket_mb=bucket_mb, seed=seed, input_mode=input_mode,
                      global_batch=global_batch, use_graph=use_graph, data_seed=data_seed,
                      allreduce_dtype=allreduce_dtype, resident=resident,
-                     shuffle_seed=shuffle_seed)
+                     shuffle_seed=shuffle_seed, lars_eeta=lars_eeta,
+                     lars_epsilon=lars_epsilon, lars_skip=lars_skip)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
     return CPUBackend(spec, batch_size, weight_decay=weight_decay, lr_schedule=lr_schedule,
                       optimizer=optimizer, seed=seed, dist_ctx=dist_ctx,
-                      global_batch=global_batch, allreduce_dtype=allreduce_dtype)
+                      global_batch=global_batch, allreduce_dtype=allreduce_dtype,
+                      lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip)

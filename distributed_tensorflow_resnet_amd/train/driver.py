@@ -217,7 +217,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            data_seed=1234 + rank, allreduce_dtype=flags.allreduce_dtype,
                            input_mode=("imagenet_u8" if u8 else
                                        "cifar_resident" if resident is not None else "auto"),
-                           resident=resident, shuffle_seed=flags.seed)
+                           resident=resident, shuffle_seed=flags.seed,
+                           lars_eeta=flags.lars_eeta, lars_epsilon=flags.lars_epsilon,
+                           lars_skip=flags.lars_skip)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

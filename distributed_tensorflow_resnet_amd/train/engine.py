@@ -67,6 +67,12 @@ OPTW_DTYPE = np.dtype([   # csrc/optim.h OptWork
 
 OPT_TILE_LOADS = 2048   # a sgd_tiles workgroup's slab loads: <= 8 16-byte loads per thread
 
+LARS_DTYPE = np.dtype([   # csrc/optim.h LarsSeg
+    ("chunk0", "<i8"), ("nchunks", "<i4"), ("skip", "<i4"),
+])
+LARS_CHUNK = 4096         # csrc/optim.h LARS_CHUNK: elements per lars_norms workgroup
+LARS_SKIPS = ("vectors", "none")
+
 
 class PersistentStepError(RuntimeError):
     """A persistent CIFAR launch's grid barrier timed out (csrc/prn_device.h: every
@@ -107,6 +113,29 @@ def opt_tile(R: int, K: int, splits: int, cslab: int, C: int, taps: int, nosplit
             break
     assert TR * TC // 4 <= units_max, (R, K, splits)
     return TR, TC
+
+
+def lars_tables(seg_arr, skip):
+    """The work map of lars_norms / lars_trust (csrc/lars.hip): per parameter segment its
+    first workgroup, its number of LARS_CHUNK-element chunks and whether it is skipped
+    (trust = 1).  Returns the LarsSeg table (numpy, LARS_DTYPE) and blk_seg (a list: the
+    segment of each lars_norms workgroup)."""
+    assert len(skip) == len(seg_arr)
+    tab = np.zeros(len(seg_arr), dtype=LARS_DTYPE)
+    blk = []
+    for i, rec in enumerate(seg_arr):
+        n = -(-int(rec["numel"]) // LARS_CHUNK)
+        tab[i] = (len(blk), n, int(bool(skip[i])))
+        blk += [i] * n
+    return tab, blk
+
+
+def lars_trust_summary(state):
+    """min / median / max trust ratio over a lars_state() dict (metrics.jsonl, the log)."""
+    t = sorted(v[2] for v in state.values())
+    if not t:
+        return {}
+    return {"lars_trust_min": t[0], "lars_trust_median": t[len(t) // 2], "lars_trust_max": t[-1]}
 
 
 def sgd_tiles_work(seg_arr, seg_names, slabs, gptr: int, names=None, nosplit=(64, 64)):
@@ -268,7 +297,8 @@ class Engine:
                  input_mode: str = "auto", global_batch: int | None = None,
                  use_graph: bool = False, data_seed: int = 1234, fork_wgrad: bool | None = None,
                  allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None,
-                 resident=None, shuffle_seed: int = 0):
+                 resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
+                 lars_epsilon: float = 0.0, lars_skip: str = "vectors"):
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
@@ -279,7 +309,16 @@ class Engine:
         self.global_batch = global_batch or batch_size * self.world
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
-        self.use_momentum = optimizer == "mom"
+        if optimizer not in ("mom", "sgd", "lars"):
+            raise ValueError(f"optimizer must be mom, sgd or lars, got {optimizer!r}")
+        if lars_skip not in LARS_SKIPS:
+            raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
+        # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
+        # buffer means what it means for mom, so checkpoints move between the two
+        self.lars = optimizer == "lars"
+        self.lars_eeta, self.lars_epsilon = float(lars_eeta), float(lars_epsilon)
+        self.lars_skip = lars_skip
+        self.use_momentum = optimizer in ("mom", "lars")
         self.sched = lr_schedule
         self.use_graph = use_graph
         self.data_seed = data_seed
@@ -388,6 +427,13 @@ class Engine:
         self.persist_slices = tune.get("persist_slices")
         self.persist_overlap_tune = bool(tune.get("persist_overlap"))
         self.opt_fused = bool(tune.get("opt_fused"))
+        # why the one-launch optimizer is off although tuned on ("" = as tuned): a trust
+        # ratio needs its tensor's whole all-reduced gradient before any of it is updated
+        self.opt_fused_reason = ""
+        if self.lars and self.opt_fused:
+            self.opt_fused = False
+            self.opt_fused_reason = ("optimizer lars: the norms are taken over the complete "
+                                     "fp32 gradient, before the update")
         # why the persistent step is off ("" = on); never on a GPU shared by several ranks
         # (its grids need every CU to themselves), and the same choice on EVERY rank (the
         # two plans issue different collectives)
@@ -515,6 +561,17 @@ class Engine:
         self.ohwi_tile0 = torch.tensor(np.concatenate([[0], np.cumsum(tiles)[:-1]]).astype(np.int64),
                                        device=self.device)
         self.wbf = torch.zeros(max(bf_total, 1), dtype=BF16, device=self.device)
+        if self.lars:
+            # chunk / skip table, chunk partials and (trust, wn, gn): fixed pointers
+            skip = [self.lars_skip == "vectors" and len(s.shape) == 1 for s in ps.train_slots]
+            tab, blk = lars_tables(seg_arr, skip)
+            assert LARS_DTYPE.itemsize == self.nat.lars_seg_bytes()
+            assert LARS_CHUNK == self.nat.LARS_CHUNK
+            self.lars_skipped = skip
+            self.lars_segs = torch.from_numpy(tab.view(np.uint8).copy()).to(self.device)
+            self.lars_blk = torch.tensor(blk, dtype=torch.int32, device=self.device)
+            self.lars_part = torch.zeros(2 * len(blk), dtype=torch.float64, device=self.device)
+            self.lars_out = torch.ones(3, self.nseg, device=self.device)
         bptr = self.wbf.data_ptr()
         for rec, s in zip(seg_arr, ps.train_slots):
             if s.kind == "conv":
@@ -1490,6 +1547,7 @@ class Engine:
         sp = self.scalars.data_ptr()
         b2 = plan.size()
         s = self.sched
+        assert not (self.lars and (names is not None or fused_slabs is not None))
         if names is not None:
             assert not fused_slabs
             self._emit_update(plan, names, gin)
@@ -1506,12 +1564,30 @@ class Engine:
                            wt.data_ptr(), bt.data_ptr(), nblk, self.wbf.data_ptr(), sp + 8,
                            self.opt_ticket.data_ptr(), gin, 0, 0)   # + global_step += 1
         else:
-            plan.sgd_update_pack(self.params.master.data_ptr(), self.grad.data_ptr(),
-                                 self.mom.data_ptr(), self.params.n_train, s.init, s.warm_steps,
-                                 s.warm_from, s.warm_to, list(s.bounds), list(s.values),
-                                 self.gstep.data_ptr(), self.momentum, self.wd, 1.0,
-                                 int(self.use_momentum), self.segs.data_ptr(), self.nseg,
-                                 self.wbf.data_ptr(), sp + 8, 1)
+            if self.lars:
+                # grad is complete here (reduced, all-reduced and joined; the s2d stem's
+                # mapped back): every rank forms the same norms from the same bits
+                out = self.lars_out.data_ptr()
+                plan.lars_norms(self.params.master.data_ptr(), self.grad.data_ptr(),
+                                self.segs.data_ptr(), self.lars_segs.data_ptr(),
+                                self.lars_blk.data_ptr(), self.lars_blk.numel(),
+                                self.lars_part.data_ptr())
+                plan.lars_trust(self.lars_part.data_ptr(), self.lars_segs.data_ptr(), self.nseg,
+                                self.lars_eeta, self.wd, self.lars_epsilon, 1.0, out,
+                                out + 4 * self.nseg, out + 8 * self.nseg)
+                plan.lars_update_pack(self.params.master.data_ptr(), self.grad.data_ptr(),
+                                      self.mom.data_ptr(), self.params.n_train, s.init,
+                                      s.warm_steps, s.warm_from, s.warm_to, list(s.bounds),
+                                      list(s.values), self.gstep.data_ptr(), self.momentum,
+                                      self.wd, 1.0, self.segs.data_ptr(), self.nseg, out,
+                                      self.wbf.data_ptr(), sp + 8)
+            else:
+                plan.sgd_update_pack(self.params.master.data_ptr(), self.grad.data_ptr(),
+                                     self.mom.data_ptr(), self.params.n_train, s.init,
+                                     s.warm_steps, s.warm_from, s.warm_to, list(s.bounds),
+                                     list(s.values), self.gstep.data_ptr(), self.momentum,
+                                     self.wd, 1.0, int(self.use_momentum), self.segs.data_ptr(),
+                                     self.nseg, self.wbf.data_ptr(), sp + 8, 1)
             plan.ohwi_pack(self.params.master.data_ptr(), self.segs.data_ptr(),
                            self.ohwi_tile0.data_ptr(), self.nseg, self.ohwi_tiles,
                            self.wbf.data_ptr(), self.gstep.data_ptr())   # + global_step += 1
@@ -1703,6 +1779,24 @@ class Engine:
         self._run_bwd(st)
         if "gsum" in self.seg:
             self._run("gsum", st)
+
+    def lars_state(self):
+        """{tensor name: (wn, gn, trust)} of the last step's LARS update: the norms of the
+        fp32 master and of the all-reduced gradient it was formed from (synchronises).
+        None unless the optimizer is lars."""
+        if not self.lars:
+            return None
+        torch.cuda.synchronize(self.device)
+        t, wn, gn = self.lars_out.cpu().tolist()
+        return {n: (wn[i], gn[i], t[i]) for i, n in enumerate(self.seg_names)}
+
+    def lars_summary(self):
+        """min / median / max trust ratio over the adapted tensors (None: not lars)."""
+        st = self.lars_state()
+        if st is None:
+            return None
+        return lars_trust_summary({n: v for (n, v), skip in zip(st.items(), self.lars_skipped)
+                                   if not skip})
 
     def persist_error(self) -> bool:
         """Whether a persistent launch's barrier wait ever timed out (synchronises)."""

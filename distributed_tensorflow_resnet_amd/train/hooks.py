@@ -61,6 +61,13 @@ class LearningRateSetterHook(Hook):
         self.lr = self.schedule.at(session.global_step)
 
 
+def _lars_summary(session):
+    """The last step's LARS trust ratios (min / median / max over the adapted tensors), or
+    None when the backend's optimizer is not lars."""
+    fn = getattr(session.backend, "lars_summary", None)
+    return fn() if fn is not None else None
+
+
 class LoggingTensorHook(Hook):
     def __init__(self, every_n_iter: int = 20, precision_key: str = "precision"):
         self.n = every_n_iter
@@ -72,8 +79,11 @@ class LoggingTensorHook(Hook):
     def after_run(self, session, step):
         if self.n > 0 and step % self.n == 0 and session.is_chief:
             m = session.metrics()
+            ls = _lars_summary(session)
+            lars = (f", lars trust min/median/max = {ls['lars_trust_min']:.4g}/"
+                    f"{ls['lars_trust_median']:.4g}/{ls['lars_trust_max']:.4g}") if ls else ""
             log(f"INFO:tensorflow:step = {m['global_step']}, loss = {m['cost']:.6f}, "
-                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}")
+                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}")
 
 
 class StepCounterHook(Hook):
@@ -144,6 +154,7 @@ class JsonlMetricsHook(Hook):
             if eng is not None:   # which step ran, and why the persistent one did not
                 m["step_path"] = "persistent" if getattr(eng, "persist", False) else "per-layer"
                 m["persist_disabled_reason"] = getattr(eng, "persist_reason", "") or None
+            m.update(_lars_summary(session) or {})   # lars_trust_min / _median / _max
             os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
             with open(self.path, "a") as fh:
                 fh.write(json.dumps(m) + "\n")

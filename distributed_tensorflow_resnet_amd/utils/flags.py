@@ -138,7 +138,18 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd"))
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars"),
+                   help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
+                        "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
+                        "epsilon) (layer-wise adaptive rate scaling, for large global batches).")
+    p.add_argument("--lars_eeta", type=float, default=0.001,
+                   help="LARS trust coefficient.")
+    p.add_argument("--lars_epsilon", type=float, default=0.0,
+                   help="Added to the denominator of the LARS trust ratio.")
+    p.add_argument("--lars_skip", default="vectors", choices=("vectors", "none"),
+                   help="Tensors LARS does not adapt (trust = 1; they keep their weight decay): "
+                        "'vectors' = every rank-1 tensor (BN gamma / beta, the dense bias), "
+                        "'none' = adapt them too.")
     p.add_argument("--bucket_mb", type=float, default=0.0,
                    help="All-reduce bucket size (MiB); 0 = auto (~4 buckets, <= 25 MiB).")
     p.add_bool("use_graph", False, "Capture the training step in a hipGraph (single stream; "

@@ -186,6 +186,25 @@ def resident_perm(key: int, p: int, records: int) -> int:
             return x
 
 
+def upload_resident(split, spec, device):
+    """(images uint8 [M,3,32,32], labels [M]) as host arrays or tensors -> the device
+    copies the resident input kernel reads: contiguous uint8 records + int32 labels."""
+    images, labels = split
+    images = torch.as_tensor(images)
+    labels = torch.as_tensor(labels)
+    if images.dtype != torch.uint8 or images.dim() != 4 or \
+            tuple(images.shape[1:]) != (3, spec.image_h, spec.image_w) or \
+            (spec.image_h, spec.image_w) != (32, 32):
+        raise ValueError("resident split: images must be uint8 [M,3,32,32], got "
+                         f"{images.dtype} {tuple(images.shape)}")
+    if labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+        raise ValueError("resident split: one label per image")
+    if not 0 < images.shape[0] < 2 ** 31:
+        raise ValueError("resident split: need 0 < records < 2**31")
+    return (images.to(device).contiguous(),
+            labels.to(device=device, dtype=torch.int32).contiguous())
+
+
 def resident_steps_per_epoch(records: int, batch: int, world: int = 1) -> int:
     """Batches per rank per epoch; the tail is dropped, as in CifarData.batches."""
     s = (records // world) // batch

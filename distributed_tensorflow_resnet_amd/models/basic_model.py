@@ -120,7 +120,7 @@ class ResNetModel(BasicModel):
 
     def build(self):
         from ..train.backends import make_backend
-        from ..train.engine import cifar_lr_schedule, constant_lr, imagenet_lr_schedule
+        from ..train.schedule import cifar_lr_schedule, constant_lr, imagenet_lr_schedule
 
         c = self.config
         self.spec = build_spec(c["dataset"], c["resnet_size"])

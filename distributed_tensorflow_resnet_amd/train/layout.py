@@ -1,0 +1,163 @@
+"""Host tables of the training engine: the parameter-segment table (where every
+trainable tensor and its bf16 copies live) and the work maps of the optimizer launches.
+Pure arithmetic over the model spec -- numpy only, no device and no native module -- laid
+out as the structs of csrc/optim.h that the kernels read."""
+from __future__ import annotations
+
+import numpy as np
+
+WGD_DTYPE = np.dtype([
+    ("part", "<u8"), ("grad", "<u8"), ("splits", "<i4"), ("K", "<i4"), ("Kv", "<i4"),
+    ("taps", "<i4"), ("C", "<i4"), ("Cv", "<i4"), ("chunk0", "<i8"),
+])
+
+SEG_DTYPE = np.dtype([
+    ("offset", "<i8"), ("numel", "<i8"), ("bf_ohwi", "<i8"), ("bf_hwio", "<i8"),
+    ("kh", "<i4"), ("kw", "<i4"), ("C", "<i4"), ("K", "<i4"), ("cpad", "<i4"), ("kpad", "<i4"),
+])
+
+OPTW_DTYPE = np.dtype([   # csrc/optim.h OptWork
+    ("part", "<u8"), ("tile0", "<i8"), ("splits", "<i4"), ("kslab", "<i4"), ("cslab", "<i4"),
+    ("tiled", "<i4"), ("tr", "<i4"), ("tc", "<i4"),
+])
+
+OPT_TILE_LOADS = 2048   # a sgd_tiles workgroup's slab loads: <= 8 16-byte loads per thread
+
+LARS_DTYPE = np.dtype([   # csrc/optim.h LarsSeg
+    ("chunk0", "<i8"), ("nchunks", "<i4"), ("skip", "<i4"),
+])
+LARS_CHUNK = 4096         # csrc/optim.h LARS_CHUNK: elements per lars_norms workgroup
+LARS_SKIPS = ("vectors", "none")
+
+
+def _ceil(a, b):
+    return (a + b - 1) // b
+
+
+def _pow2ceil(x: int) -> int:
+    return 1 << max(0, (int(x) - 1).bit_length())
+
+
+def param_segments(spec, train_slots, *, cpad_in: int, kpad: int, stem_s2d: bool):
+    """The parameter-segment table (SEG_DTYPE, one record per trainable slot, in slot
+    order) and the element count of the bf16 weight buffer.  A conv weight gets a bf16
+    OHWI copy (input channels padded to `cpad_in` below 8; none for a space-to-depth
+    stem, whose operand comes from stem_s2d_pack) and, from 8 input channels up (the
+    stem never needs dgrad), a bf16 HWIO copy; the dense kernel both, its classes padded
+    to `kpad`.  bf_ohwi / bf_hwio are element offsets into that buffer, -1 = no copy."""
+    conv_specs = {c.name: c for c in spec.all_convs()}
+    seg_arr = np.zeros(len(train_slots), dtype=SEG_DTYPE)
+    bf_total = 0
+    for rec, s in zip(seg_arr, train_slots):
+        rec["offset"], rec["numel"] = s.offset, s.numel
+        rec["bf_ohwi"] = rec["bf_hwio"] = -1
+        if s.kind == "conv":
+            c = conv_specs[s.name.split("/")[0]]
+            taps = c.kh * c.kw
+            cpad = cpad_in if c.cin < 8 else c.cin
+            rec["kh"], rec["kw"], rec["C"], rec["K"] = c.kh, c.kw, c.cin, c.cout
+            rec["cpad"], rec["kpad"] = cpad, c.cout
+            if not (stem_s2d and c.name == spec.stem.name):
+                rec["bf_ohwi"] = bf_total
+                bf_total += c.cout * taps * cpad
+            if c.cin >= 8:
+                rec["bf_hwio"] = bf_total
+                bf_total += taps * c.cin * c.cout
+        elif s.kind == "dense_kernel":
+            F, classes = s.shape
+            rec["kh"], rec["kw"], rec["C"], rec["K"] = 1, 1, F, classes
+            rec["cpad"], rec["kpad"] = F, kpad
+            rec["bf_ohwi"] = bf_total
+            bf_total += kpad * F
+            rec["bf_hwio"] = bf_total
+            bf_total += F * kpad
+        else:
+            rec["kh"] = rec["kw"] = rec["C"] = rec["K"] = rec["cpad"] = rec["kpad"] = 1
+    return seg_arr, bf_total
+
+
+def opt_tile(R: int, K: int, splits: int, cslab: int, C: int, taps: int, nosplit=(64, 64)):
+    """Tile (rows tap*C+ci, output channels) of a weight in the one-launch optimizer
+    (csrc/optim.hip sgd_tiles_kernel): 64 x 64 without slabs; with `splits` slabs the
+    tile shrinks (columns first) until its float4 slab loads fit OPT_TILE_LOADS and,
+    past 8 splits (4 thread groups of 64 float4 units), until it has <= 64 units.
+    Padded slab rows (cslab != C, the stem) keep all rows in one tile."""
+    if splits == 0:
+        return nosplit
+    units_max = 64 if splits > 8 else 1 << 30
+    TC = min(64, _pow2ceil(K))
+    if cslab != C:
+        assert R <= 64 and (taps * cslab) % 4 == 0, (R, taps, cslab)
+        cols4 = taps * cslab // 4
+        while TC > 1 and (TC * cols4 * splits > OPT_TILE_LOADS or TC * cols4 > units_max):
+            TC //= 2
+        assert TC * cols4 <= units_max, (R, K, splits, cslab)
+        return R, TC
+    assert C % 4 == 0, C
+    TR = min(64, _pow2ceil(R))
+    while (TR * TC // 4) * splits > OPT_TILE_LOADS or TR * TC // 4 > units_max:
+        if TC >= TR and TC > 1:
+            TC //= 2
+        elif TR > 4:
+            TR //= 2
+        else:
+            break
+    assert TR * TC // 4 <= units_max, (R, K, splits)
+    return TR, TC
+
+
+def lars_tables(seg_arr, skip):
+    """The work map of lars_norms / lars_trust (csrc/lars.hip): per parameter segment its
+    first workgroup, its number of LARS_CHUNK-element chunks and whether it is skipped
+    (trust = 1).  Returns the LarsSeg table (numpy, LARS_DTYPE) and blk_seg (a list: the
+    segment of each lars_norms workgroup)."""
+    assert len(skip) == len(seg_arr)
+    tab = np.zeros(len(seg_arr), dtype=LARS_DTYPE)
+    blk = []
+    for i, rec in enumerate(seg_arr):
+        n = -(-int(rec["numel"]) // LARS_CHUNK)
+        tab[i] = (len(blk), n, int(bool(skip[i])))
+        blk += [i] * n
+    return tab, blk
+
+
+def lars_trust_summary(state):
+    """min / median / max trust ratio over a lars_state() dict (metrics.jsonl, the log)."""
+    t = sorted(v[2] for v in state.values())
+    if not t:
+        return {}
+    return {"lars_trust_min": t[0], "lars_trust_median": t[len(t) // 2], "lars_trust_max": t[-1]}
+
+
+def sgd_tiles_work(seg_arr, seg_names, slabs, gptr: int, names=None, nosplit=(64, 64)):
+    """The work map of the one-launch optimizer (csrc/optim.hip sgd_tiles_kernel): per
+    parameter segment its slab (split-K partials still to be summed, or none: the
+    gradient is in `grad`, at device address gptr) and its first workgroup; weights with
+    bf16 copies or slabs go in tiles of their HWIO master (opt_tile), other tensors in
+    1024-element chunks.  `names`: only those segments get workgroups (a bucket's pack
+    launch).  Returns the OptWork table (numpy, OPTW_DTYPE) and blk_seg (a list)."""
+    work = np.zeros(len(seg_arr), dtype=OPTW_DTYPE)
+    blk = []
+    for i, (rec, name) in enumerate(zip(seg_arr, seg_names)):
+        if names is not None and name not in names:
+            continue
+        d = slabs.get(name)
+        taps, C, K = int(rec["kh"] * rec["kw"]), int(rec["C"]), int(rec["K"])
+        tiled = d is not None or rec["bf_ohwi"] >= 0 or rec["bf_hwio"] >= 0
+        part, splits, kslab, cslab = 0, 0, 0, 0
+        if d is not None:
+            part, grad, splits, kslab, Kv, dtaps, cslab, Cv = d
+            assert (grad, Kv, dtaps, Cv) == (gptr + 4 * int(rec["offset"]), K, taps, C), name
+            assert kslab >= K and cslab >= C and part % 16 == 0, name
+        tr = tc = 0
+        if tiled:
+            assert taps * C * K == rec["numel"], name
+            tr, tc = opt_tile(taps * C, K, splits, cslab or C, C, taps, nosplit)
+            n = _ceil(taps * C, tr) * _ceil(K, tc)
+        else:
+            n = _ceil(int(rec["numel"]), 1024)
+        work[i] = (part, len(blk), splits, kslab, cslab, int(tiled), tr, tc)
+        blk += [i] * n
+    assert not set(slabs) - set(seg_names), "slab without a parameter segment"
+    assert names is None or not set(slabs) - set(names), "slab outside the packed segments"
+    return work, blk

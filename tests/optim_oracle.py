@@ -45,7 +45,7 @@ import math
 import numpy as np
 import torch
 
-from distributed_tensorflow_resnet_amd.train.engine import (OPTW_DTYPE, SEG_DTYPE, opt_tile,
+from distributed_tensorflow_resnet_amd.train.layout import (OPTW_DTYPE, SEG_DTYPE, opt_tile,
                                                               sgd_tiles_work)
 
 U32 = 2.0 ** -24

@@ -11,7 +11,8 @@ import torch
 
 from distributed_tensorflow_resnet_amd.models.spec import cifar_spec
 from distributed_tensorflow_resnet_amd.train.backends import CPUBackend
-from distributed_tensorflow_resnet_amd.train.engine import constant_lr, lars_tables
+from distributed_tensorflow_resnet_amd.train.layout import lars_tables
+from distributed_tensorflow_resnet_amd.train.schedule import constant_lr
 from distributed_tensorflow_resnet_amd.utils import tensor_bundle as tb
 from distributed_tensorflow_resnet_amd.utils.flags import build_parser
 
@@ -34,7 +35,7 @@ def test_lars_flags(kind):
 def test_lars_tables():
     import numpy as np
 
-    from distributed_tensorflow_resnet_amd.train.engine import LARS_CHUNK, SEG_DTYPE
+    from distributed_tensorflow_resnet_amd.train.layout import LARS_CHUNK, SEG_DTYPE
 
     seg = np.zeros(4, dtype=SEG_DTYPE)
     seg["numel"] = [3, LARS_CHUNK, LARS_CHUNK + 1, 2 * LARS_CHUNK + 5]

@@ -5,8 +5,8 @@ import pytest
 import torch
 
 import optim_oracle as oo
-from distributed_tensorflow_resnet_amd.train.engine import (LRSchedule, cifar_lr_schedule,
-                                                              imagenet_lr_schedule)
+from distributed_tensorflow_resnet_amd.train.schedule import (LRSchedule, cifar_lr_schedule,
+                                                                imagenet_lr_schedule)
 
 SEVEN = LRSchedule(0.3, [10, 20, 35, 50, 80, 81, 1000],
                    [0.3, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005, 0.001],

@@ -411,30 +411,57 @@ static Launch mk_avgpool_bwd(ptr_t dp, ptr_t dx, int N, int HW, int C) {
   return [=](hipStream_t s) { avgpool_bwd(P<const bf16>(dp), P<bf16>(dx), N, HW, C, s); };
 }
 
-static Launch mk_softmax_xent(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                              ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                              float grad_scale, ptr_t probs, ptr_t ws) {
+// The loss-head ops take three trailing arguments that default to (0, 0, null):
+// label_smoothing in [0, 1), topk (k of the in-top-k count, 0: none) and topk_out (the
+// count; softmax_xent_reduce takes topk_out alone, head_fused the first two -- its flags
+// go to the workspace).  Each op is registered at both arities, so a call without them
+// means what it always meant.
+static void check_xent_opts(const char* op, float label_smoothing, int topk, ptr_t topk_out) {
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
+    throw std::invalid_argument(std::string(op) + ": label_smoothing in [0, 1), topk >= 0 "
+                                "(> 0 with topk_out)");
+}
+
+static Launch mk_softmax_xent_ls(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                                 ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                                 float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                                 int topk, ptr_t topk_out) {
+  check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
   return [=](hipStream_t s) {
     softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
                  P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
-                 P<float>(probs), P<float>(ws), s);
+                 P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s);
+  };
+}
+
+static Launch mk_softmax_xent(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                              ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                              float grad_scale, ptr_t probs, ptr_t ws) {
+  return mk_softmax_xent_ls(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
+                            grad_scale, probs, ws, 0.f, 0, 0);
+}
+
+static Launch mk_softmax_xent_reduce_k(ptr_t ws, int ld, int N, int classes, ptr_t loss_sum,
+                                       ptr_t correct, ptr_t dbias, ptr_t topk_out) {
+  return [=](hipStream_t s) {
+    softmax_xent_reduce(P<const float>(ws), ld, N, classes, P<float>(loss_sum), P<float>(correct),
+                        P<float>(dbias), P<float>(topk_out), s);
   };
 }
 
 static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t loss_sum,
                                      ptr_t correct, ptr_t dbias) {
-  return [=](hipStream_t s) {
-    softmax_xent_reduce(P<const float>(ws), ld, N, classes, P<float>(loss_sum), P<float>(correct),
-                        P<float>(dbias), s);
-  };
+  return mk_softmax_xent_reduce_k(ws, ld, N, classes, loss_sum, correct, dbias, 0);
 }
 
 // head_fused(x, bn=[acc, gamma, beta, mmean, mvar, mean, rstd, scale, shift], momentum, eps,
 //            update_moving, w_hwio, bias, labels, shape=[N, HW, C, classes, kpad], grad_scale,
-//            out=[pooled, dlogits, ws, dact, bacc])
-static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                            int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                            std::vector<int> shape, float grad_scale, std::vector<ptr_t> out) {
+//            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk])
+static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                               float label_smoothing, int topk) {
+  check_xent_opts("head_fused", label_smoothing, topk, 0);
   if (bn.size() != 9 || shape.size() != 5 || out.size() != 5)
     throw std::invalid_argument("head_fused: bn needs 9 pointers, shape 5 ints, out 5 pointers");
   HeadArgs a{};
@@ -465,16 +492,26 @@ static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, floa
   a.ws = P<float>(out[2]);
   a.dact = P<bf16>(out[3]);
   a.bacc = P<double>(out[4]);
+  a.label_smoothing = label_smoothing;
+  a.topk = topk;
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
   return [a](hipStream_t s) { head_fused(a, s); };
+}
+
+static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                            int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                            std::vector<int> shape, float grad_scale, std::vector<ptr_t> out) {
+  return mk_head_fused_ls(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
+                          std::move(shape), grad_scale, std::move(out), 0.f, 0);
 }
 
 // Persistent small-batch CIFAR step (prn_fwd.hip, prn_bwd.hip).  mode 0: forward launch,
 // 1: backward launch, 2: head folds.  `args` is keyed by the PrnArgs member names
 // (pointers as integers; bucket_of_stage a 3-sequence) plus wgrad_wgs, the backward's
 // weight-gradient workgroups; probe and shards are set by the launch functions.  A
-// missing key and a key that is no PrnArgs member both raise, naming the key.
+// missing key and a key that is no PrnArgs member both raise, naming the key -- except
+// label_smoothing, topk and topk_out, which may be left out (0, 0, null).
 static Launch mk_prn(int mode, py::dict args) {
   std::vector<std::string> known;
   auto get = [&](const char* key) -> py::object {
@@ -517,12 +554,16 @@ static Launch mk_prn(int mode, py::dict args) {
   PRN_VAL(update_moving);
   PRN_VAL(overlap);
   PRN_VAL(fault_bar);
-#undef PRN_PTR
-#undef PRN_VAL
   const auto bos = get("bucket_of_stage").cast<std::vector<int>>();
   if (bos.size() != 3) throw std::invalid_argument("prn: bucket_of_stage needs 3 entries");
   for (int i = 0; i < 3; ++i) a.bucket_of_stage[i] = bos[i];
   const int wgs = get("wgrad_wgs").cast<int>();
+  if (args.contains("label_smoothing")) PRN_VAL(label_smoothing);
+  if (args.contains("topk")) PRN_VAL(topk);
+  if (args.contains("topk_out")) PRN_PTR(topk_out);
+  check_xent_opts("prn", a.label_smoothing, a.topk, (ptr_t)(uintptr_t)a.topk_out);
+#undef PRN_PTR
+#undef PRN_VAL
   for (auto kv : args) {   // (every key read above exists, so any other is unknown)
     const std::string key = py::str(kv.first);
     if (std::find(known.begin(), known.end(), key) == known.end())
@@ -1275,11 +1316,14 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "bnrelu_avgpool", mk_bnrelu_avgpool);
   def_op(m, plan, "avgpool_bwd", mk_avgpool_bwd);
   def_op(m, plan, "softmax_xent", mk_softmax_xent);
+  def_op(m, plan, "softmax_xent", mk_softmax_xent_ls);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce);
+  def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce_k);
   def_op(m, plan, "bn_bwd_apply_acc", mk_bn_bwd_apply_acc);
   m.def("bn_bwd_apply_acc_fits", &bn_bwd_apply_acc_fits,
         "whether bn_bwd_apply_acc (finalize fused into the apply) covers (M, C)");
   def_op(m, plan, "head_fused", mk_head_fused);
+  def_op(m, plan, "head_fused", mk_head_fused_ls);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
   def_op(m, plan, "prn_infer", mk_prn_infer);

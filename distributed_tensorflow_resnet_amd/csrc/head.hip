@@ -12,6 +12,7 @@
 #include "bn_fused.h"
 #include "common.h"
 #include "kernels.h"
+#include "xent_row.h"
 
 namespace dtr {
 
@@ -92,51 +93,39 @@ void avgpool_bwd(const bf16* dpooled, bf16* dx, int N, int HW, int C, hipStream_
 
 // Single 1024-thread block (N <= a few thousand rows): one wave per row at a
 // time, fixed reduction order -> deterministic loss / precision / dbias.
-// dlogits = (softmax - onehot) * grad_scale   (grad_scale = 1/global_batch).
+// dlogits = (softmax - target) * grad_scale   (grad_scale = 1/global_batch); the row
+// math is xent_row's (xent_row.h).
 __global__ void __launch_bounds__(1024)
 softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                     int N, int classes, float* loss_sum, float* correct,
                     bf16* __restrict__ dlogits, float* __restrict__ dbias, float grad_scale,
-                    float* __restrict__ probs) {
+                    float* __restrict__ probs, float eps, int topk, float* topk_out) {
   extern __shared__ __attribute__((aligned(16))) float sh[];  // [16 waves][ld] dbias partial + misc
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nw = blockDim.x >> 6;
   float* db = sh;                    // [nw][ld]
   float* wl = sh + nw * ld;          // [nw] loss
   float* wc = wl + nw;               // [nw] correct
+  float* wk = wc + nw;               // [nw] in top k
   for (int c = lane; c < ld; c += 64) db[wave * ld + c] = 0.f;
-  float lsum = 0.f, csum = 0.f;
+  float lsum = 0.f, csum = 0.f, ksum = 0.f;
   for (int row = wave; row < N; row += nw) {
     const float* z = logits + (long)row * ld;
-    float mx = -INFINITY;
-    int amax = 0;
-    for (int c = lane; c < classes; c += 64) {
-      const float v = z[c];
-      if (v > mx) { mx = v; amax = c; }
-    }
-    // wave argmax (first max on ties, like tf.argmax)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(mx, o, 64);
-      const int oa = __shfl_xor(amax, o, 64);
-      if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
-    }
-    float se = 0.f;
-    for (int c = lane; c < classes; c += 64) se += __expf(z[c] - mx);
-    se = wave_sum(se);
-    const float lse = mx + __logf(se);
     const int y = labels[row];
-    const float zy = (y >= 0 && y < classes) ? z[y] : lse;
+    const float zy = (y >= 0 && y < classes) ? z[y] : 0.f;
+    const XentRow r = xent_row<0>([&](int j) { return z[lane + 64 * j]; }, lane, classes, y, zy,
+                                  eps, topk);
     if (lane == 0) {
-      lsum += lse - zy;
-      csum += (amax == y) ? 1.f : 0.f;
+      lsum += r.loss;
+      csum += r.top1;
+      ksum += r.topk;
     }
     for (int c = lane; c < ld; c += 64) {
       float g = 0.f;
       if (c < classes) {
-        const float p = __expf(z[c] - lse);
+        const float p = r.prob(z[c]);
         if (probs) probs[(long)row * ld + c] = p;
-        g = (p - (c == y ? 1.f : 0.f)) * grad_scale;
+        g = r.grad(p, c == y, grad_scale);
       }
       if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
       db[wave * ld + c] += g;
@@ -145,6 +134,7 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
   if (lane == 0) {
     wl[wave] = lsum;
     wc[wave] = csum;
+    wk[wave] = ksum;
   }
   __syncthreads();
   for (int c = tid; c < ld; c += blockDim.x) {
@@ -153,13 +143,15 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
     if (dbias && c < classes) dbias[c] = t;
   }
   if (tid == 0) {
-    float l = 0.f, k = 0.f;
+    float l = 0.f, k = 0.f, k5 = 0.f;
     for (int w = 0; w < nw; ++w) {
       l += wl[w];
       k += wc[w];
+      k5 += wk[w];
     }
     if (loss_sum) *loss_sum = l;
     if (correct) *correct = k;
+    if (topk_out) *topk_out = k5;
   }
 }
 
@@ -174,7 +166,8 @@ template <int VPL>
 __global__ void __launch_bounds__(256)
 softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                          int N, int classes, bf16* __restrict__ dlogits, float grad_scale,
-                         float* __restrict__ probs, float* __restrict__ ws, bool want_g) {
+                         float* __restrict__ probs, float* __restrict__ ws, bool want_g,
+                         float eps, int topk) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;   // wave-uniform
@@ -185,23 +178,9 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
     const int c = lane + 64 * k;
     v[k] = c < classes ? z[c] : -INFINITY;
   }
-  float mx = -INFINITY;
-  int amax = 0x7fffffff;
-#pragma unroll
-  for (int k = 0; k < VPL; ++k)
-    if (v[k] > mx) { mx = v[k]; amax = lane + 64 * k; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {   // first max on ties, like tf.argmax
-    const float om = __shfl_xor(mx, o, 64);
-    const int oa = __shfl_xor(amax, o, 64);
-    if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
-  }
-  float se = 0.f;
-#pragma unroll
-  for (int k = 0; k < VPL; ++k) se += (lane + 64 * k < classes) ? __expf(v[k] - mx) : 0.f;
-  se = wave_sum(se);
-  const float lse = mx + __logf(se);
   const int y = labels[row];
+  const float zy = (y >= 0 && y < classes) ? z[y] : 0.f;
+  const XentRow r = xent_row<VPL>([&](int j) { return v[j]; }, lane, classes, y, zy, eps, topk);
   float* gw = ws + (long)row * ld;
 #pragma unroll
   for (int k = 0; k < VPL; ++k) {
@@ -209,27 +188,29 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
     if (c >= ld) break;
     float g = 0.f;
     if (c < classes) {
-      const float p = __expf(v[k] - lse);
+      const float p = r.prob(v[k]);
       if (probs) probs[(long)row * ld + c] = p;
-      g = (p - (c == y ? 1.f : 0.f)) * grad_scale;
+      g = r.grad(p, c == y, grad_scale);
     }
     if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
     if (want_g) gw[c] = g;
   }
   if (lane == 0) {
-    const float zy = (y >= 0 && y < classes) ? z[y] : lse;
     float* rs = ws + (long)N * ld + 2 * row;
-    rs[0] = lse - zy;
-    rs[1] = (amax == y) ? 1.f : 0.f;
+    rs[0] = r.loss;
+    rs[1] = r.top1;
+    if (topk > 0) ws[(long)N * ld + 2L * N + row] = r.topk;
   }
 }
 
 // grid = ceil(classes / 64) blocks of 256: thread (column c, row slice q = tid / 64)
 // sums rows q, q + 4, ... ; the 4 slices are added in fixed order.  Block 0 also
-// folds the per-row loss / correct flags.
+// folds the per-row loss / correct flags and, when `topk_out` is given, the in-top-k
+// flags behind them.
 __global__ void __launch_bounds__(256)
 softmax_xent_reduce_kernel(const float* __restrict__ ws, int ld, int N, int classes,
-                           float* loss_sum, float* correct, float* __restrict__ dbias) {
+                           float* loss_sum, float* correct, float* __restrict__ dbias,
+                           float* topk_out) {
   __shared__ float red[4][64];
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
   const int c = blockIdx.x * 64 + lane;
@@ -256,16 +237,24 @@ softmax_xent_reduce_kernel(const float* __restrict__ ws, int ld, int N, int clas
       if (loss_sum) *loss_sum = l;
       if (correct) *correct = k;
     }
+    if (topk_out) {   // uniform
+      const float* rk = rs + 2L * N;
+      float k5 = 0.f;
+      for (int r = lane; r < N; r += 64) k5 += rk[r];
+      k5 = wave_sum(k5);
+      if (lane == 0) *topk_out = k5;
+    }
   }
 }
 
-long softmax_xent_ws_floats(int N, int ld) { return (long)N * ld + 2L * N; }
+// [N][ld] gradient rows, [N][2] (loss, correct), [N] in-top-k flags
+long softmax_xent_ws_floats(int N, int ld) { return (long)N * ld + 3L * N; }
 
 void softmax_xent_reduce(const float* ws, int ld, int N, int classes, float* loss_sum,
-                         float* correct, float* dbias, hipStream_t s) {
+                         float* correct, float* dbias, float* topk_out, hipStream_t s) {
   const int cb = dbias ? (classes + 63) / 64 : 1;
   hipLaunchKernelGGL(softmax_xent_reduce_kernel, dim3((unsigned)cb), dim3(256), 0, s, ws, ld, N,
-                     classes, loss_sum, correct, dbias);
+                     classes, loss_sum, correct, dbias, topk_out);
   DTR_CHECK_LAUNCH();
 }
 
@@ -374,22 +363,11 @@ __global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
       for (int c = 0; c < C; ++c) acc += pool_s[c] * w_s[c * kpad + lane];
       z = acc + a.bias[lane];
     }
-    float mx = z;
-    int amax = lane < a.classes ? lane : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {   // first max on ties, like tf.argmax
-      const float om = __shfl_xor(mx, o, 64);
-      const int oa = __shfl_xor(amax, o, 64);
-      if (om > mx || (om == mx && oa < amax)) {
-        mx = om;
-        amax = oa;
-      }
-    }
-    const float se = wave_sum(lane < a.classes ? __expf(z - mx) : 0.f);
-    const float lse = mx + __logf(se);
     const float zy = __shfl(z, (y >= 0 && y < a.classes) ? y : 0, 64);
+    const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
+                                  a.label_smoothing, a.topk);
     float g = 0.f;
-    if (lane < a.classes) g = (__expf(z - lse) - (lane == y ? 1.f : 0.f)) * a.grad_scale;
+    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, a.grad_scale);
     if (lane < kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)n * kpad + lane] = gb;
@@ -398,8 +376,9 @@ __global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
     }
     if (lane == 0) {
       float* rs = a.ws + (long)a.N * kpad + 2 * n;
-      rs[0] = lse - ((y >= 0 && y < a.classes) ? zy : lse);
-      rs[1] = (amax == y) ? 1.f : 0.f;
+      rs[0] = r.loss;
+      rs[1] = r.top1;
+      if (a.topk > 0) a.ws[(long)a.N * kpad + 2L * a.N + n] = r.topk;
     }
   }
   __syncthreads();
@@ -472,30 +451,31 @@ void head_fused(const HeadArgs& a, hipStream_t s) {
 
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias, float grad_scale,
-                  float* probs, float* ws, hipStream_t s) {
+                  float* probs, float* ws, float label_smoothing, int topk, float* topk_out,
+                  hipStream_t s) {
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
+    throw std::invalid_argument("softmax_xent: label_smoothing in [0, 1), topk >= 0 (> 0 with topk_out)");
   if (ws != nullptr && ld <= 1024) {
     const dim3 grid((unsigned)((N + 3) / 4));
     const bool want_g = dbias != nullptr;
     if (ld <= 64)
       hipLaunchKernelGGL(softmax_xent_rows_kernel<1>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
     else if (ld <= 256)
       hipLaunchKernelGGL(softmax_xent_rows_kernel<4>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
     else
       hipLaunchKernelGGL(softmax_xent_rows_kernel<16>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
     DTR_CHECK_LAUNCH();
-    const int cb = dbias ? (classes + 63) / 64 : 1;
-    hipLaunchKernelGGL(softmax_xent_reduce_kernel, dim3((unsigned)cb), dim3(256), 0, s, ws, ld, N,
-                       classes, loss_sum, correct, dbias);
-    DTR_CHECK_LAUNCH();
+    softmax_xent_reduce(ws, ld, N, classes, loss_sum, correct, dbias, topk_out, s);
     return;
   }
   const int threads = 1024, nw = threads / 64;
-  const size_t lds = ((size_t)nw * ld + 2 * nw) * sizeof(float);
+  const size_t lds = ((size_t)nw * ld + 3 * nw) * sizeof(float);
   hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels, N,
-                     classes, loss_sum, correct, dlogits, dbias, grad_scale, probs);
+                     classes, loss_sum, correct, dlogits, dbias, grad_scale, probs, label_smoothing,
+                     topk, topk_out);
   DTR_CHECK_LAUNCH();
 }
 

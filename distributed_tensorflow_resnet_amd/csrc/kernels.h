@@ -285,10 +285,12 @@ struct PrnArgs {
   bf16* pooled;              // [N][64]
   bf16* dlogits;             // [N][kpad]
   float* ws;                 // softmax_xent workspace: [N][kpad] gradient rows, then [N][2]
+                             // (loss, correct), then [N] in-top-k flags (topk > 0)
   float* dpool;              // [N][64] fp32: average-pool gradient per channel (dact)
   // the head's batch folds (prn_head):
   float* loss_sum;           // sum of the per-image losses
   float* correct;            // number of correct top-1 predictions
+  float* topk_out = nullptr; // number of labels in the top `topk` logits (nullptr: not folded)
   float* dbias;              // [classes] dense bias gradient
   float* dense_grad;         // [64][classes] fp32 dense weight gradient (HWIO)
   bf16* dx0;                 // backward: gradient of the stem output [N][32][32][16]
@@ -296,6 +298,8 @@ struct PrnArgs {
   int nitems;
   int N, P, classes, kpad;   // P: row slices (workgroups) per image
   float grad_scale;          // 1 / global batch
+  float label_smoothing = 0.f;   // softmax cross-entropy target smoothing in [0, 1) (xent_row.h)
+  int topk = 0;              // k of the in-top-k flags (0: none)
   float momentum, eps;
   int update_moving;
   long long* probe = nullptr;   // diagnostics: workgroup 0's (tag, wall clock) phase stamps
@@ -479,18 +483,23 @@ struct HeadArgs {
   float grad_scale;         // 1 / global batch
   bf16* pooled;             // [N][C]
   bf16* dlogits;            // [N][kpad]
-  float* ws;                // softmax_xent workspace: [N][kpad] fp32 gradient rows, [N][2]
+  float* ws;                // softmax_xent workspace: [N][kpad] fp32 gradient rows, [N][2],
+                            // [N] in-top-k flags (softmax_xent_ws_floats)
   bf16* dact;               // [N][HW][C] gradient of the pooled activations
   double* bacc;             // final BN backward accumulators (sum g, sum g*xhat)
+  float label_smoothing = 0.f;   // target smoothing in [0, 1) (xent_row.h)
+  int topk = 0;             // k of the in-top-k flags (0: none written)
 };
 bool head_fused_supported(int N, int HW, int C, int classes, int kpad);
 void head_fused(const HeadArgs& a, hipStream_t s);
+// topk_out (may be nullptr): the sum of the workspace's in-top-k flags
 void softmax_xent_reduce(const float* ws, int ld, int N, int classes, float* loss_sum,
-                         float* correct, float* dbias, hipStream_t s);
+                         float* correct, float* dbias, float* topk_out, hipStream_t s);
 void avgpool_bwd(const bf16* dpooled, bf16* dx, int N, int HW, int C, hipStream_t s);
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias,
-                  float grad_scale, float* probs, float* ws, hipStream_t s);
+                  float grad_scale, float* probs, float* ws, float label_smoothing, int topk,
+                  float* topk_out, hipStream_t s);
 long softmax_xent_ws_floats(int N, int ld);
 
 // ---- max pool (ImageNet stem) ----

@@ -651,17 +651,19 @@ __device__ __forceinline__ bool prn_bwd_slices(const PrnArgs& a, char* smem, int
 __device__ void prn_head_fold(const PrnArgs& a, char* smem, int tid) {
   const int N = a.N, ld = a.kpad, classes = a.classes;
   // every operand into LDS with one round of 16-byte loads: the fp32 gradient rows and
-  // the per-image (loss, correct) pairs of the softmax workspace, pooled [N][64] and
-  // dlogits [N][ld] (bf16); rows of 64 and ld (% 16) elements are whole 16-B chunks,
-  // the pair block goes in 8-byte pieces
+  // the per-image (loss, correct) pairs and in-top-k flags of the softmax workspace, pooled
+  // [N][64] and dlogits [N][ld] (bf16); rows of 64 and ld (% 16) elements are whole 16-B
+  // chunks, the pair block goes in 8-byte pieces, the flags one by one
   float* red = reinterpret_cast<float*>(smem);           // [4][64]
-  float* sw = red + 256;                                  // [N][ld] + [N][2]
-  bf16* sp = reinterpret_cast<bf16*>(sw + ((N * ld + 2 * N + 3) & ~3));   // 16-B aligned
+  float* sw = red + 256;                                  // [N][ld] + [N][2] + [N]
+  bf16* sp = reinterpret_cast<bf16*>(sw + ((N * ld + 3 * N + 3) & ~3));   // 16-B aligned
   bf16* sd = sp + N * 64;
   for (int i = tid; i < N * ld / 4; i += PT)
     reinterpret_cast<f32x4*>(sw)[i] = ldg(reinterpret_cast<const f32x4*>(a.ws) + i);
   for (int i = tid; i < N; i += PT)
     reinterpret_cast<float2*>(sw + N * ld)[i] = ldg(reinterpret_cast<const float2*>(a.ws + N * ld) + i);
+  if (a.topk_out != nullptr)
+    for (int i = tid; i < N; i += PT) sw[N * ld + 2 * N + i] = ldg(a.ws + N * ld + 2 * N + i);
   for (int i = tid; i < N * 8; i += PT)
     reinterpret_cast<uint4*>(sp)[i] = ldg(reinterpret_cast<const uint4*>(a.pooled) + i);
   for (int i = tid; i < N * ld / 8; i += PT)
@@ -687,6 +689,13 @@ __device__ void prn_head_fold(const PrnArgs& a, char* smem, int tid) {
     if (lane == 0) {
       stg(a.loss_sum, l);
       stg(a.correct, k);
+    }
+    if (a.topk_out != nullptr) {   // uniform
+      const float* rk = rs + 2 * N;
+      float k5 = 0.f;
+      for (int r = lane; r < N; r += 64) k5 += rk[r];
+      k5 = wave_sum(k5);
+      if (lane == 0) stg(a.topk_out, k5);
     }
   }
   // dense weight gradient: thread (f = tid % 64, image chunk tid / 64 of 8) holds 16
@@ -799,7 +808,7 @@ static_assert(wg_lds(16, 16, 1, 32) <= LDS_TOTAL && wg_lds(32, 16, 2, 16) <= LDS
               "weight-gradient LDS");
 
 static size_t prn_head_lds(int N, int kpad) {
-  return 1024 + 32 + (size_t)N * ((64 + kpad) * sizeof(bf16) + (kpad + 2) * sizeof(float)) +
+  return 1024 + 32 + (size_t)N * ((64 + kpad) * sizeof(bf16) + (kpad + 3) * sizeof(float)) +
          8 * 64 * 16 * sizeof(float);
 }
 

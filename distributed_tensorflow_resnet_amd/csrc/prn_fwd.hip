@@ -2,6 +2,7 @@
 // head (dense, softmax cross-entropy, dense dgrad, pool gradient) in one launch.  The
 // design, the hand-off protocol and the device primitives are in prn_device.h.
 #include "prn_device.h"
+#include "xent_row.h"
 
 namespace dtr {
 
@@ -235,22 +236,11 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
       for (int c = 0; c < 64; ++c) acc += pool_s[c] * wd[c * a.kpad + lane];
       z = acc + a.dense_b[lane];
     }
-    float mx = z;
-    int amax = lane < a.classes ? lane : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {   // first max on ties, like tf.argmax
-      const float om = __shfl_xor(mx, o, 64);
-      const int oa = __shfl_xor(amax, o, 64);
-      if (om > mx || (om == mx && oa < amax)) {
-        mx = om;
-        amax = oa;
-      }
-    }
-    const float se = wave_sum(lane < a.classes ? __expf(z - mx) : 0.f);
-    const float lse = mx + __logf(se);
     const float zy = __shfl(z, (y >= 0 && y < a.classes) ? y : 0, 64);
+    const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
+                                  a.label_smoothing, a.topk);
     float g = 0.f;
-    if (lane < a.classes) g = (__expf(z - lse) - (lane == y ? 1.f : 0.f)) * a.grad_scale;
+    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, a.grad_scale);
     if (lane < a.kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)x.img * a.kpad + lane] = gb;
@@ -259,8 +249,9 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
     }
     if (lane == 0) {
       float* rs = a.ws + (long)a.N * a.kpad + 2 * x.img;
-      rs[0] = lse - ((y >= 0 && y < a.classes) ? zy : lse);
-      rs[1] = (amax == y) ? 1.f : 0.f;
+      rs[0] = r.loss;
+      rs[1] = r.top1;
+      if (a.topk > 0) a.ws[(long)a.N * a.kpad + 2L * a.N + x.img] = r.topk;
     }
   }
   __syncthreads();

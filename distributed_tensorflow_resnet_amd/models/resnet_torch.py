@@ -105,8 +105,9 @@ class TorchResNet:
             wd = _W.apply(wd)
         return q(x @ wd + self._p("dense/bias"), False)
 
-    def loss(self, logits, labels, weight_decay: float):
-        """cost = xent + wd * sum(l2_loss(v) for v in trainables) (resnet_model.py:78-86)."""
-        xent = ref.softmax_cross_entropy(logits, labels)
+    def loss(self, logits, labels, weight_decay: float, label_smoothing: float = 0.0):
+        """cost = xent + wd * sum(l2_loss(v) for v in trainables) (resnet_model.py:78-86);
+        xent with smoothed targets when label_smoothing > 0."""
+        xent = ref.softmax_cross_entropy(logits, labels, label_smoothing)
         l2 = (self.master * self.master).sum() * 0.5
         return xent, xent + weight_decay * l2

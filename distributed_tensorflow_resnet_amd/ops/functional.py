@@ -239,13 +239,18 @@ def avgpool_bwd(dpooled, H, W):
     return dx
 
 
-def softmax_xent(logits, labels, classes, grad_scale, want_probs=False):
-    """Returns (loss_sum, correct, dlogits bf16 [N][ld], dbias fp32 [classes], probs)."""
+def softmax_xent(logits, labels, classes, grad_scale, want_probs=False, label_smoothing=0.0,
+                 topk=0):
+    """Returns (loss_sum, correct, dlogits bf16 [N][ld], dbias fp32 [classes], probs) and,
+    when topk > 0, a sixth element: the number of rows whose label is in the top `topk`
+    logits (tf.nn.in_top_k).  label_smoothing in [0, 1) smooths the targets to
+    (1 - eps) * onehot + eps / classes."""
     _check(logits, torch.float32, 2, "logits")
     N, ld = logits.shape
     dev = logits.device
     loss = torch.zeros(1, device=dev)
     corr = torch.zeros(1, device=dev)
+    ink = torch.zeros(1, device=dev) if topk > 0 else None
     dl = torch.empty((N, ld), device=dev, dtype=BF16)
     db = torch.empty(classes, device=dev)
     probs = torch.zeros((N, ld), device=dev) if want_probs else None
@@ -253,8 +258,9 @@ def softmax_xent(logits, labels, classes, grad_scale, want_probs=False):
     ws = torch.empty(native().softmax_xent_ws_floats(N, ld), device=dev)
     native().softmax_xent(logits.data_ptr(), ld, labels.data_ptr(), N, classes, loss.data_ptr(),
                           corr.data_ptr(), dl.data_ptr(), db.data_ptr(), float(grad_scale),
-                          _ptr(probs), ws.data_ptr(), _stream())
-    return loss, corr, dl, db, probs
+                          _ptr(probs), ws.data_ptr(), float(label_smoothing), int(topk),
+                          _ptr(ink), _stream())
+    return (loss, corr, dl, db, probs, ink) if topk > 0 else (loss, corr, dl, db, probs)
 
 
 def maxpool_fwd(x, k=3, stride=2):

@@ -76,9 +76,31 @@ def max_pool_same(x: torch.Tensor, k: int = 3, stride: int = 2) -> torch.Tensor:
     return y.permute(0, 2, 3, 1)
 
 
-def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """tf.losses.softmax_cross_entropy(onehot, logits): mean over the batch."""
-    return F.cross_entropy(logits, labels.long(), reduction="mean")
+def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor,
+                          label_smoothing: float = 0.0) -> torch.Tensor:
+    """tf.losses.softmax_cross_entropy(onehot, logits, label_smoothing): mean over the
+    batch.  The smoothed target is (1 - eps) * onehot + eps / classes, so a row's loss is
+    lse - (1 - eps) * z[y] - (eps / classes) * sum(z)."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if label_smoothing == 0.0:
+        return F.cross_entropy(logits, labels.long(), reduction="mean")
+    eps, K = float(label_smoothing), logits.shape[1]
+    lse = torch.logsumexp(logits, dim=1)
+    zy = logits.gather(1, labels.long()[:, None])[:, 0]
+    return (lse - (1.0 - eps) * zy - (eps / K) * logits.sum(dim=1)).mean()
+
+
+def in_top_k(logits: torch.Tensor, labels: torch.Tensor, k: int) -> torch.Tensor:
+    """tf.nn.in_top_k: bool [N], true iff the label is a valid class, its logit is finite
+    and fewer than k classes have a strictly larger logit (ties at the boundary count
+    as in; k >= classes is true for every finite row)."""
+    K = logits.shape[1]
+    y = labels.long()
+    ok = (y >= 0) & (y < K)
+    zy = logits.gather(1, y.clamp(0, K - 1)[:, None])
+    above = (logits > zy).sum(dim=1)
+    return ok & torch.isfinite(zy[:, 0]) & (above < k)
 
 
 def l2_loss(v: torch.Tensor) -> torch.Tensor:

@@ -19,6 +19,7 @@ from ..data.cifar import augment_cpu
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
+from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_state
 
@@ -57,12 +58,12 @@ class GPUBackend:
             eng.step(need_cost)
         self._host_step += 1
 
-    def metrics(self):
+    def metrics(self, top5: bool = False):
         # rank-local (the session's hooks read metrics on their own schedules, chief-only
         # hooks on the chief only, so a collective here would be joined by nobody -- or,
         # with the c10d transport, by another rank's gradient all-reduce).  Like the
         # reference's per-worker LoggingTensorHook, each rank logs its own batch.
-        return self.engine.metrics(reduce=False)
+        return self.engine.metrics(reduce=False, top5=top5)
 
     def synchronize(self):
         torch.cuda.synchronize()
@@ -97,7 +98,8 @@ class CPUBackend:
                  optimizer: str = "mom", momentum: float = 0.9, seed: int = 0, dist_ctx=None,
                  global_batch: int | None = None, threads: int = 0,
                  allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
-                 lars_epsilon: float = 0.0, lars_skip: str = "vectors"):
+                 lars_epsilon: float = 0.0, lars_skip: str = "vectors",
+                 label_smoothing: float = 0.0):
         # intra-op threads: DTR_CPU_THREADS, default 1 -- on small containers the
         # OpenMP pool's spin-waits oversubscribe the CPU quota (measured here: one
         # 8x32x32x16 conv fwd+bwd 1.2 ms on 1 thread, 612 ms on 8)
@@ -114,6 +116,11 @@ class CPUBackend:
         self.model = TorchResNet(spec, self.store)
         self.mom = torch.zeros(self.store.n_train)
         self.wd = weight_decay
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+        self.label_smoothing = float(label_smoothing)
+        self.last_logits = None    # the last step's logits (detached)
+        self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
         if optimizer not in ("mom", "sgd", "lars"):
             raise ValueError(f"optimizer must be mom, sgd or lars, got {optimizer!r}")
@@ -130,6 +137,7 @@ class CPUBackend:
         self._x = None
         self._y = None
         self._last = {}
+        self._last_top5 = 0.0      # in-top-5 fraction of the last step
         self.profile_phases = False
         self.last_phase_ms = None
         if allreduce_dtype not in ("fp32", "bf16"):
@@ -152,7 +160,7 @@ class CPUBackend:
         if master.grad is not None:
             master.grad = None
         logits = m(self._x, True)
-        xent, _ = m.loss(logits, self._y, self.wd)
+        xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing)
         # mean over the GLOBAL batch: local mean * (local/global), then sum-allreduce
         (xent * (self.N / self.global_batch)).backward()
         g = master.grad
@@ -176,16 +184,19 @@ class CPUBackend:
                 master.sub_(lr * gp)
             l2 = 0.5 * float((master * master).sum())
             correct = float((logits.argmax(1) == self._y).float().sum())
-        loss_sum = float(xent) * self.N
+            top5 = float(ref.in_top_k(logits, self._y, 5).float().sum())
+            self.last_logits = logits.detach()
+        loss_sum = float(xent.detach()) * self.N
         if self.dist is not None and self.world > 1:
-            t = torch.tensor([loss_sum, correct])
+            t = torch.tensor([loss_sum, correct, top5])
             self.dist.all_reduce_sum(t)
-            loss_sum, correct = t.tolist()
+            loss_sum, correct, top5 = t.tolist()
         n = self.global_batch
         self.step_count += 1
         self._last = {"global_step": self.step_count, "cross_entropy": loss_sum / n,
                       "cost": loss_sum / n + self.wd * l2, "precision": correct / n, "lr": lr,
                       "l2": l2}
+        self._last_top5 = top5 / n
 
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
@@ -217,8 +228,12 @@ class CPUBackend:
 
         return lars_trust_summary({n: v[:3] for n, v in self._lars_state.items() if not v[3]})
 
-    def metrics(self):
-        return dict(self._last)
+    def metrics(self, top5: bool = False):
+        """The last step's scalars; ``top5`` adds `precision_top5` (as Engine.metrics)."""
+        m = dict(self._last)
+        if top5:
+            m["precision_top5"] = self._last_top5
+        return m
 
     def synchronize(self):
         pass
@@ -252,6 +267,7 @@ class CPUBackend:
             probs = torch.softmax(logits, 1)
             loss = torch.nn.functional.cross_entropy(logits, labels.long(), reduction="sum")
             correct = (logits.argmax(1) == labels.long()).float().sum()
+            self.last_eval_top5 = float(ref.in_top_k(logits, labels, 5).float().sum())
         return float(loss), float(correct), probs
 
 
@@ -261,7 +277,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  input_mode: str = "auto", data_seed: int = 1234,
                  allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0,
                  lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
-                 lars_skip: str = "vectors"):
+                 lars_skip: str = "vectors", label_smoothing: float = 0.0):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -277,11 +293,13 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      global_batch=global_batch, use_graph=use_graph, data_seed=data_seed,
                      allreduce_dtype=allreduce_dtype, resident=resident,
                      shuffle_seed=shuffle_seed, lars_eeta=lars_eeta,
-                     lars_epsilon=lars_epsilon, lars_skip=lars_skip)
+                     lars_epsilon=lars_epsilon, lars_skip=lars_skip,
+                     label_smoothing=label_smoothing)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
     return CPUBackend(spec, batch_size, weight_decay=weight_decay, lr_schedule=lr_schedule,
                       optimizer=optimizer, seed=seed, dist_ctx=dist_ctx,
                       global_batch=global_batch, allreduce_dtype=allreduce_dtype,
-                      lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip)
+                      lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip,
+                      label_smoothing=label_smoothing)

@@ -219,7 +219,7 @@ def main(argv=None, kind: str = "cifar") -> int:
                                        "cifar_resident" if resident is not None else "auto"),
                            resident=resident, shuffle_seed=flags.seed,
                            lars_eeta=flags.lars_eeta, lars_epsilon=flags.lars_epsilon,
-                           lars_skip=flags.lars_skip)
+                           lars_skip=flags.lars_skip, label_smoothing=flags.label_smoothing)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

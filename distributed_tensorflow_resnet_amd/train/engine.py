@@ -120,7 +120,8 @@ class Engine:
                  use_graph: bool = False, data_seed: int = 1234, fork_wgrad: bool | None = None,
                  allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None,
                  resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
-                 lars_epsilon: float = 0.0, lars_skip: str = "vectors"):
+                 lars_epsilon: float = 0.0, lars_skip: str = "vectors",
+                 label_smoothing: float = 0.0):
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
@@ -141,6 +142,13 @@ class Engine:
         self.lars_eeta, self.lars_epsilon = float(lars_eeta), float(lars_epsilon)
         self.lars_skip = lars_skip
         self.use_momentum = optimizer in ("mom", "lars")
+        # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
+        # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
+        # eval plans never smooth.
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+        self.label_smoothing = float(label_smoothing)
+        self.topk = min(5, spec.num_classes)   # k of the `precision_top5` count
         self.sched = lr_schedule
         self.use_graph = use_graph
         self.data_seed = data_seed
@@ -217,7 +225,8 @@ class Engine:
         self.grad = torch.zeros(self.params.n_train, device=dev)
         self.mom = torch.zeros(self.params.n_train, device=dev)
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.scalars = torch.zeros(8, device=dev)  # loss_sum, correct, lr, l2
+        # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
+        self.scalars = torch.zeros(8, device=dev)
         # sgd_tiles' last-workgroup ticket (the launch that steps global_step; left at zero)
         self.opt_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         # weight-gradient and all-reduce streams: one pair per process, created before
@@ -833,28 +842,33 @@ class Engine:
         self.labels.copy_(torch.randint(0, self.spec.num_classes, (self.N,), generator=g,
                                         dtype=torch.int32))
 
-    def metrics(self, reduce: bool = True) -> dict:
+    def metrics(self, reduce: bool = True, top5: bool = False) -> dict:
         """Host read of the last step's scalars (synchronises).  The `cost` term
         wd * 1/2 sum v^2 is exact (pre-update weights) when the step ran with
         need_cost=True; otherwise it is computed now from the updated weights.
         ``reduce``: loss and precision over the whole global batch -- a collective
-        that EVERY rank must call at the same point; False: this rank's batch."""
+        that EVERY rank must call at the same point; False: this rank's batch.
+        ``top5`` adds `precision_top5` (in-top-k, k = min(5, classes)); without it the
+        keys are the ones callers that store every scalar have always got."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
         v = self.scalars.detach().cpu().tolist()
         self.check_health(v[4])
-        loss_sum, correct, lr, l2 = v[0], v[1], v[2], v[3]
+        loss_sum, correct, lr, l2, top5_sum = v[0], v[1], v[2], v[3], v[5]
         if reduce and self.dist is not None and self.world > 1:
-            t = torch.tensor([loss_sum, correct], device=self.device)
+            t = torch.tensor([loss_sum, correct, top5_sum], device=self.device)
             self.dist.all_reduce_sum(t)
-            loss_sum, correct = t.tolist()
+            loss_sum, correct, top5_sum = t.tolist()
             n = self.N * self.world
         else:
             n = self.N
         xent = loss_sum / n
-        return {"global_step": int(self.gstep.item()), "cross_entropy": xent,
-                "cost": xent + self.wd * l2, "precision": correct / n, "lr": lr, "l2": l2}
+        m = {"global_step": int(self.gstep.item()), "cross_entropy": xent,
+             "cost": xent + self.wd * l2, "precision": correct / n, "lr": lr, "l2": l2}
+        if top5:
+            m["precision_top5"] = top5_sum / n
+        return m
 
     def sync_from_params(self):
         """After loading master/stats from a checkpoint: reset step and repack."""

@@ -23,7 +23,8 @@ class _EvalPlan:
         self.probs = torch.zeros((N, eng.kpad), device=dev)
         self.xent_ws = torch.empty(eng.nat.softmax_xent_ws_floats(N, eng.kpad), device=dev)
         self.logits = torch.zeros((N, eng.kpad), device=dev)
-        self.scalars = torch.zeros(4, device=dev)
+        self.scalars = torch.zeros(4, device=dev)   # loss_sum, correct, in-top-5 count
+        self.top5 = 0.0   # the last run's in-top-5 count (tf.nn.in_top_k, k = min(5, classes))
         p = nat.Plan()
         self.plan = p
         self.input_plan = nat.Plan()
@@ -41,9 +42,10 @@ class _EvalPlan:
         else:
             self._record_layers(p)
         sp = self.scalars.data_ptr()
+        # evaluation is never smoothed: the loss stays comparable across training recipes
         p.softmax_xent(self.logits.data_ptr(), eng.kpad, self.labels.data_ptr(), N,
                        spec.num_classes, sp, sp + 4, 0, 0, 1.0, self.probs.data_ptr(),
-                       self.xent_ws.data_ptr())
+                       self.xent_ws.data_ptr(), 0.0, min(5, spec.num_classes), sp + 8)
 
     def attach(self, images, labels):
         """Keep a whole eval split (uint8 [M,3,32,32] + labels) on the device:
@@ -135,7 +137,8 @@ class _EvalPlan:
                     [], BN_DECAY, BN_EPS, 1)
 
     def run(self, images=None, labels=None, raw_u8: bool = True):
-        """Returns (loss_sum, correct, probs[N, classes]) for one eval batch.
+        """Returns (loss_sum, correct, probs[N, classes]) for one eval batch; the batch's
+        in-top-5 count is left in ``self.top5``.
 
         NOTE: the per-layer plan shares the per-BN scale/shift buffers with the
         training plan, so it must not run concurrently with a training step (the
@@ -155,4 +158,5 @@ class _EvalPlan:
             self.labels.copy_(labels.to(torch.int32))
         self.plan.run(0, self.plan.size(), st, 0)
         v = self.scalars.cpu().tolist()
+        self.top5 = v[2]
         return v[0], v[1], self.probs[:, :self.eng.spec.num_classes]

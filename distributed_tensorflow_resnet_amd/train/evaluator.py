@@ -6,11 +6,14 @@ model (GPU: the engine's forward-only plan with moving-average BN; CPU: the
 fp32 model), scores `eval_batch_count` batches, logs
 
     precision: 0.933, best precision: 0.936
+    precision@5: 0.997, best precision@5: 0.998
 
-and writes `Precision` / `Best_Precision` scalar summaries at the checkpoint's
-global_step into `eval_dir`.  `eval_once` evaluates a single checkpoint and
-returns; otherwise it sleeps `eval_interval_secs` (60 s in the reference)
-between polls and skips checkpoints it has already scored.
+(the first line is the reference's, the second this project's top-5 line) and writes
+`Precision` / `Best_Precision` and `Precision_top5` / `Best Precision_top5` scalar
+summaries at the checkpoint's global_step into `eval_dir`.  The loss is the unsmoothed
+cross-entropy whatever --label_smoothing the training run used.  `eval_once`
+evaluates a single checkpoint and returns; otherwise it sleeps `eval_interval_secs`
+(60 s in the reference) between polls and skips checkpoints it has already scored.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import time
 
 import torch
 
+from ..ops.reference import in_top_k
 from ..utils import tensor_bundle as tb
 from ..utils.checkpoint import tf_to_state
 from ..utils.records import EventWriter
@@ -33,6 +37,7 @@ class GPUInference:
         self.plan = self.engine.build_eval_plan(batch_size)
         # "persistent" (one prn_infer launch + softmax) or "per-layer" (tune persist_eval)
         self.eval_path = self.plan.kind
+        self.last_top5 = 0.0   # in-top-5 count of the last run's valid rows
 
     def load(self, tensors):
         tf_to_state(tensors, self.engine.params, None, strict=True)
@@ -55,9 +60,11 @@ class GPUInference:
             y = labels.to(p.device).long()
             loss = float(-torch.log(p.gather(1, y[:, None]).clamp_min(1e-30)).sum())
             correct = float((p.argmax(1) == y).sum())
+            self.last_top5 = float(in_top_k(p, y, 5).sum())
             return loss, correct, probs[:n]
         loss, correct, probs = self.plan.run(images.to(self.engine.device),
                                              labels.to(self.engine.device), raw_u8=raw)
+        self.last_top5 = self.plan.top5
         return loss, correct, probs
 
     # ---- device-resident eval split (CIFAR): no per-batch image copy
@@ -85,7 +92,9 @@ class GPUInference:
             y = self.plan.labels[:n_valid].long()
             loss = float(-torch.log(p.gather(1, y[:, None]).clamp_min(1e-30)).sum())
             correct = float((p.argmax(1) == y).sum())
+            self.last_top5 = float(in_top_k(p, y, 5).sum())
             return loss, correct, probs[:n_valid]
+        self.last_top5 = self.plan.top5
         return loss, correct, probs
 
 
@@ -95,12 +104,15 @@ class CPUInference:
         from .engine import constant_lr
 
         self.backend = CPUBackend(spec, batch_size, weight_decay=0.0, lr_schedule=constant_lr(0.0))
+        self.last_top5 = 0.0
 
     def load(self, tensors):
         tf_to_state(tensors, self.backend.store, None, strict=True)
 
     def run(self, images, labels):
-        return self.backend.evaluate_batch(images, labels)
+        loss, correct, probs = self.backend.evaluate_batch(images, labels)
+        self.last_top5 = self.backend.last_eval_top5
+        return loss, correct, probs
 
 
 def make_inference(spec, batch_size: int, device: str = "auto"):
@@ -109,29 +121,33 @@ def make_inference(spec, batch_size: int, device: str = "auto"):
     return GPUInference(spec, batch_size) if device == "gpu" else CPUInference(spec, batch_size)
 
 
-def evaluate_checkpoint(model, prefix: str, batches, eval_batch_count: int):
-    """Restore `prefix`, score up to eval_batch_count batches -> (precision, loss, step).
+def evaluate_checkpoint(model, prefix: str, batches, eval_batch_count: int, top5: bool = False):
+    """Restore `prefix`, score up to eval_batch_count batches -> (precision, loss, step),
+    with ``top5`` -> (precision, loss, step, top-5 precision).
     A model with an attached device-resident split (GPUInference.attach) scores that
     split's batches, in order, instead of `batches()`."""
     tensors = tb.read_bundle(prefix)
     model.load(tensors)
     step = int(tensors.get("global_step", 0))
-    total = correct = loss = 0.0
+    total = correct = loss = in5 = 0.0
     if getattr(model, "attached", False):   # the split already lives on the device
         for i, n in enumerate(model.resident_batch_sizes()[:eval_batch_count]):
             l, c, _ = model.run_resident(i, n)
             loss += l
             correct += c
+            in5 += model.last_top5
             total += n
-        return (correct / max(total, 1.0)), (loss / max(total, 1.0)), step
-    for i, (x, y) in enumerate(batches()):
-        if i >= eval_batch_count:
-            break
-        l, c, _ = model.run(x, y)
-        loss += l
-        correct += c
-        total += y.shape[0]
-    return (correct / max(total, 1.0)), (loss / max(total, 1.0)), step
+    else:
+        for i, (x, y) in enumerate(batches()):
+            if i >= eval_batch_count:
+                break
+            l, c, _ = model.run(x, y)
+            loss += l
+            correct += c
+            in5 += getattr(model, "last_top5", 0.0)
+            total += y.shape[0]
+    out = (correct / max(total, 1.0)), (loss / max(total, 1.0)), step
+    return out + (in5 / max(total, 1.0),) if top5 else out
 
 
 class SidecarEvaluator:
@@ -147,8 +163,10 @@ class SidecarEvaluator:
         self.interval = interval_s
         self.exit_if_none = exit_if_no_checkpoint
         self.best = 0.0
+        self.best_top5 = 0.0
         self.last_prefix = None
-        self.history = []
+        self.history = []        # (step, precision, loss) per scored checkpoint
+        self.history_top5 = []   # its top-5 precision
         path = getattr(model, "eval_path", None)
         if path is not None:
             log(f"INFO:tensorflow:eval forward path: {path}")
@@ -163,14 +181,21 @@ class SidecarEvaluator:
                 if self.exit_if_none or self.once:
                     return self.history
             elif prefix != self.last_prefix:
-                prec, loss, step = evaluate_checkpoint(self.model, prefix, self.batches, self.count)
+                prec, loss, step, prec5 = evaluate_checkpoint(self.model, prefix, self.batches,
+                                                              self.count, top5=True)
                 self.best = max(self.best, prec)
+                self.best_top5 = max(self.best_top5, prec5)
                 self.last_prefix = prefix
                 self.history.append((step, prec, loss))
+                self.history_top5.append(prec5)
                 log(f"INFO:tensorflow:loss: {loss:.3f}, precision: {prec:.3f}, "
                     f"best precision: {self.best:.3f}")
+                log(f"INFO:tensorflow:precision@5: {prec5:.3f}, "
+                    f"best precision@5: {self.best_top5:.3f}")
                 if self.writer is not None:
-                    self.writer.add_scalars(step, {"Precision": prec, "Best_Precision": self.best})
+                    self.writer.add_scalars(step, {"Precision": prec, "Best_Precision": self.best,
+                                                   "Precision_top5": prec5,
+                                                   "Best Precision_top5": self.best_top5})
                     self.writer.flush()
                 if self.once:
                     return self.history

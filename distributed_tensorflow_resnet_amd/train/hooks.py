@@ -127,8 +127,11 @@ class SummarySaverHook(Hook):
     def after_run(self, session, step):
         if self.writer is not None and self.n > 0 and step % self.n == 0 and session.is_chief:
             m = session.metrics()
-            self.writer.add_scalars(step, {"cross_entropy": m["cross_entropy"], "cost": m["cost"],
-                                           "learning_rate": m["lr"], self.tag: m["precision"]})
+            vals = {"cross_entropy": m["cross_entropy"], "cost": m["cost"],
+                    "learning_rate": m["lr"], self.tag: m["precision"]}
+            if "precision_top5" in m:
+                vals["Precision_top5"] = m["precision_top5"]
+            self.writer.add_scalars(step, vals)
             self.writer.flush()
 
     def end(self, session):

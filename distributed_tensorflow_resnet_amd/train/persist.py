@@ -418,6 +418,7 @@ class PersistStep:
             dlogits=eng.dlogits.data_ptr(), ws=eng.xent_ws.data_ptr(),
             dpool=self.dpool.data_ptr(),
             loss_sum=0 if fwd else sp, correct=0 if fwd else sp + 4,
+            topk_out=0 if fwd else sp + 20, label_smoothing=eng.label_smoothing, topk=eng.topk,
             dbias=0 if fwd else eng.dense_bias_grad, dense_grad=0 if fwd else eng.dense_grad,
             dx0=self.dx0.data_ptr(), items=self.item_dev.data_ptr(), nitems=len(self.items),
             N=eng.N, P=self.P_fwd if fwd else self.P, classes=spec.num_classes, kpad=eng.kpad,

@@ -710,7 +710,8 @@ class StepRecorder:
                             e.dense_bias, e.labels.data_ptr(),
                             [N, HL * WL, F, spec.num_classes, e.kpad], 1.0 / e.global_batch,
                             [e.pooled.data_ptr(), e.dlogits.data_ptr(),
-                             e.xent_ws.data_ptr(), dact.data_ptr(), fbn.bacc.data_ptr()])
+                             e.xent_ws.data_ptr(), dact.data_ptr(), fbn.bacc.data_ptr()],
+                            e.label_smoothing, e.topk)
         else:
             self._bn_finalize(fbn, consumer_conv=False)   # consumer: bnrelu_avgpool
             plan.bnrelu_avgpool(XL.data_ptr(), fbn.scale.data_ptr(), fbn.shift.data_ptr(),
@@ -720,7 +721,8 @@ class StepRecorder:
                            [], [], [], [], [], BN_DECAY, BN_EPS, 1)
             plan.softmax_xent(e.logits.data_ptr(), e.kpad, e.labels.data_ptr(), N,
                               spec.num_classes, sp, sp + 4, e.dlogits.data_ptr(),
-                              e.dense_bias_grad, 1.0 / e.global_batch, 0, e.xent_ws.data_ptr())
+                              e.dense_bias_grad, 1.0 / e.global_batch, 0, e.xent_ws.data_ptr(),
+                              e.label_smoothing, e.topk, sp + 20)
         return dact
 
     def _backward(self, dact):
@@ -746,7 +748,7 @@ class StepRecorder:
             # accumulator sums for the first dgrad's BN-backward prologue
             xr = lambda: plan.softmax_xent_reduce(  # noqa: E731
                 e.xent_ws.data_ptr(), e.kpad, N, spec.num_classes, sp, sp + 4,
-                e.dense_bias_grad)
+                e.dense_bias_grad, sp + 20)
             if e.fork_wgrad:
                 self._side_q += [xr, dense_wgrad]
             else:

@@ -53,7 +53,7 @@ class TrainingSession:
 
     def metrics(self) -> dict:
         if self._metrics_step != self.global_step:
-            self._metrics_cache = self.backend.metrics()
+            self._metrics_cache = self.backend.metrics(top5=True)
             self._metrics_step = self.global_step
         return self._metrics_cache
 

@@ -46,6 +46,16 @@ def str2bool(v) -> bool:
     raise argparse.ArgumentTypeError(f"not a boolean: {v!r}")
 
 
+def _smoothing(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < 1.0:
+        raise argparse.ArgumentTypeError(f"label smoothing must be in [0, 1), got {v!r}")
+    return f
+
+
 def _absl_bools(argv, bool_names):
     """Translate absl `--noflag` / bare `--flag` spellings for boolean flags."""
     out = []
@@ -150,6 +160,10 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="Tensors LARS does not adapt (trust = 1; they keep their weight decay): "
                         "'vectors' = every rank-1 tensor (BN gamma / beta, the dense bias), "
                         "'none' = adapt them too.")
+    p.add_argument("--label_smoothing", type=_smoothing, default=0.0,
+                   help="Training-loss label smoothing eps in [0, 1): targets (1 - eps) * onehot "
+                        "+ eps / classes (tf.losses.softmax_cross_entropy's label_smoothing).  "
+                        "Evaluation is never smoothed.")
     p.add_argument("--bucket_mb", type=float, default=0.0,
                    help="All-reduce bucket size (MiB); 0 = auto (~4 buckets, <= 25 MiB).")
     p.add_bool("use_graph", False, "Capture the training step in a hipGraph (single stream; "

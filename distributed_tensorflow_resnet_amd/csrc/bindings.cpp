@@ -724,6 +724,18 @@ static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, f
   };
 }
 
+static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
+                            float one_minus_decay, int warm) {
+  if ((master | shadow) & 15)
+    throw std::invalid_argument("ema_update: master and shadow must be 16-byte aligned");
+  if (!(one_minus_decay > 0.f && one_minus_decay <= 1.f))
+    throw std::invalid_argument("ema_update: one_minus_decay in (0, 1]");
+  return [=](hipStream_t s) {
+    ema_update(P<const float>(master), P<float>(shadow), n, P<const long long>(gstep),
+               one_minus_decay, warm, s);
+  };
+}
+
 static Launch mk_step_increment(ptr_t gstep) {
   return [=](hipStream_t s) { step_increment(P<long long>(gstep), s); };
 }
@@ -1348,6 +1360,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "lars_norms", mk_lars_norms);
   def_op(m, plan, "lars_trust", mk_lars_trust);
   def_op(m, plan, "lars_update_pack", mk_lars_update_pack);
+  def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);
   def_op(m, plan, "fill", mk_fill);

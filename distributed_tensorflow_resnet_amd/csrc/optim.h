@@ -68,6 +68,11 @@ void lars_update_pack(float* master, const float* grad, float* mom, long n, cons
                       const long long* gstep, float momentum, float wd, float grad_scale,
                       const ParamSeg* segs, int nseg, const float* trust, bf16* bf,
                       float* lr_out, hipStream_t st);
+// Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
+// one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
+// read; master and shadow must be 16-byte aligned.
+void ema_update(const float* master, float* shadow, long n, const long long* gstep,
+                float one_minus_decay, int warm, hipStream_t st);
 void step_increment(long long* gstep, hipStream_t s);
 int l2_workspace_floats();
 void l2_half_sum(const float* v, long n, float* ws, float* out, hipStream_t s);

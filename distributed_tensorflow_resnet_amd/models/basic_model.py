@@ -129,7 +129,9 @@ class ResNetModel(BasicModel):
                  cifar_lr_schedule() if cifar else imagenet_lr_schedule())
         self.backend = make_backend(self.spec, c["batch_size"], device=c["device"],
                                     weight_decay=2e-4 if cifar else 1e-4, lr_schedule=sched,
-                                    seed=self.random_seed)
+                                    seed=self.random_seed,
+                                    ema_decay=c.get("ema_decay", 0.0),
+                                    ema_warmup=c.get("ema_warmup", True))
 
     def _batches(self):
         """Synthetic batches of the dataset's shape (uint8 CIFAR records / NHWC floats)."""
@@ -153,10 +155,12 @@ class ResNetModel(BasicModel):
         return self.backend.metrics()
 
     def infer(self, images):
-        """Class probabilities of a batch (eval-mode BatchNorm, current weights)."""
+        """Class probabilities of a batch (eval-mode BatchNorm, current weights; config
+        ``eval_ema``: their EMA shadows, which needs ``ema_decay`` > 0)."""
         from ..train.evaluator import make_inference
 
-        inf = make_inference(self.spec, images.shape[0], device=self.config["device"])
+        inf = make_inference(self.spec, images.shape[0], device=self.config["device"],
+                             ema=bool(self.config.get("eval_ema", False)))
         inf.load(self.state_tensors())
         labels = torch.zeros(images.shape[0], dtype=torch.long)
         return inf.run(images, labels)[2]

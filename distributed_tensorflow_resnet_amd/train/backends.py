@@ -75,13 +75,21 @@ class GPUBackend:
 
     def state_tensors(self):
         self.check_health()
-        return state_to_tf(self.engine.params, self.engine.mom, self.global_step)
+        return state_to_tf(self.engine.params, self.engine.mom, self.global_step,
+                           ema=self.engine.ema)
 
     def load_state(self, tensors):
         eng = self.engine
-        gs = tf_to_state(tensors, eng.params, eng.mom, strict=True)
-        eng.sync_from_params()
+        gs = tf_to_state(tensors, eng.params, eng.mom, strict=True, ema=eng.ema)
+        eng.sync_from_params(ema_loaded=True)
         self._host_step = gs
+
+    @property
+    def ema_decay(self) -> float:
+        return self.engine.ema_decay
+
+    def ema_state(self):
+        return self.engine.ema_state()
 
     def lars_summary(self):
         return self.engine.lars_summary()
@@ -99,7 +107,7 @@ class CPUBackend:
                  global_batch: int | None = None, threads: int = 0,
                  allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
         # intra-op threads: DTR_CPU_THREADS, default 1 -- on small containers the
         # OpenMP pool's spin-waits oversubscribe the CPU quota (measured here: one
         # 8x32x32x16 conv fwd+bwd 1.2 ms on 1 thread, 612 ms on 8)
@@ -115,6 +123,11 @@ class CPUBackend:
         self.store.initialize(seed)
         self.model = TorchResNet(spec, self.store)
         self.mom = torch.zeros(self.store.n_train)
+        # EMA shadows of the trainables: csrc/ema.hip's expressions in fp32 torch
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self.ema = self.store.master.detach().clone() if self.ema_decay > 0 else None
         self.wd = weight_decay
         if not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
@@ -193,10 +206,28 @@ class CPUBackend:
             loss_sum, correct, top5 = t.tolist()
         n = self.global_batch
         self.step_count += 1
+        if self.ema is not None:
+            self._ema_update()
         self._last = {"global_step": self.step_count, "cross_entropy": loss_sum / n,
                       "cost": loss_sum / n + self.wd * l2, "precision": correct / n, "lr": lr,
                       "l2": l2}
         self._last_top5 = top5 / n
+
+    def _ema_update(self):
+        """shadow -= om * (shadow - master), k = the steps completed (csrc/ema.hip)."""
+        om = torch.tensor(1.0 - self.ema_decay, dtype=torch.float32)
+        if self.ema_warmup:
+            k = torch.tensor(float(10 + self.step_count), dtype=torch.float32)
+            om = torch.maximum(om, torch.tensor(9.0, dtype=torch.float32) / k)
+        with torch.no_grad():
+            self.ema.sub_(om * (self.ema - self.store.master))
+
+    def ema_state(self):
+        """{tensor name: view of its shadow} (None: ema_decay 0)."""
+        if self.ema is None:
+            return None
+        return {s.name: self.ema[s.offset:s.offset + s.numel].view(s.shape)
+                for s in self.store.train_slots}
 
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
@@ -242,16 +273,17 @@ class CPUBackend:
         pass
 
     def state_tensors(self):
-        return state_to_tf(self.store, self.mom, self.step_count)
+        return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema)
 
     def load_state(self, tensors):
         with torch.no_grad():
-            self.step_count = tf_to_state(tensors, self.store, self.mom)
+            self.step_count = tf_to_state(tensors, self.store, self.mom, ema=self.ema)
 
     def broadcast_parameters(self, src: int = 0):
         if self.dist is not None and self.world > 1:
             with torch.no_grad():
-                for t in (self.store.master, self.store.stats, self.mom):
+                for t in (self.store.master, self.store.stats, self.mom) + (
+                        (self.ema,) if self.ema is not None else ()):
                     self.dist.broadcast(t.data, src)
                 s = torch.tensor([self.step_count])
                 self.dist.broadcast(s, src)
@@ -277,7 +309,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  input_mode: str = "auto", data_seed: int = 1234,
                  allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0,
                  lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
-                 lars_skip: str = "vectors", label_smoothing: float = 0.0):
+                 lars_skip: str = "vectors", label_smoothing: float = 0.0,
+                 ema_decay: float = 0.0, ema_warmup: bool = True):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -294,7 +327,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      allreduce_dtype=allreduce_dtype, resident=resident,
                      shuffle_seed=shuffle_seed, lars_eeta=lars_eeta,
                      lars_epsilon=lars_epsilon, lars_skip=lars_skip,
-                     label_smoothing=label_smoothing)
+                     label_smoothing=label_smoothing, ema_decay=ema_decay,
+                     ema_warmup=ema_warmup)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -302,4 +336,5 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       optimizer=optimizer, seed=seed, dist_ctx=dist_ctx,
                       global_batch=global_batch, allreduce_dtype=allreduce_dtype,
                       lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip,
-                      label_smoothing=label_smoothing)
+                      label_smoothing=label_smoothing, ema_decay=ema_decay,
+                      ema_warmup=ema_warmup)

@@ -118,7 +118,7 @@ def resident_requested(flags, spec, device: str, data_path: str) -> bool:
 
 
 def run_eval(flags, spec, device: str):
-    model = make_inference(spec, flags.eval_batch_size, device)
+    model = make_inference(spec, flags.eval_batch_size, device, ema=flags.eval_ema)
     if resident_requested(flags, spec, device, flags.eval_data_path):
         from ..data.cifar import CifarData
 
@@ -219,7 +219,8 @@ def main(argv=None, kind: str = "cifar") -> int:
                                        "cifar_resident" if resident is not None else "auto"),
                            resident=resident, shuffle_seed=flags.seed,
                            lars_eeta=flags.lars_eeta, lars_epsilon=flags.lars_epsilon,
-                           lars_skip=flags.lars_skip, label_smoothing=flags.label_smoothing)
+                           lars_skip=flags.lars_skip, label_smoothing=flags.label_smoothing,
+                           ema_decay=flags.ema_decay, ema_warmup=flags.ema_warmup)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

@@ -121,7 +121,7 @@ class Engine:
                  allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None,
                  resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
@@ -149,6 +149,11 @@ class Engine:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
         self.label_smoothing = float(label_smoothing)
         self.topk = min(5, spec.num_classes)   # k of the `precision_top5` count
+        # shadow (exponential moving average) copy of the trainables, advanced by one launch
+        # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         self.sched = lr_schedule
         self.use_graph = use_graph
         self.data_seed = data_seed
@@ -224,6 +229,7 @@ class Engine:
         self.params.initialize(seed)
         self.grad = torch.zeros(self.params.n_train, device=dev)
         self.mom = torch.zeros(self.params.n_train, device=dev)
+        self.ema = self.params.master.detach().clone() if self.ema_decay > 0 else None
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
         # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
         self.scalars = torch.zeros(8, device=dev)
@@ -611,6 +617,18 @@ class Engine:
         return lars_trust_summary({n: v for (n, v), skip in zip(st.items(), self.lars_skipped)
                                    if not skip})
 
+    def ema_state(self):
+        """{tensor name: view of its shadow in the flat EMA buffer} (None: --ema_decay 0)."""
+        if self.ema is None:
+            return None
+        return {s.name: self.ema[s.offset:s.offset + s.numel].view(s.shape)
+                for s in self.params.train_slots}
+
+    def reset_ema(self):
+        """Shadows := the current weights (a fresh start, or a checkpoint without shadows)."""
+        if self.ema is not None:
+            self.ema.copy_(self.params.master.detach())
+
     def persist_error(self) -> bool:
         """Whether a persistent launch's barrier wait ever timed out (synchronises)."""
         return self.prn is not None and bool(self.prn.err.item())
@@ -870,23 +888,31 @@ class Engine:
             m["precision_top5"] = top5_sum / n
         return m
 
-    def sync_from_params(self):
-        """After loading master/stats from a checkpoint: reset step and repack."""
+    def sync_from_params(self, ema_loaded: bool = False):
+        """After loading master/stats from a checkpoint: reset step and repack.  The shadows
+        start from the loaded weights unless the caller has loaded them too (ema_loaded)."""
         self.gstep.fill_(self.params.global_step)
+        if not ema_loaded:
+            self.reset_ema()
         self.repack()
+
+    def _replicated(self):
+        """The state every rank holds a copy of (the shadows too when EMA is on)."""
+        ts = (self.params.master, self.params.stats, self.mom, self.gstep)
+        return ts + (self.ema,) if self.ema is not None else ts
 
     def broadcast_parameters(self, src: int = 0):
         """hvd.BroadcastGlobalVariablesHook(0) equivalent: weights, momentum,
-        BN moving statistics and global_step from `src` to every rank."""
+        BN moving statistics, global_step (and the EMA shadows) from `src` to every rank."""
         if self.dist is None or self.world == 1:
             return
         if self.comm is not None:
             st = torch.cuda.current_stream().cuda_stream
-            for t in (self.params.master, self.params.stats, self.mom, self.gstep):
+            for t in self._replicated():
                 code = self.nat.COMM_I64 if t.dtype == torch.int64 else self.nat.COMM_F32
                 self.comm.broadcast(t.data_ptr(), t.numel(), code, src, st)
         else:
-            for t in (self.params.master, self.params.stats, self.mom, self.gstep):
+            for t in self._replicated():
                 self.dist.broadcast(t, src)
         self.repack()
 

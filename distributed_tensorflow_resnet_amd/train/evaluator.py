@@ -23,14 +23,16 @@ import torch
 
 from ..ops.reference import in_top_k
 from ..utils import tensor_bundle as tb
-from ..utils.checkpoint import tf_to_state
+from ..utils.checkpoint import ema_weights, tf_to_state
 from ..utils.records import EventWriter
 from .hooks import log
 
 
 class GPUInference:
-    def __init__(self, spec, batch_size: int, device=None):
+    def __init__(self, spec, batch_size: int, device=None, ema: bool = False):
         from .engine import Engine, constant_lr
+
+        self.ema = bool(ema)   # score the checkpoint's EMA shadows instead of its weights
 
         self.engine = Engine(spec, batch_size, weight_decay=0.0, lr_schedule=constant_lr(0.0),
                              device=device, use_graph=False)
@@ -40,6 +42,8 @@ class GPUInference:
         self.last_top5 = 0.0   # in-top-5 count of the last run's valid rows
 
     def load(self, tensors):
+        if self.ema:   # trainables := their shadows (KeyError if the checkpoint has none)
+            tensors = ema_weights(tensors, self.engine.params)
         tf_to_state(tensors, self.engine.params, None, strict=True)
         self.engine.repack()
 
@@ -99,14 +103,18 @@ class GPUInference:
 
 
 class CPUInference:
-    def __init__(self, spec, batch_size: int):
+    def __init__(self, spec, batch_size: int, ema: bool = False):
         from .backends import CPUBackend
         from .engine import constant_lr
+
+        self.ema = bool(ema)
 
         self.backend = CPUBackend(spec, batch_size, weight_decay=0.0, lr_schedule=constant_lr(0.0))
         self.last_top5 = 0.0
 
     def load(self, tensors):
+        if self.ema:
+            tensors = ema_weights(tensors, self.backend.store)
         tf_to_state(tensors, self.backend.store, None, strict=True)
 
     def run(self, images, labels):
@@ -115,10 +123,13 @@ class CPUInference:
         return loss, correct, probs
 
 
-def make_inference(spec, batch_size: int, device: str = "auto"):
+def make_inference(spec, batch_size: int, device: str = "auto", ema: bool = False):
+    """``ema``: load() takes every trainable from its ``/ExponentialMovingAverage`` shadow
+    (utils/checkpoint.py ema_weights); BN moving statistics stay the checkpoint's."""
     if device == "auto":
         device = "gpu" if torch.cuda.is_available() else "cpu"
-    return GPUInference(spec, batch_size) if device == "gpu" else CPUInference(spec, batch_size)
+    return (GPUInference(spec, batch_size, ema=ema) if device == "gpu"
+            else CPUInference(spec, batch_size, ema=ema))
 
 
 def evaluate_checkpoint(model, prefix: str, batches, eval_batch_count: int, top5: bool = False):
@@ -167,6 +178,8 @@ class SidecarEvaluator:
         self.last_prefix = None
         self.history = []        # (step, precision, loss) per scored checkpoint
         self.history_top5 = []   # its top-5 precision
+        if getattr(model, "ema", False):
+            log("INFO:tensorflow:weights: ema")
         path = getattr(model, "eval_path", None)
         if path is not None:
             log(f"INFO:tensorflow:eval forward path: {path}")

@@ -158,6 +158,9 @@ class JsonlMetricsHook(Hook):
                 m["step_path"] = "persistent" if getattr(eng, "persist", False) else "per-layer"
                 m["persist_disabled_reason"] = getattr(eng, "persist_reason", "") or None
             m.update(_lars_summary(session) or {})   # lars_trust_min / _median / _max
+            ema = getattr(session.backend, "ema_decay", 0.0)
+            if ema:
+                m["ema_decay"] = ema
             os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
             with open(self.path, "a") as fh:
                 fh.write(json.dumps(m) + "\n")

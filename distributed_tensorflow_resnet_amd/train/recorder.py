@@ -586,6 +586,14 @@ class StepRecorder:
                            e.ohwi_tiles, e.wbf.data_ptr(), e.gstep.data_ptr())   # + global_step += 1
         if e.stem_s2d:
             plan.stem_s2d_pack(e.stem_master, e.stem_w4.data_ptr(), spec.stem.cout)
+        if e.ema is not None:
+            # the shadows follow the step's last update and its global_step += 1 (k = steps
+            # completed); main stream, every other stream joined: ordinary in-order work
+            i = plan.ema_update(master, e.ema.data_ptr(), e.params.n_train, e.gstep.data_ptr(),
+                                float(np.float32(1.0 - e.ema_decay)), int(e.ema_warmup))
+            if out.op_buffers:   # the overlap plan declares what its ops touch
+                out.op_buffers[i] = ({f"param:{b}" for b in range(len(e.buckets))}
+                                     | {"ema", "gstep"})
         out.t_opt_end = plan.timing_point("opt_end")
         out.seg["opt"] = (b2, plan.size())
         # 1/2 sum v^2 of the weights, which only feeds the logged `cost`

@@ -4,8 +4,9 @@ Variables saved exactly as the reference's MonitoredTrainingSession did
 (403 entries for CIFAR ResNet-50): every trainable
 under its TF name (HWIO conv kernels, BN gamma/beta, dense kernel/bias), its
 ``<name>/Momentum`` optimizer slot, the BN moving statistics and the int64
-``global_step``.  ``max_to_keep`` = 5, the ``checkpoint`` state file lists the
-retained prefixes, files are written to temporaries and renamed (a killed
+``global_step``; a run with ``--ema_decay`` adds ``<name>/ExponentialMovingAverage`` per
+trainable (tf.train.ExponentialMovingAverage's shadow variables).  ``max_to_keep``
+= 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
 from __future__ import annotations
@@ -19,25 +20,52 @@ import torch
 from . import tensor_bundle as tb
 
 
-def state_to_tf(store, momentum: torch.Tensor | None, global_step: int) -> dict[str, np.ndarray]:
-    """ParamStore (+flat momentum in the same layout) -> {TF name: array}."""
+EMA_SUFFIX = "/ExponentialMovingAverage"   # tf.train.ExponentialMovingAverage's shadow name
+
+
+def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
+                ema: torch.Tensor | None = None) -> dict[str, np.ndarray]:
+    """ParamStore (+flat momentum, +flat EMA shadows, in the same layout) -> {TF name: array}.
+    ``ema`` adds ``<name>/ExponentialMovingAverage`` per trainable; without it the entries
+    are exactly the reference's."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
     mom = momentum.detach().float().cpu().numpy() if momentum is not None else None
+    sh = ema.detach().float().cpu().numpy() if ema is not None else None
     for s in store.train_slots:
         out[s.name] = master[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if mom is not None:
             out[f"{s.name}/Momentum"] = mom[s.offset:s.offset + s.numel].reshape(s.shape).copy()
+        if sh is not None:
+            out[s.name + EMA_SUFFIX] = sh[s.offset:s.offset + s.numel].reshape(s.shape).copy()
     for s in store.stat_slots:
         out[s.name] = stats[s.offset:s.offset + s.numel].reshape(s.shape).copy()
     out["global_step"] = np.array(int(global_step), dtype=np.int64)
     return out
 
 
+def ema_weights(tensors: dict, store) -> dict:
+    """The tensor dict with every trainable replaced by its EMA shadow (what an
+    ``ema.variables_to_restore()`` restore gives TF); BN moving statistics, global_step and
+    everything else stay.  KeyError naming the first few when a shadow is missing: a
+    checkpoint of a run without --ema_decay is never scored as if it had them."""
+    missing = [s.name for s in store.train_slots if s.name + EMA_SUFFIX not in tensors]
+    if missing:
+        raise KeyError(f"checkpoint lacks the EMA shadows of {len(missing)} variables, e.g. "
+                       f"{[m + EMA_SUFFIX for m in missing[:3]]}")
+    out = dict(tensors)
+    for s in store.train_slots:
+        out[s.name] = tensors[s.name + EMA_SUFFIX]
+    return out
+
+
 def tf_to_state(tensors: dict, store, momentum: torch.Tensor | None = None,
-                strict: bool = True) -> int:
-    """Load {TF name: array} into the ParamStore (+momentum); returns global_step."""
+                strict: bool = True, ema: torch.Tensor | None = None) -> int:
+    """Load {TF name: array} into the ParamStore (+momentum, +EMA shadows); returns
+    global_step.  ``ema``: the flat shadow buffer of a run with --ema_decay > 0; a checkpoint
+    without (all of) the ``<name>/ExponentialMovingAverage`` entries starts every shadow
+    from the restored weights, with one log line.  Without ``ema`` the entries are ignored."""
     missing = []
     for s in store.train_slots + store.stat_slots:
         if s.name not in tensors:
@@ -54,6 +82,20 @@ def tf_to_state(tensors: dict, store, momentum: torch.Tensor | None = None,
                 momentum.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
     if strict and missing:
         raise KeyError(f"checkpoint lacks {len(missing)} variables, e.g. {missing[:3]}")
+    if ema is not None:
+        absent = [s.name for s in store.train_slots if s.name + EMA_SUFFIX not in tensors]
+        if absent:
+            print(f"INFO:tensorflow:checkpoint has no EMA shadows for {len(absent)} of "
+                  f"{len(store.train_slots)} variables (e.g. {absent[0] + EMA_SUFFIX}): every "
+                  "shadow starts from the restored weights", flush=True)
+            ema.data.copy_(store.master.detach())
+        else:
+            for s in store.train_slots:
+                a = np.asarray(tensors[s.name + EMA_SUFFIX], dtype=np.float32).reshape(-1)
+                if a.size != s.numel:
+                    raise ValueError(f"{s.name + EMA_SUFFIX}: {a.size} elements, expected "
+                                     f"{s.numel}")
+                ema.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
     gs = int(np.asarray(tensors.get("global_step", 0)))
     store.global_step = gs
     return gs

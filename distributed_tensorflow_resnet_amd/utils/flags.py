@@ -10,6 +10,7 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --dtype            bf16 (GPU compute) | fp32 (CPU path)
   --synthetic        synthetic data of the dataset's shape
   --resident_data    CIFAR split resident on the GPU, shuffled on the device
+  --ema_decay        device-side EMA of the weights, checkpointed; --eval_ema scores it
   --bucket_mb        gradient all-reduce bucket size
   --device           auto | gpu | cpu
   --use_graph        capture the training step in a hipGraph
@@ -53,6 +54,16 @@ def _smoothing(v) -> float:
         raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
     if not 0.0 <= f < 1.0:
         raise argparse.ArgumentTypeError(f"label smoothing must be in [0, 1), got {v!r}")
+    return f
+
+
+def _ema_decay(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < 1.0:
+        raise argparse.ArgumentTypeError(f"EMA decay must be in [0, 1), got {v!r}")
     return f
 
 
@@ -164,6 +175,17 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="Training-loss label smoothing eps in [0, 1): targets (1 - eps) * onehot "
                         "+ eps / classes (tf.losses.softmax_cross_entropy's label_smoothing).  "
                         "Evaluation is never smoothed.")
+    p.add_argument("--ema_decay", type=_ema_decay, default=0.0,
+                   help="Keep an exponential moving average of the trainable weights on the "
+                        "device: shadow -= (1 - decay) * (shadow - weight) after every step "
+                        "(tf.train.ExponentialMovingAverage; 0.9999 is TF's usual value), saved "
+                        "as <name>/ExponentialMovingAverage.  In [0, 1); 0 = off.")
+    p.add_bool("ema_warmup", True,
+               "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
+               "the average forgets the initial weights quickly.")
+    p.add_bool("eval_ema", False,
+               "Evaluate the checkpoint's EMA shadows instead of its raw weights (BN moving "
+               "statistics stay the raw ones); an error if the checkpoint has none.")
     p.add_argument("--bucket_mb", type=float, default=0.0,
                    help="All-reduce bucket size (MiB); 0 = auto (~4 buckets, <= 25 MiB).")
     p.add_bool("use_graph", False, "Capture the training step in a hipGraph (single stream; "

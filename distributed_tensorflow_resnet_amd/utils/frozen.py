@@ -282,13 +282,20 @@ def export_eval_meta_graph(spec: ModelSpec, tensors: dict) -> bytes:
 
 
 def freeze(prefix: str, out_path: str, dataset: str, resnet_size: int,
-           num_classes: int | None = None, meta_path: str | None = "") -> dict:
+           num_classes: int | None = None, meta_path: str | None = "",
+           ema: bool = False) -> dict:
     """Checkpoint (tensor bundle) -> frozen eval GraphDef `.pb` (freeze_graph
     equivalent), and the unfrozen eval graph's MetaGraphDef next to it
     (``meta_path``; "" = <dir>/resnet<size>_<cifar|imagenet>_eval_graph.meta,
-    None = skip)."""
+    None = skip).  ``ema``: the trainables' EMA shadows are frozen in, not the raw weights
+    (KeyError when the checkpoint has none)."""
     spec = build_spec(dataset, resnet_size, num_classes)
     tensors = tb.read_bundle(prefix)
+    if ema:
+        from types import SimpleNamespace
+
+        from .checkpoint import ema_weights
+        tensors = ema_weights(tensors, SimpleNamespace(train_slots=list(spec.trainables)))
     missing = [p.name for p in spec.params if p.name not in tensors]
     if missing:
         raise KeyError(f"{missing[:3]}... missing from {prefix}")

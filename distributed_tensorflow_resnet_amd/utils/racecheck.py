@@ -15,8 +15,8 @@ shows up in practice -- as a result that depends on the schedule:
    max_us)``), a different subset and duration each run and trial, so any pair
    of unordered ops overlaps in a different order each time;
 3. the final training state (fp32 master weights, momentum, BN moving
-   statistics, global_step) of every perturbed run must equal the reference's
-   BIT FOR BIT.  The step is deterministic by construction (fixed-order split-K
+   statistics, global_step, and the EMA shadows when on) of every perturbed
+   run must equal the reference's BIT FOR BIT.  The step is deterministic by construction (fixed-order split-K
    reduce, exact fp64 BN sums, RNG keyed on global_step), so any difference is
    an ordering bug: a missing fork, a missing join, or a buffer reused while an
    unordered stream still reads it.
@@ -39,8 +39,11 @@ import torch
 
 def engine_state(eng) -> Dict[str, torch.Tensor]:
     torch.cuda.synchronize()
-    return {"master": eng.params.master.detach().clone(), "momentum": eng.mom.detach().clone(),
-            "stats": eng.params.stats.detach().clone(), "global_step": eng.gstep.detach().clone()}
+    st = {"master": eng.params.master.detach().clone(), "momentum": eng.mom.detach().clone(),
+          "stats": eng.params.stats.detach().clone(), "global_step": eng.gstep.detach().clone()}
+    if getattr(eng, "ema", None) is not None:   # the EMA shadows, when the engine keeps them
+        st["ema"] = eng.ema.detach().clone()
+    return st
 
 
 def _diff(ref: Dict[str, torch.Tensor], got: Dict[str, torch.Tensor]) -> List[str]:
@@ -73,10 +76,11 @@ def perturbation_check(make_engine: Callable[[], object], steps: int = 3, trials
 
 
 def _make_factory(model: str, batch: int, device, loopback: bool = False,
-                  allreduce_dtype: str = "fp32", bucket_mb: float = 0.0):
+                  allreduce_dtype: str = "fp32", bucket_mb: float = 0.0, ema_decay: float = 0.0):
     """Engine factory; ``loopback``: with the comm stream active -- every bucket
     all-reduced (x2, csrc/comm.h loopback transport) on stream 2 between its
-    side-stream producers and the optimizer, bf16 casts included if asked."""
+    side-stream producers and the optimizer, bf16 casts included if asked.  ``ema_decay``
+    > 0: with the EMA launch recorded, its shadows part of the compared state."""
     from .. import native
     from ..models.spec import cifar_spec, imagenet_spec
     from ..train.engine import Engine, cifar_lr_schedule
@@ -94,7 +98,8 @@ def _make_factory(model: str, batch: int, device, loopback: bool = False,
             kw = dict(comm=native().Comm.loopback(2.0), allreduce_dtype=allreduce_dtype,
                       bucket_mb=bucket_mb or None)
         eng = Engine(spec, batch, weight_decay=2e-4, lr_schedule=cifar_lr_schedule(),
-                     device=device, seed=7, data_seed=99, use_graph=False, **kw)
+                     device=device, seed=7, data_seed=99, use_graph=False, ema_decay=ema_decay,
+                     **kw)
         eng.fill_synthetic(3)
         return eng
     return make
@@ -114,12 +119,14 @@ def main(argv=None):
                     help="comm stream active: loopback (x2) all-reduce of every bucket")
     ap.add_argument("--allreduce_dtype", default="fp32", choices=("fp32", "bf16"))
     ap.add_argument("--bucket_mb", type=float, default=0.0)
+    ap.add_argument("--ema_decay", type=float, default=0.0,
+                    help="> 0: record the weight-EMA launch and compare its shadows too")
     a = ap.parse_args(argv)
     res = perturbation_check(_make_factory(a.model, a.batch, torch.device("cuda", 0), a.loopback,
-                                           a.allreduce_dtype, a.bucket_mb),
+                                           a.allreduce_dtype, a.bucket_mb, a.ema_decay),
                              a.steps, a.trials, a.prob, a.max_us, a.seed)
     print(json.dumps(dict(res, model=a.model, batch=a.batch, loopback=a.loopback,
-                          allreduce_dtype=a.allreduce_dtype)))
+                          allreduce_dtype=a.allreduce_dtype, ema_decay=a.ema_decay)))
     return 0 if res["ok"] else 1
 
 

@@ -27,12 +27,15 @@ def main(argv=None):
     ap.add_argument("--resnet_size", type=int, default=50)
     ap.add_argument("--eval_data_path", default="")
     ap.add_argument("--device", default="auto", choices=("auto", "gpu", "cpu", "interp"))
+    ap.add_argument("--eval_ema", action="store_true",
+                    help="Freeze each trainable's /ExponentialMovingAverage shadow (a run with "
+                         "--ema_decay) instead of the raw weight.")
     a = ap.parse_args(argv)
     prefix = a.checkpoint_path or tb.latest_checkpoint(a.train_dir)
     if not prefix:
         print("no checkpoint found", file=sys.stderr)
         return 1
-    meta = freeze(prefix, a.output, a.dataset, a.resnet_size)
+    meta = freeze(prefix, a.output, a.dataset, a.resnet_size, ema=a.eval_ema)
     print(f"froze {prefix} -> {a.output}: {meta}")
     from resnet_cifar_predict_from_pd import main as predict
 

@@ -33,6 +33,8 @@ def main(argv=None):
     ap.add_argument("--resnet_size", type=int, default=50)
     ap.add_argument("--device", default="auto")
     ap.add_argument("--save_grid", default="", help="write a PNG grid of the predictions")
+    ap.add_argument("--eval_ema", action="store_true",
+                    help="Use each trainable's /ExponentialMovingAverage shadow (a run with --ema_decay).")
     a = ap.parse_args(argv)
     prefix = a.checkpoint_path or tb.latest_checkpoint(a.train_dir)
     if not prefix:
@@ -46,7 +48,7 @@ def main(argv=None):
     else:
         n = EVAL_NUM
         x, y = next(synthetic_batches(n, spec.num_classes, seed=7))
-    model = make_inference(spec, n, a.device)
+    model = make_inference(spec, n, a.device, ema=a.eval_ema)
     model.load(tb.read_bundle(prefix))
     _, correct, probs = model.run(x, y)
     pred = probs.argmax(1).cpu()

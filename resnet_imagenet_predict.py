@@ -45,6 +45,8 @@ def main(argv=None):
     ap.add_argument("--resnet_size", type=int, default=50)
     ap.add_argument("--num_images", type=int, default=16)
     ap.add_argument("--device", default="auto")
+    ap.add_argument("--eval_ema", action="store_true",
+                    help="Use each trainable's /ExponentialMovingAverage shadow (a run with --ema_decay).")
     a = ap.parse_args(argv)
     prefix = a.checkpoint_path or tb.latest_checkpoint(a.train_dir)
     if not prefix:
@@ -57,7 +59,7 @@ def main(argv=None):
     else:
         x, y = next(imagenet.synthetic_batches(n, spec.num_classes, spec.image_h, seed=7))
     names = read_labels(a.labels_file) if a.labels_file else None
-    model = make_inference(spec, n, a.device)
+    model = make_inference(spec, n, a.device, ema=a.eval_ema)
     model.load(tb.read_bundle(prefix))
     _, correct, probs = model.run(x, y)
     top = torch.topk(probs.float().cpu(), 5, dim=1)

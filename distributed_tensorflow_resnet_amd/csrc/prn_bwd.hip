@@ -183,14 +183,19 @@ __device__ __forceinline__ bf16x8 bwd8(bf16x8 da, bf16x8 x, bf16x8 add, bool has
 // Backward: slice workgroup 0 republishes every completed barrier as a count on its own
 // line (bar + PRN_READY): the ~190 weight-gradient workgroups poll that line instead of
 // the arrival shards the slices' atomics go to.
-// backward arrive; workgroup 0 then also counts a finished bucket of BatchNorm gradients
+// after a backward arrive workgroup 0 also counts a finished bucket of BatchNorm gradients
 // (x.mark), ordered after the arrive's drain of its write-through dgamma / dbeta stores
-__device__ __forceinline__ void arrive_bwd(Ctx& x) {
-  grid_arrive(x.a->bar + PRN_BWD, x.a->shards);
+// (thread 0's wave issued them, and drains in either arrive before thread 0 goes on)
+__device__ __forceinline__ void mark_bwd(Ctx& x) {
   if (x.mark != nullptr) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(x.mark, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     x.mark = nullptr;
   }
+}
+// backward arrive without BN sums in front of it
+__device__ __forceinline__ void arrive_bwd(Ctx& x) {
+  grid_arrive(x.a->bar + PRN_BWD, x.a->shards);
+  mark_bwd(x);
 }
 __device__ __forceinline__ bool wait_bwd(Ctx& x) {
   ++x.nbar;
@@ -200,10 +205,11 @@ __device__ __forceinline__ bool wait_bwd(Ctx& x) {
   return ok;
 }
 
-// sums of g = da [xs*scale+shift > 0] and g * xhat with the forward table tb
+// sums of g = da [xs*scale+shift > 0] and g * xhat with the forward table tb, then the
+// arrive at the backward barrier (bn_sums_arrive); probe tag `tag` (0: none) once the atomics are issued
 template <int S, int P>
-__device__ __forceinline__ void bwd_sums(Ctx& x, const bf16x4 (&da)[8], const bf16x4 (&xs)[8],
-                                         const float* tb, int bi, int wave, int lane) {
+__device__ __forceinline__ void bwd_sums_arrive(Ctx& x, const bf16x4 (&da)[8], const bf16x4 (&xs)[8],
+                                                const float* tb, int bi, int tag, int wave, int lane) {
   lane = opaque_v(lane);
   bn_sums<S, P>([&](int t, int r, float& s1, float& s2) {
     int pb, cb;
@@ -214,6 +220,9 @@ __device__ __forceinline__ void bwd_sums(Ctx& x, const bf16x4 (&da)[8], const bf
     s1 = gg;
     s2 = gg * fmaf(xf, tb[192 + c], tb[128 + c]);   // (tb[128] = -mean * rstd)
   }, x.m.red, ld_const(x.a->bns + (bi)).bacc, wave, lane);
+  if (tag) probe(x, tag);
+  bn_sums_arrive<P>(x.a->bar + PRN_BWD, x.a->shards, wave);
+  mark_bwd(x);
 }
 
 // dh = a g - b - c xhat (+ add) with the backward coefficient table cf
@@ -302,9 +311,8 @@ __device__ __forceinline__ bool block_bwd(Ctx& x, bf16x4 (&dout)[8], bf16x4 (&hs
   probe(x, 3);
   if constexpr (P > 1)   // only the neighbouring slices read it, only its border rows
     publish<S, P, 1>(da, B.da2 + img_o, x.kslice, wave, lane);
-  bwd_sums<S, P>(x, da, hs, x.m.tbl, B.bn2, wave, lane);
-  probe(x, 4);
-  arrive_bwd(x);
+  if constexpr (P > 1) probe(x, 20);
+  bwd_sums_arrive<S, P>(x, da, hs, x.m.tbl, B.bn2, 4, wave, lane);
   // dout for the conv2 / projection weight gradients and the neighbours' residual rows:
   // stored after this arrive and the next phase's prefetches (its drain overlaps the
   // wait), drained by the next arrive; from its halo in HB as whole 16-B units (the
@@ -348,9 +356,8 @@ __device__ __forceinline__ bool block_bwd(Ctx& x, bf16x4 (&dout)[8], bf16x4 (&hs
   probe(x, 9);
   if constexpr (P > 1)   // only the neighbouring slices read it, only its border rows
     publish<SI, P, 1>(da, B.da1 + img_i, x.kslice, wave, lane);
-  bwd_sums<SI, P>(x, da, xs, x.m.tbl, B.bn1, wave, lane);
-  probe(x, 10);
-  arrive_bwd(x);
+  if constexpr (P > 1) probe(x, 21);
+  bwd_sums_arrive<SI, P>(x, da, xs, x.m.tbl, B.bn1, 10, wave, lane);
   // dh1 for the conv1 weight gradient, from its halo (HA, intact until the next block
   // stages its own): stored after this arrive, drained by the next one
   halo_to_global<S, P>(x.m.ha, B.dh1 + img_o, x.kslice);
@@ -593,8 +600,7 @@ __device__ __forceinline__ bool prn_bwd_slices(const PrnArgs& a, char* smem, int
 #pragma unroll
       for (int r = 0; r < 4; ++r) dp[t][r] = (bf16)dps[(cb * 16 + 4 * (lane >> 4) + r) & 63];
     }
-    bwd_sums<2, P>(x, dp, xs, x.m.tbl, fb, wave, lane);
-    arrive_bwd(x);
+    bwd_sums_arrive<2, P>(x, dp, xs, x.m.tbl, fb, 0, wave, lane);
     bn_prefetch_bwd(ld_const(a.bns + (fb)), 64, x.bnr);
     bn_prefetch_tab(ld_const(a.bns + (BL.bn2)), 64, x.ftr);
     if (!wait_bwd(x)) return false;

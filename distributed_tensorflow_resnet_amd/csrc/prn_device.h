@@ -260,7 +260,10 @@ __device__ __forceinline__ void prn_fail(unsigned* bar, int* err) {
 }
 
 // Every wave drains its stores / atomics, then lane 0 arrives on its shard.  The caller
-// issues its prefetches (waves 1-7) and waits (grid_wait).
+// issues its prefetches (waves 1-7) and waits (grid_wait).  This is the arrive of the
+// barriers without BN sums in front of them (the forward's pool sums, the backward's last
+// publish) and, at 2 and 4 slices per image, of every BN barrier; at one slice per image
+// the BN sums arrive themselves (bn_sums_arrive) without this second workgroup barrier.
 __device__ __forceinline__ void grid_arrive(unsigned* bar, int shards) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -606,6 +609,20 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += dpp_mov<0x140>(v);   // row_mirror
   return v;
 }
+// row16_sum of N independent values, level by level: each value goes through the same
+// four adds in the same order, but the N chains are written interleaved, so a level's
+// DPP moves issue back to back instead of every value waiting out its own four-deep chain
+template <int N>
+__device__ __forceinline__ void row16_sum_n(float (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov<0xB1>(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov<0x4E>(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov<0x141>(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov<0x140>(v[i]);
+}
 
 // fp64 accumulator replicas per BatchNorm of the persistent kernels (the per-layer
 // kernels use BN_ACC_REP; the engine sizes every BN's block for the larger count).  Each
@@ -618,62 +635,101 @@ constexpr int PRN_ACC_REP = 4;
 
 // Per-channel sums over this slice of two per-value quantities f(t, r, x1, x2), added to
 // a BN's fp64 accumulator replicas acc [PRN_ACC_REP][2][C] (memory-side atomics; exact, so
-// order-independent).  Folding: xor-shuffles over the 16 pixel lanes, then the waves that
-// hold each channel through LDS `red` [8 waves][128] in a fixed order.
+// order-independent); the caller follows it with the workgroup's arrive at the grid
+// barrier, bn_sums_arrive (a probe stamp may stand between the two).
+// The fp32 addition tree is fixed (the step's outputs are bitwise reproducible across
+// builds): per thread over its tiles with equal t % CBW in ascending t; over the 16 pixel
+// lanes in row16_sum's order; over the waves that hold the channel in ascending wave
+// order from 0.f.
+//   * the 2 CBW 4 lane-sum chains run interleaved (row16_sum_n);
+//   * lanes fr == 0 write their 4 consecutive channels of a sum as one 16-byte LDS store
+//     into `red` [8 waves][128]: a wave's row holds sum 1 of channel c at c and sum 2 at
+//     C + c (the four fq lanes of a store cover 64 contiguous bytes: no bank conflict);
+//   * after ONE workgroup barrier, lane i < 2C of wave 0 folds entry i over the waves
+//     (C = 64: lane c folds c and 64 + c, so that wave 0 alone holds every atomic): the
+//     chain's LDS loads are all issued before its adds, then one fp64 atomic per entry.
+// The hand-off to the arrive.  At one slice per image (P = 1) no wave has stored anything
+// since the last arrive that it has not had a whole phase to complete (the forward's
+// saved tensors and the backward's dout / dh1 go out right after the previous arrive), so
+// every wave drains (s_waitcnt vmcnt(0)) BEFORE the one workgroup barrier; after it only
+// wave 0 has global operations in flight -- the atomics -- and it drains itself and its
+// lane 0 adds to the barrier counter: the protocol's order (all of the workgroup's stores
+// and atomics complete, then the counter add) holds without the second workgroup barrier
+// of grid_arrive, and waves 1-7 go on to their prefetches while wave 0 folds.  `red` is
+// safe to reuse: its next writer (the next sums, a split conv's partials, the pool sums)
+// runs after the grid_wait that follows, whose __syncthreads wave 0 joins only after its
+// fold's reads.  At P > 1 every wave's border-row publish is issued right before the
+// sums; draining it in front of the workgroup barrier would expose its round trip, so the
+// sums are followed by grid_arrive (drain, barrier, add).
 template <int S, int P, typename F>
 __device__ __forceinline__ void bn_sums(F f, float* red, double* acc, int wave, int lane) {
   using G = Stg<S, P>;
+  constexpr int C = G::C;
+  constexpr int SPT = 2 * C > 64 ? 2 : 1, NTH = 2 * C / SPT;   // entries per lane, lanes
+  constexpr int NCH = NW / G::WPB;                              // waves per channel
+  constexpr bool SELF = P == 1;                                 // wave 0 arrives by itself
   lane = opaque_v(lane);
   const int fr = lane & 15, fq = lane >> 4;
   if (wave_active<S, P>(wave)) {
-    float s1[G::CBW][4], s2[G::CBW][4];
+    float s[2 * G::CBW * 4];   // [sum][channel block j][r]
 #pragma unroll
-    for (int j = 0; j < G::CBW; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s1[j][r] = s2[j][r] = 0.f;
+    for (int i = 0; i < 2 * G::CBW * 4; ++i) s[i] = 0.f;
 #pragma unroll
     for (int t = 0; t < G::TPW; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float a, b;
         f(t, r, a, b);
-        s1[t % G::CBW][r] += a;
-        s2[t % G::CBW][r] += b;
+        s[(t % G::CBW) * 4 + r] += a;
+        s[(G::CBW + t % G::CBW) * 4 + r] += b;
       }
-#pragma unroll
-    for (int j = 0; j < G::CBW; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s1[j][r] = row16_sum(s1[j][r]);
-        s2[j][r] = row16_sum(s2[j][r]);
-      }
+    row16_sum_n(s);
     if (fr == 0) {
       int pb, cb0;
       tile_of<S, P>(wave, 0, pb, cb0);
 #pragma unroll
-      for (int j = 0; j < G::CBW; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = (cb0 + j) * 16 + 4 * fq + r;
-          red[wave * 128 + c] = s1[j][r];
-          red[wave * 128 + 64 + c] = s2[j][r];
-        }
+      for (int j = 0; j < G::CBW; ++j) {
+        float* q = red + wave * 128 + (cb0 + j) * 16 + 4 * fq;
+        *reinterpret_cast<f32x4*>(q) = f32x4{s[j * 4], s[j * 4 + 1], s[j * 4 + 2], s[j * 4 + 3]};
+        *reinterpret_cast<f32x4*>(q + C) = f32x4{s[(G::CBW + j) * 4], s[(G::CBW + j) * 4 + 1],
+                                                 s[(G::CBW + j) * 4 + 2], s[(G::CBW + j) * 4 + 3]};
+      }
     }
   }
+  if constexpr (SELF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x < G::C) {
-    const int c = threadIdx.x;
-    const int grp = (c / 16) / G::CBW;   // waves w with w % WPB == grp hold channel c
-    float v1 = 0.f, v2 = 0.f;
+  if (threadIdx.x < NTH) {
+    float ld[SPT][NCH];
 #pragma unroll
-    for (int w = 0; w < NW; ++w)
-      if (w % G::WPB == grp) {
-        v1 += red[w * 128 + c];
-        v2 += red[w * 128 + 64 + c];
-      }
-    double* p = acc + (long)(blockIdx.x % PRN_ACC_REP) * 2 * G::C + c;
-    atomic_add_g(p, (double)v1);
-    atomic_add_g(p + G::C, (double)v2);
+    for (int k = 0; k < SPT; ++k) {
+      const int i = threadIdx.x + k * NTH;
+      const int grp = ((i & (C - 1)) / 16) / G::CBW;   // waves w with w % WPB == grp hold the channel
+#pragma unroll
+      for (int q = 0; q < NCH; ++q) ld[k][q] = red[(grp + q * G::WPB) * 128 + i];
+    }
+    double* p = acc + (long)(blockIdx.x % PRN_ACC_REP) * 2 * C + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < SPT; ++k) {
+      float v = 0.f;
+#pragma unroll
+      for (int q = 0; q < NCH; ++q) v += ld[k][q];
+      atomic_add_g(p + k * NTH, (double)v);
+    }
+  }
+}
+
+// the arrive after bn_sums (see there): at P = 1 wave 0 alone, no workgroup barrier
+template <int P>
+__device__ __forceinline__ void bn_sums_arrive(unsigned* bar, int shards, int wave) {
+  if constexpr (P == 1) {
+    if (wave == 0) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (threadIdx.x == 0)
+        __hip_atomic_fetch_add(bar + (blockIdx.x % shards) * PRN_LINE, 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else {
+    grid_arrive(bar, shards);
   }
 }
 

@@ -20,13 +20,18 @@ __device__ __forceinline__ bool wait_fwd(Ctx& x) {
   return grid_wait(x.a->bar, PRN_FWD, x.nbar, x.slices, x.a->shards, x.a->err, x.m.flag);
 }
 
+// the slice's sums of v and v^2 into BatchNorm bi's accumulators, then the arrive at the
+// forward barrier (bn_sums_arrive); probe tag `tag` (0: none) once the atomics are issued
 template <int S, int P>
-__device__ __forceinline__ void fwd_sums(Ctx& x, const bf16x4 (&v)[8], int bi, int wave, int lane) {
+__device__ __forceinline__ void fwd_sums_arrive(Ctx& x, const bf16x4 (&v)[8], int bi, int tag,
+                                                int wave, int lane) {
   bn_sums<S, P>([&](int t, int r, float& s1, float& s2) {
     const float f = (float)v[t][r];
     s1 = f;
     s2 = f * f;
   }, x.m.red, ld_const(x.a->bns + (bi)).acc, wave, lane);
+  if (tag) probe(x, tag);
+  bn_sums_arrive<P>(x.a->bar + PRN_FWD, x.a->shards, wave);
 }
 
 // BN + ReLU of the published raw tensor `src` (stage S, this image) into halo `hal`: own
@@ -83,9 +88,8 @@ __device__ __forceinline__ bool block_fwd(Ctx& x, bf16x4 (&xr)[8], int bi_next,
   // border rows: those are published before the arrive; the rest (read by the backward
   // launch) is stored after it, its drain overlapping the barrier wait.
   if constexpr (P > 1) publish<S, P, 1>(hr, B.h1 + img_o, x.kslice, wave, lane);
-  fwd_sums<S, P>(x, hr, B.bn2, wave, lane);
-  probe(x, 4);
-  grid_arrive(a.bar + PRN_FWD, a.shards);
+  if constexpr (P > 1) probe(x, 20);
+  fwd_sums_arrive<S, P>(x, hr, B.bn2, 4, wave, lane);
   publish<S, P, P == 1 ? 0 : 2, true>(hr, B.h1 + img_o, x.kslice, wave, lane);
   probe(x, 5);
   {
@@ -107,9 +111,8 @@ __device__ __forceinline__ bool block_fwd(Ctx& x, bf16x4 (&xr)[8], int bi_next,
   else round_acc<S, P, true>(xr, acc, xr);
   probe(x, 9);
   if constexpr (P > 1) publish<S, P, 1>(xr, B.out + img_o, x.kslice, wave, lane);
-  fwd_sums<S, P>(x, xr, bi_next, wave, lane);
-  probe(x, 10);
-  grid_arrive(a.bar + PRN_FWD, a.shards);
+  if constexpr (P > 1) probe(x, 21);
+  fwd_sums_arrive<S, P>(x, xr, bi_next, 10, wave, lane);
   publish<S, P, P == 1 ? 0 : 2, true>(xr, B.out + img_o, x.kslice, wave, lane);
   probe(x, 11);
   bf16x8 w1r[nreg_next_fwd<S>()], wpr[1];
@@ -151,8 +154,7 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
     conv_acc<0, P, 8, 3, 1, false>(acc, x.m.ha, x.m.w1, x.kslice, x.wave, x.lane, x.m.red);
     round_acc<0, P, false>(xr, acc, xr);
     if constexpr (P > 1) publish<0, P, 1>(xr, B0.x + (long)x.img * 1024 * 16, x.kslice, x.wave, x.lane);
-    fwd_sums<0, P>(x, xr, B0.bn1, x.wave, x.lane);
-    grid_arrive(a.bar + PRN_FWD, a.shards);
+    fwd_sums_arrive<0, P>(x, xr, B0.bn1, 0, x.wave, x.lane);
     publish<0, P, P == 1 ? 0 : 2, true>(xr, B0.x + (long)x.img * 1024 * 16, x.kslice, x.wave, x.lane);
     const WLoad L1 = wl_fwd(B0.w1f, 16, 16, 3);
     WLoad LP{};

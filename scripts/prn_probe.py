@@ -1,7 +1,10 @@
 """Phase timeline of the persistent CIFAR launches (csrc/prn_fwd.hip, csrc/prn_bwd.hip): image 0's
 lane 0 stamps the wall clock (100 MHz) at every phase boundary; this prints, per
 phase transition, the mean and total time over all blocks of the forward and of the
-backward launch.  python scripts/prn_probe.py [batch] [resnet_size]"""
+backward launch.  The BN statistics fold has its own phase ("stats fold": from the conv's
+end -- at 2 or 4 slices per image from the end of the border-row publish, tags 20 / 21 -- to
+the fold's atomics being issued); "arrive" is the drain, the counter add and the issue of
+what follows it.  python scripts/prn_probe.py [batch] [resnet_size]"""
 import os
 import sys
 from collections import defaultdict
@@ -14,11 +17,11 @@ from distributed_tensorflow_resnet_amd.models.spec import cifar_spec  # noqa: E4
 from distributed_tensorflow_resnet_amd.train.engine import Engine, cifar_lr_schedule  # noqa: E402
 
 NAMES = {
-    "fwd": {0: "start", 99: "prev block: tail", 1: "BN1 table+halo", 2: "BN1 sync", 3: "conv1", 4: "publish+stats", 5: "arrive",
-            6: "wait", 8: "BN2 combine+halo+wstore+sync", 9: "conv2", 10: "publish+stats",
+    "fwd": {0: "start", 99: "prev block: tail", 1: "BN1 table+halo", 2: "BN1 sync", 3: "conv1", 20: "publish (border rows)", 4: "stats fold", 5: "arrive",
+            6: "wait", 8: "BN2 combine+halo+wstore+sync", 9: "conv2", 21: "publish (border rows)", 10: "stats fold",
             11: "arrive", 12: "wait+wstore", 200: "blocks done"},
-    "bwd": {0: "start", 1: "loads+publish+sync", 3: "conv2 dgrad", 99: "prev block: wstore+tail", 4: "publish+bwd sums", 5: "arrive", 6: "wait",
-            8: "BN2 combine+apply+halo+wstore+sync", 9: "conv1 dgrad", 10: "publish+bwd sums",
+    "bwd": {0: "start", 1: "loads+publish+sync", 3: "conv2 dgrad", 99: "prev block: wstore+tail", 20: "publish (border rows)", 4: "stats fold", 5: "arrive", 6: "wait",
+            8: "BN2 combine+apply+halo+wstore+sync", 9: "conv1 dgrad", 21: "publish (border rows)", 10: "stats fold",
             11: "arrive", 12: "wait", 13: "BN1 table (sums read)", 14: "BN1 apply",
             15: "BN1 halo", 200: "blocks done"},
 }

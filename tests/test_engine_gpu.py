@@ -73,6 +73,15 @@ def test_engine_step_matches_autograd_shallow(gpu, spec_fn, N):
                     for s in eng.params.train_slots), reverse=True)
     print("worst per-tensor gradient rel err:", worst[:4], "global", _rel(eng.grad, g_ref))
     assert _rel(eng.grad, g_ref) < 5e-2, worst[:5]
+    # ... and per tensor: within twice what the bf16 roundings move that tensor of the
+    # free-running fp32 oracle (the criterion of test_layerwise_gpu.py, whose oracles are
+    # teacher-forced and so tighter)
+    g_32 = out[False][1]
+    noise = {s.name: _rel(g_32[s.offset:s.offset + s.numel], g_ref[s.offset:s.offset + s.numel])
+             for s in eng.params.train_slots}
+    over = sorted(((e / (2 * noise[n] + 1e-3), e, noise[n], n) for e, n in worst), reverse=True)
+    print("worst err_t / (2 noise_t + 1e-3), err_t, noise_t:", over[:4])
+    assert over[0][0] <= 1.0, over[:5]
     # BN moving statistics updated like TF (decay 0.997, Bessel variance)
     assert _rel(eng.params.stats, store.stats) < 1e-3
 

@@ -98,6 +98,20 @@ def test_persistent_step_matches_autograd(gpu, monkeypatch, size, N, slices):
                      s.name) for s in ep.params.train_slots), reverse=True)
     print("worst per-tensor gradient rel err:", worst[:4], "global", _rel(ep.grad, g_ref))
     assert _rel(ep.grad, g_ref) < 5e-2, worst[:5]
+    # ... and per tensor: within twice what the bf16 roundings move that tensor of the
+    # free-running fp32 oracle (the criterion of test_layerwise_gpu.py, whose oracles are
+    # teacher-forced and so tighter)
+    store32 = ParamStore(spec, device=gpu)
+    store32.master.copy_(ep.params.master)
+    store32.stats.copy_(ep.params.stats)
+    m32 = TorchResNet(spec, store32, emulate_bf16=False)
+    m32.loss(m32(imgs, True), labels, 2e-4)[0].backward()
+    g_32 = store32.master.grad.detach()
+    noise = {s.name: _rel(g_32[s.offset:s.offset + s.numel], g_ref[s.offset:s.offset + s.numel])
+             for s in ep.params.train_slots}
+    over = sorted(((e / (2 * noise[n] + 1e-3), e, noise[n], n) for e, n in worst), reverse=True)
+    print("worst err_t / (2 noise_t + 1e-3), err_t, noise_t:", over[:4])
+    assert over[0][0] <= 1.0, over[:5]
     assert _rel(ep.params.stats, store.stats) < 1e-3
 
 

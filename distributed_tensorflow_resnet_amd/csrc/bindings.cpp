@@ -724,6 +724,34 @@ static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, f
   };
 }
 
+static Launch mk_grad_sqnorm(ptr_t grad, long long n, ptr_t part) {
+  if (grad & 15) throw std::invalid_argument("grad_sqnorm: grad must be 16-byte aligned");
+  if (n < 0) throw std::invalid_argument("grad_sqnorm: n >= 0");
+  return [=](hipStream_t s) { grad_sqnorm(P<const float>(grad), n, P<double>(part), s); };
+}
+
+static Launch mk_clip_scale(ptr_t part, int nchunks, float c, ptr_t out) {
+  if (!(c > 0.f)) throw std::invalid_argument("clip_scale: c must be positive (inf allowed)");
+  if (nchunks < 0) throw std::invalid_argument("clip_scale: nchunks >= 0");
+  return [=](hipStream_t s) { clip_scale(P<const double>(part), nchunks, c, P<float>(out), s); };
+}
+
+static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                      long long warm_steps, float warm_from, float warm_to,
+                                      std::vector<long long> bounds, std::vector<float> vals,
+                                      ptr_t gstep, float momentum, float wd, ptr_t clip,
+                                      int use_momentum, ptr_t segs, int nseg, ptr_t bf,
+                                      ptr_t lr_out) {
+  if (!clip) throw std::invalid_argument("sgd_clip_update_pack: no clip slot");
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+  return [=](hipStream_t s) {
+    sgd_clip_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
+                         P<const long long>(gstep), momentum, wd, P<const float>(clip),
+                         use_momentum, P<const ParamSeg>(segs), nseg, P<bf16>(bf),
+                         P<float>(lr_out), s);
+  };
+}
+
 static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
                             float one_minus_decay, int warm) {
   if ((master | shadow) & 15)
@@ -1360,6 +1388,9 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "lars_norms", mk_lars_norms);
   def_op(m, plan, "lars_trust", mk_lars_trust);
   def_op(m, plan, "lars_update_pack", mk_lars_update_pack);
+  def_op(m, plan, "grad_sqnorm", mk_grad_sqnorm);
+  def_op(m, plan, "clip_scale", mk_clip_scale);
+  def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack);
   def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);
@@ -1460,6 +1491,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("opt_work_bytes", []() { return (int)sizeof(OptWork); });
   m.def("lars_seg_bytes", []() { return (int)sizeof(LarsSeg); });
   m.attr("LARS_CHUNK") = (int)LARS_CHUNK;
+  m.attr("CLIP_CHUNK") = (int)CLIP_CHUNK;
+  m.def("clip_chunks", &clip_chunks, "workgroups (fp64 partials) of grad_sqnorm over n elements");
   m.def("device_count", &hip_device_count);
   m.def("cu_count", &device_cus,
         "CUs this process dispatches to on the current device (the set bits of its CU mask, "

@@ -68,6 +68,20 @@ void lars_update_pack(float* master, const float* grad, float* mom, long n, cons
                       const long long* gstep, float momentum, float wd, float grad_scale,
                       const ParamSeg* segs, int nseg, const float* trust, bf16* bf,
                       float* lr_out, hipStream_t st);
+// Global gradient-norm clipping (clip.hip).  part[b] = sum of squares of grad[b * CLIP_CHUNK,
+// min(n, (b + 1) * CLIP_CHUNK)) in fp64, clip_chunks(n) of them; grad must be 16-byte
+// aligned and nothing at or past n is read.
+constexpr int CLIP_CHUNK = 4096;   // elements summed by one workgroup
+int clip_chunks(long long n);
+void grad_sqnorm(const float* grad, long long n, double* part, hipStream_t st);
+// out[0] = norm = sqrt(sum of the partials, in chunk order), out[1] = scale: 1 if
+// norm <= c, c / norm if norm > c, NaN if the sum is not finite (c > 0, inf allowed).
+void clip_scale(const double* part, int nchunks, float c, float* out, hipStream_t st);
+// sgd_update_pack's update with the gradient scaled by the device value clip[1].
+void sgd_clip_update_pack(float* master, const float* grad, float* mom, long n,
+                          const LrSchedule& s, const long long* gstep, float momentum, float wd,
+                          const float* clip, int use_momentum, const ParamSeg* segs, int nseg,
+                          bf16* bf, float* lr_out, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

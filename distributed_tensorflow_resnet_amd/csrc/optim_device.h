@@ -49,14 +49,17 @@ __device__ __forceinline__ void write_hwio(const ParamSeg& sg, long e, float w, 
 // of a binary search per element.  The OHWI copy (a transpose) is ohwi_pack's.
 // LARS: the rate of an element is lr * trust[its segment] (lars.hip); `sseg` is the
 // calling kernel's LDS copy of the segment table (SEG_LDS_MAX entries).
-template <bool LARS>
+// CLIP: the gradient's scale is read from the device slot clip[1] (clip.hip's clip_scale)
+// in place of the host grad_scale.
+template <bool LARS, bool CLIP = false>
 __device__ __forceinline__ void
 sgd_pack_body(ParamSeg* sseg, float* __restrict__ w, const float* __restrict__ g,
               float* __restrict__ mom, long n, const LrSchedule& sched,
               const long long* __restrict__ gstep, float momentum, float wd, float grad_scale,
               int use_momentum, const ParamSeg* __restrict__ segs, int nseg,
               const float* __restrict__ trust, bf16* __restrict__ bf, float* __restrict__ lr_out,
-              int update) {
+              int update, const float* __restrict__ clip = nullptr) {
+  if constexpr (CLIP) grad_scale = clip[1];
   // the segment table in LDS: one coalesced round trip per block instead of a binary
   // search of dependent global loads per thread (~8 for ResNet-50's 161 tensors)
   const ParamSeg* S = segs;

@@ -22,6 +22,7 @@ from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_state
+from .layout import check_clip_grad_norm
 
 
 class GPUBackend:
@@ -94,6 +95,9 @@ class GPUBackend:
     def lars_summary(self):
         return self.engine.lars_summary()
 
+    def clip_state(self):
+        return self.engine.clip_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -107,7 +111,11 @@ class CPUBackend:
                  global_batch: int | None = None, threads: int = 0,
                  allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
-                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
+                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
+                 clip_grad_norm: float = 0.0):
+        # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
+        self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
+        self._clip_state = None
         # intra-op threads: DTR_CPU_THREADS, default 1 -- on small containers the
         # OpenMP pool's spin-waits oversubscribe the CPU quota (measured here: one
         # 8x32x32x16 conv fwd+bwd 1.2 ms on 1 thread, 612 ms on 8)
@@ -186,7 +194,11 @@ class CPUBackend:
                 self.dist.all_reduce_sum(g)
         lr = self.sched.at(self.step_count)
         with torch.no_grad():
-            gp = g + self.wd * master
+            if self.clip_grad_norm > 0:
+                # after the all-reduce: every rank forms the same norm from the same bits
+                gp = self._clip_scale(g) * g + self.wd * master
+            else:
+                gp = g + self.wd * master
             if self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
@@ -229,6 +241,26 @@ class CPUBackend:
         return {s.name: self.ema[s.offset:s.offset + s.numel].view(s.shape)
                 for s in self.store.train_slots}
 
+    def _clip_scale(self, g):
+        """The scale of the clipped update (csrc/clip.hip): 1 if norm <= c, c / norm if
+        norm > c, NaN if the sum of squares is not finite; the gradient is not rescaled."""
+        ss = (g.double() * g.double()).sum()
+        norm = torch.sqrt(ss)
+        c = torch.tensor(self.clip_grad_norm, dtype=torch.float32).double()
+        if not bool(torch.isfinite(ss)):
+            scale = torch.tensor(float("nan"), dtype=torch.float64)
+        elif bool(norm > c):
+            scale = c / norm
+        else:
+            scale = torch.tensor(1.0, dtype=torch.float64)
+        norm, scale = norm.float(), scale.float()
+        self._clip_state = (float(norm), float(scale))
+        return scale
+
+    def clip_state(self):
+        """(norm, scale) of the last step (None: clipping off, or no step yet)."""
+        return self._clip_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -264,6 +296,8 @@ class CPUBackend:
         m = dict(self._last)
         if top5:
             m["precision_top5"] = self._last_top5
+        if self._clip_state is not None:
+            m["grad_norm"], m["clip_scale"] = self._clip_state
         return m
 
     def synchronize(self):
@@ -310,7 +344,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0,
                  lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
                  lars_skip: str = "vectors", label_smoothing: float = 0.0,
-                 ema_decay: float = 0.0, ema_warmup: bool = True):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, clip_grad_norm: float = 0.0):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -328,7 +362,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      shuffle_seed=shuffle_seed, lars_eeta=lars_eeta,
                      lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                      label_smoothing=label_smoothing, ema_decay=ema_decay,
-                     ema_warmup=ema_warmup)
+                     ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -337,4 +371,4 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       global_batch=global_batch, allreduce_dtype=allreduce_dtype,
                       lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                       label_smoothing=label_smoothing, ema_decay=ema_decay,
-                      ema_warmup=ema_warmup)
+                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm)

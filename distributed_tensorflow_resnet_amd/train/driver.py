@@ -194,7 +194,10 @@ def main(argv=None, kind: str = "cifar") -> int:
         dev = torch.device("cuda", local)
     from .persist import OVERLAP_RESERVE_CUS
     # CIFAR: RCCL's channels capped at the persistent overlap plan's CU reserve (DistContext)
-    ctx = DistContext(device=dev, timeout_s=flags.comm_timeout_secs,
+    # (--device cpu on a host that has a GPU: CPU tensors need gloo, not the nccl default)
+    ctx = DistContext(backend=None if device == "gpu" else
+                      os.environ.get("DTR_DIST_BACKEND") or "gloo",
+                      device=dev, timeout_s=flags.comm_timeout_secs,
                       rccl_max_channels=(OVERLAP_RESERVE_CUS if spec.dataset.startswith("cifar")
                                          else None))
     dp_ctx = None if flags.variable_update == "independent" else ctx
@@ -220,7 +223,8 @@ def main(argv=None, kind: str = "cifar") -> int:
                            resident=resident, shuffle_seed=flags.seed,
                            lars_eeta=flags.lars_eeta, lars_epsilon=flags.lars_epsilon,
                            lars_skip=flags.lars_skip, label_smoothing=flags.label_smoothing,
-                           ema_decay=flags.ema_decay, ema_warmup=flags.ema_warmup)
+                           ema_decay=flags.ema_decay, ema_warmup=flags.ema_warmup,
+                           clip_grad_norm=flags.clip_grad_norm)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

@@ -48,6 +48,7 @@ from ..utils import tune
 from ..utils.streamcheck import check_plan
 from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa: F401
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
+                     OPT_FUSED_CLIP_REASON, CLIP_CHUNK, check_clip_grad_norm,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
@@ -121,7 +122,11 @@ class Engine:
                  allreduce_dtype: str = "fp32", native_comm: bool | None = None, comm=None,
                  resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
-                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
+                 label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
+                 clip_grad_norm: float = 0.0):
+        # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
+        # recorded), inf = the norm is only measured
+        self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
@@ -279,6 +284,9 @@ class Engine:
             self.opt_fused = False
             self.opt_fused_reason = ("optimizer lars: the norms are taken over the complete "
                                      "fp32 gradient, before the update")
+        if self.clip_grad_norm > 0 and self.opt_fused:
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_CLIP_REASON
         # why the persistent step is off ("" = on); never on a GPU shared by several ranks
         # (its grids need every CU to themselves), and the same choice on EVERY rank (the
         # two plans issue different collectives)
@@ -379,6 +387,13 @@ class Engine:
             self.lars_blk = torch.tensor(blk, dtype=torch.int32, device=dev)
             self.lars_part = torch.zeros(2 * len(blk), dtype=torch.float64, device=dev)
             self.lars_out = torch.ones(3, self.nseg, device=dev)
+        self.clip_part = self.clip_out = None
+        if self.clip_grad_norm > 0:
+            # chunk partials and the {norm, scale} slot: fixed pointers
+            assert CLIP_CHUNK == self.nat.CLIP_CHUNK
+            self.clip_chunks = self.nat.clip_chunks(ps.n_train)
+            self.clip_part = torch.zeros(self.clip_chunks, dtype=torch.float64, device=dev)
+            self.clip_out = torch.tensor([0.0, 1.0], device=dev)
         bptr = self.wbf.data_ptr()
         self.convs: dict[str, _Conv] = {}
         conv_specs = {c.name: c for c in spec.all_convs()}
@@ -616,6 +631,15 @@ class Engine:
             return None
         return lars_trust_summary({n: v for (n, v), skip in zip(st.items(), self.lars_skipped)
                                    if not skip})
+
+    def clip_state(self):
+        """(norm, scale) of the last step's clipping: the global norm of the complete
+        gradient and the factor its update applied (synchronises).  None: clipping off."""
+        if self.clip_out is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        norm, scale = self.clip_out.cpu().tolist()
+        return norm, scale
 
     def ema_state(self):
         """{tensor name: view of its shadow in the flat EMA buffer} (None: --ema_decay 0)."""
@@ -867,7 +891,8 @@ class Engine:
         ``reduce``: loss and precision over the whole global batch -- a collective
         that EVERY rank must call at the same point; False: this rank's batch.
         ``top5`` adds `precision_top5` (in-top-k, k = min(5, classes)); without it the
-        keys are the ones callers that store every scalar have always got."""
+        keys are the ones callers that store every scalar have always got.  With clipping
+        on, `grad_norm` and `clip_scale` of the last step are added (clip_state())."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
@@ -886,6 +911,8 @@ class Engine:
              "cost": xent + self.wd * l2, "precision": correct / n, "lr": lr, "l2": l2}
         if top5:
             m["precision_top5"] = top5_sum / n
+        if self.clip_out is not None:
+            m["grad_norm"], m["clip_scale"] = self.clip_out.cpu().tolist()
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -82,8 +82,10 @@ class LoggingTensorHook(Hook):
             ls = _lars_summary(session)
             lars = (f", lars trust min/median/max = {ls['lars_trust_min']:.4g}/"
                     f"{ls['lars_trust_median']:.4g}/{ls['lars_trust_max']:.4g}") if ls else ""
+            clip = (f", grad norm = {m['grad_norm']:.6g} (scale {m['clip_scale']:.6g})"
+                    if "grad_norm" in m else "")   # --clip_grad_norm
             log(f"INFO:tensorflow:step = {m['global_step']}, loss = {m['cost']:.6f}, "
-                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}")
+                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}{clip}")
 
 
 class StepCounterHook(Hook):
@@ -131,6 +133,9 @@ class SummarySaverHook(Hook):
                     "learning_rate": m["lr"], self.tag: m["precision"]}
             if "precision_top5" in m:
                 vals["Precision_top5"] = m["precision_top5"]
+            for k in ("grad_norm", "clip_scale"):   # --clip_grad_norm
+                if k in m:
+                    vals[k] = m[k]
             self.writer.add_scalars(step, vals)
             self.writer.flush()
 

@@ -129,6 +129,27 @@ def lars_trust_summary(state):
     return {"lars_trust_min": t[0], "lars_trust_median": t[len(t) // 2], "lars_trust_max": t[-1]}
 
 
+CLIP_CHUNK = 4096         # csrc/optim.h CLIP_CHUNK: elements per grad_sqnorm workgroup
+OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gradient, "
+                         "before the update")
+
+
+def check_clip_grad_norm(c, optimizer: str) -> float:
+    """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
+    the norm is measured, the scale is exactly 1); not together with lars, whose trust
+    ratio already normalises by the gradient norm."""
+    try:
+        c = float(c)
+    except (TypeError, ValueError):
+        raise ValueError(f"clip_grad_norm must be a number, got {c!r}") from None
+    if not c >= 0.0:   # negative or NaN
+        raise ValueError(f"clip_grad_norm must be 0 (off), positive or inf, got {c!r}")
+    if c > 0 and optimizer == "lars":
+        raise ValueError("clip_grad_norm cannot be combined with optimizer lars: the trust "
+                         "ratio already normalises by the gradient norm")
+    return c
+
+
 def sgd_tiles_work(seg_arr, seg_names, slabs, gptr: int, names=None, nosplit=(64, 64)):
     """The work map of the one-launch optimizer (csrc/optim.hip sgd_tiles_kernel): per
     parameter segment its slab (split-K partials still to be summed, or none: the

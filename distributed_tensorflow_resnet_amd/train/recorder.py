@@ -578,6 +578,23 @@ class StepRecorder:
                 plan.lars_update_pack(master, grad, mom, e.params.n_train, *e.sched.launch_args(),
                                       e.gstep.data_ptr(), e.momentum, e.wd, 1.0,
                                       e.segs.data_ptr(), e.nseg, lo, e.wbf.data_ptr(), sp + 8)
+            elif e.clip_grad_norm > 0:
+                # as for lars: grad is complete here and every other stream is joined, so
+                # every rank forms the same norm from the same bits
+                co = e.clip_out.data_ptr()
+                i0 = plan.grad_sqnorm(grad, e.params.n_train, e.clip_part.data_ptr())
+                plan.clip_scale(e.clip_part.data_ptr(), e.clip_chunks,
+                                float(np.float32(e.clip_grad_norm)), co)
+                plan.sgd_clip_update_pack(master, grad, mom, e.params.n_train,
+                                          *e.sched.launch_args(), e.gstep.data_ptr(), e.momentum,
+                                          e.wd, co, int(e.use_momentum), e.segs.data_ptr(),
+                                          e.nseg, e.wbf.data_ptr(), sp + 8)
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    out.op_buffers[i0] = gb | {"clip"}
+                    out.op_buffers[i0 + 1] = {"clip"}
+                    out.op_buffers[i0 + 2] = (gb | {f"param:{b}" for b in range(len(e.buckets))}
+                                              | {"clip", "lr", "gstep"})
             else:
                 plan.sgd_update_pack(master, grad, mom, e.params.n_train, *e.sched.launch_args(),
                                      e.gstep.data_ptr(), e.momentum, e.wd, 1.0, int(e.use_momentum),

@@ -11,6 +11,7 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --synthetic        synthetic data of the dataset's shape
   --resident_data    CIFAR split resident on the GPU, shuffled on the device
   --ema_decay        device-side EMA of the weights, checkpointed; --eval_ema scores it
+  --clip_grad_norm   clip the gradient by its global norm on the device (inf: only log it)
   --bucket_mb        gradient all-reduce bucket size
   --device           auto | gpu | cpu
   --use_graph        capture the training step in a hipGraph
@@ -67,6 +68,16 @@ def _ema_decay(v) -> float:
     return f
 
 
+def _clip_norm(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not f >= 0.0:   # negative or NaN
+        raise argparse.ArgumentTypeError(f"clip norm must be 0 (off), positive or inf, got {v!r}")
+    return f
+
+
 def _absl_bools(argv, bool_names):
     """Translate absl `--noflag` / bare `--flag` spellings for boolean flags."""
     out = []
@@ -92,7 +103,11 @@ class FlagParser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         argv = sys.argv[1:] if args is None else list(args)
-        return super().parse_args(_absl_bools(argv, self._bools), namespace)
+        ns = super().parse_args(_absl_bools(argv, self._bools), namespace)
+        if getattr(ns, "clip_grad_norm", 0.0) > 0 and getattr(ns, "optimizer", "") == "lars":
+            self.error("--clip_grad_norm cannot be combined with --optimizer lars: the trust "
+                       "ratio already normalises by the gradient norm")
+        return ns
 
     def parse_known_args(self, args=None, namespace=None):
         argv = sys.argv[1:] if args is None else list(args)
@@ -180,6 +195,14 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "device: shadow -= (1 - decay) * (shadow - weight) after every step "
                         "(tf.train.ExponentialMovingAverage; 0.9999 is TF's usual value), saved "
                         "as <name>/ExponentialMovingAverage.  In [0, 1); 0 = off.")
+    p.add_argument("--clip_grad_norm", type=_clip_norm, default=0.0,
+                   help="Clip the gradient by its global norm (tf.clip_by_global_norm): the "
+                        "update uses g * min(1, c / |g|), |g| over all trainables of the "
+                        "all-reduced mean gradient, before weight decay (the decay term is not "
+                        "clipped).  The norm and the scale are logged (grad_norm, clip_scale); a "
+                        "non-finite norm gives a NaN scale.  0 = off, inf = only measure.  Not "
+                        "with --optimizer lars.  On the persistent step it replaces the "
+                        "one-launch optimizer by the generic one.")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

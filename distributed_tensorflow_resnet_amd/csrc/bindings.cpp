@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <functional>
@@ -27,6 +28,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -655,11 +657,55 @@ static LrSchedule make_sched(float init, long long warm_steps, float warm_from, 
   return sc;
 }
 
+// The trailing argument of the optimizer ops' decay overloads (LRSchedule.decay_args()):
+// (kind "piecewise" | "cosine" | "poly", decay_steps D, end, power).  The peak of a decay
+// schedule is warm_to; D > W >= 0, power > 0, every rate finite and >= 0.
+using LrDecayArgs = std::tuple<std::string, long long, float, float>;
+static const LrDecayArgs kPiecewise{"piecewise", 0, 0.f, 0.f};
+
+static LrSchedule make_sched(float init, long long warm_steps, float warm_from, float warm_to,
+                             std::vector<long long> bounds, std::vector<float> vals,
+                             const LrDecayArgs& decay) {
+  LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+  const std::string& kind = std::get<0>(decay);
+  if (kind == "piecewise") return sc;
+  if (kind == "cosine") sc.kind = LR_COSINE;
+  else if (kind == "poly") sc.kind = LR_POLY;
+  else throw std::invalid_argument("lr schedule: decay '" + kind + "' (piecewise, cosine, poly)");
+  sc.decay_steps = std::get<1>(decay);
+  sc.end = std::get<2>(decay);
+  sc.power = std::get<3>(decay);
+  if (warm_steps < 0 || sc.decay_steps <= warm_steps)
+    throw std::invalid_argument("lr schedule: decay_steps > warm_steps >= 0");
+  if (!(sc.power > 0.f) || !std::isfinite(sc.power))
+    throw std::invalid_argument("lr schedule: power must be positive and finite");
+  for (float r : {init, warm_from, warm_to, sc.end})
+    if (!std::isfinite(r) || r < 0.f)
+      throw std::invalid_argument("lr schedule: rates must be finite and >= 0");
+  return sc;
+}
+
 static Launch mk_ohwi_pack(ptr_t master, ptr_t segs, ptr_t tile0, int nseg, long long tiles,
                            ptr_t bf, ptr_t gstep_inc) {
   return [=](hipStream_t s) {
     ohwi_pack(P<const float>(master), P<const ParamSeg>(segs), P<const long long>(tile0), nseg,
               tiles, P<bf16>(bf), P<long long>(gstep_inc), s);
+  };
+}
+
+// The four ops that evaluate the schedule are bound twice: with the piecewise schedule's
+// six arguments alone, and with one trailing LrDecayArgs.
+static Launch mk_sgd_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                       long long warm_steps, float warm_from, float warm_to,
+                                       std::vector<long long> bounds, std::vector<float> vals,
+                                       ptr_t gstep, float momentum, float wd, float grad_scale,
+                                       int use_momentum, ptr_t segs, int nseg, ptr_t bf,
+                                       ptr_t lr_out, int update, LrDecayArgs decay) {
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    sgd_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
+                    P<const long long>(gstep), momentum, wd, grad_scale, use_momentum,
+                    P<const ParamSeg>(segs), nseg, P<bf16>(bf), P<float>(lr_out), update, s);
   };
 }
 
@@ -669,11 +715,24 @@ static Launch mk_sgd_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, fl
                                  ptr_t gstep, float momentum, float wd, float grad_scale,
                                  int use_momentum, ptr_t segs, int nseg, ptr_t bf, ptr_t lr_out,
                                  int update) {
-  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+  return mk_sgd_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
+                                  bounds, vals, gstep, momentum, wd, grad_scale, use_momentum,
+                                  segs, nseg, bf, lr_out, update, kPiecewise);
+}
+
+static Launch mk_sgd_tiles_decay(ptr_t master, ptr_t grad, ptr_t mom, float init,
+                                 long long warm_steps, float warm_from, float warm_to,
+                                 std::vector<long long> bounds, std::vector<float> vals,
+                                 ptr_t gstep, float momentum, float wd, float grad_scale,
+                                 int use_momentum, ptr_t segs, ptr_t work, ptr_t blk_seg,
+                                 int nblocks, ptr_t bf, ptr_t lr_out, ptr_t ticket, ptr_t gin,
+                                 ptr_t gout, int pack, LrDecayArgs decay) {
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
-    sgd_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
-                    P<const long long>(gstep), momentum, wd, grad_scale, use_momentum,
-                    P<const ParamSeg>(segs), nseg, P<bf16>(bf), P<float>(lr_out), update, s);
+    sgd_tiles(P<float>(master), P<float>(grad), P<float>(mom), sc, P<long long>(gstep),
+              momentum, wd, grad_scale, use_momentum, P<const ParamSeg>(segs),
+              P<const OptWork>(work), P<const int>(blk_seg), nblocks, P<bf16>(bf),
+              P<float>(lr_out), P<unsigned>(ticket), P<const bf16>(gin), P<bf16>(gout), pack, s);
   };
 }
 
@@ -683,13 +742,9 @@ static Launch mk_sgd_tiles(ptr_t master, ptr_t grad, ptr_t mom, float init,
                            float momentum, float wd, float grad_scale, int use_momentum,
                            ptr_t segs, ptr_t work, ptr_t blk_seg, int nblocks, ptr_t bf,
                            ptr_t lr_out, ptr_t ticket, ptr_t gin, ptr_t gout, int pack) {
-  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
-  return [=](hipStream_t s) {
-    sgd_tiles(P<float>(master), P<float>(grad), P<float>(mom), sc, P<long long>(gstep),
-              momentum, wd, grad_scale, use_momentum, P<const ParamSeg>(segs),
-              P<const OptWork>(work), P<const int>(blk_seg), nblocks, P<bf16>(bf),
-              P<float>(lr_out), P<unsigned>(ticket), P<const bf16>(gin), P<bf16>(gout), pack, s);
-  };
+  return mk_sgd_tiles_decay(master, grad, mom, init, warm_steps, warm_from, warm_to, bounds, vals,
+                            gstep, momentum, wd, grad_scale, use_momentum, segs, work, blk_seg,
+                            nblocks, bf, lr_out, ticket, gin, gout, pack, kPiecewise);
 }
 
 static Launch mk_lars_norms(ptr_t master, ptr_t grad, ptr_t segs, ptr_t lsegs, ptr_t blk_seg,
@@ -710,18 +765,29 @@ static Launch mk_lars_trust(ptr_t part, ptr_t lsegs, int nseg, float eeta, float
   };
 }
 
-static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                  long long warm_steps, float warm_from, float warm_to,
-                                  std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, float momentum, float wd, float grad_scale,
-                                  ptr_t segs, int nseg, ptr_t trust, ptr_t bf, ptr_t lr_out) {
-  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+static Launch mk_lars_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                        long long warm_steps, float warm_from, float warm_to,
+                                        std::vector<long long> bounds, std::vector<float> vals,
+                                        ptr_t gstep, float momentum, float wd, float grad_scale,
+                                        ptr_t segs, int nseg, ptr_t trust, ptr_t bf,
+                                        ptr_t lr_out, LrDecayArgs decay) {
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     lars_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
                      P<const long long>(gstep), momentum, wd, grad_scale,
                      P<const ParamSeg>(segs), nseg, P<const float>(trust), P<bf16>(bf),
                      P<float>(lr_out), s);
   };
+}
+
+static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float momentum, float wd, float grad_scale,
+                                  ptr_t segs, int nseg, ptr_t trust, ptr_t bf, ptr_t lr_out) {
+  return mk_lars_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
+                                   bounds, vals, gstep, momentum, wd, grad_scale, segs, nseg,
+                                   trust, bf, lr_out, kPiecewise);
 }
 
 static Launch mk_grad_sqnorm(ptr_t grad, long long n, ptr_t part) {
@@ -736,20 +802,31 @@ static Launch mk_clip_scale(ptr_t part, int nchunks, float c, ptr_t out) {
   return [=](hipStream_t s) { clip_scale(P<const double>(part), nchunks, c, P<float>(out), s); };
 }
 
-static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                      long long warm_steps, float warm_from, float warm_to,
-                                      std::vector<long long> bounds, std::vector<float> vals,
-                                      ptr_t gstep, float momentum, float wd, ptr_t clip,
-                                      int use_momentum, ptr_t segs, int nseg, ptr_t bf,
-                                      ptr_t lr_out) {
+static Launch mk_sgd_clip_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n,
+                                            float init, long long warm_steps, float warm_from,
+                                            float warm_to, std::vector<long long> bounds,
+                                            std::vector<float> vals, ptr_t gstep, float momentum,
+                                            float wd, ptr_t clip, int use_momentum, ptr_t segs,
+                                            int nseg, ptr_t bf, ptr_t lr_out, LrDecayArgs decay) {
   if (!clip) throw std::invalid_argument("sgd_clip_update_pack: no clip slot");
-  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals);
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     sgd_clip_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
                          P<const long long>(gstep), momentum, wd, P<const float>(clip),
                          use_momentum, P<const ParamSeg>(segs), nseg, P<bf16>(bf),
                          P<float>(lr_out), s);
   };
+}
+
+static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                      long long warm_steps, float warm_from, float warm_to,
+                                      std::vector<long long> bounds, std::vector<float> vals,
+                                      ptr_t gstep, float momentum, float wd, ptr_t clip,
+                                      int use_momentum, ptr_t segs, int nseg, ptr_t bf,
+                                      ptr_t lr_out) {
+  return mk_sgd_clip_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
+                                       bounds, vals, gstep, momentum, wd, clip, use_momentum,
+                                       segs, nseg, bf, lr_out, kPiecewise);
 }
 
 static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
@@ -1383,14 +1460,18 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "maxpool_fwd", mk_maxpool_fwd);
   def_op(m, plan, "maxpool_bwd", mk_maxpool_bwd);
   def_op(m, plan, "sgd_update_pack", mk_sgd_update_pack);
+  def_op(m, plan, "sgd_update_pack", mk_sgd_update_pack_decay);
   def_op(m, plan, "ohwi_pack", mk_ohwi_pack);
   def_op(m, plan, "sgd_tiles", mk_sgd_tiles);
+  def_op(m, plan, "sgd_tiles", mk_sgd_tiles_decay);
   def_op(m, plan, "lars_norms", mk_lars_norms);
   def_op(m, plan, "lars_trust", mk_lars_trust);
   def_op(m, plan, "lars_update_pack", mk_lars_update_pack);
+  def_op(m, plan, "lars_update_pack", mk_lars_update_pack_decay);
   def_op(m, plan, "grad_sqnorm", mk_grad_sqnorm);
   def_op(m, plan, "clip_scale", mk_clip_scale);
   def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack);
+  def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack_decay);
   def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);

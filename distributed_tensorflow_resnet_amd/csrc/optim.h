@@ -4,14 +4,22 @@
 
 namespace dtr {
 
-// Piecewise learning-rate schedule evaluated on the device from global_step.
+// Learning-rate schedule evaluated on the device from global_step: an optional linear
+// warm-up, then piecewise-constant steps or a cosine / polynomial decay to `end`.
+enum LrDecay : int { LR_PIECEWISE = 0, LR_COSINE = 1, LR_POLY = 2 };
 struct LrSchedule {
   float init;            // rate used at step 0 (the hook's begin())
-  long long warm_steps;  // linear warm-up length (0 = none)
-  float warm_from, warm_to;
+  long long warm_steps;  // linear warm-up length W (0 = none)
+  float warm_from, warm_to;   // warm_to: the peak rate of a decay schedule
   int nb;                // number of boundaries (<= 7)
   long long bound[7];
   float val[8];
+  // cosine / poly (optim_device.h lr_decay_at): with t = step - 1 in [W, D),
+  // q = (D - t) / (D - W), lr = end + (warm_to - end) * F(q), F = sinpi(q / 2)^2 or
+  // q^power; exactly `end` from t = D on
+  int kind;              // LrDecay
+  long long decay_steps; // D > W
+  float end, power;
 };
 
 void sgd_update_pack(float* master, const float* grad, float* mom, long n, const LrSchedule& s,

@@ -10,7 +10,8 @@
 // forward, HWIO for dgrad).  The learning rate is evaluated on the device from
 // the device-resident global_step with the reference's piecewise schedule
 // (resnet_cifar_main.py:304-324, resnet_imagenet_main.py:306-329 incl. the
-// step-0 quirk), so the whole training step can be captured in a hipGraph.
+// step-0 quirk) or a cosine / polynomial decay (optim_device.h lr_decay_at), so the whole
+// training step can be captured in a hipGraph.
 #include "optim_device.h"
 
 namespace dtr {

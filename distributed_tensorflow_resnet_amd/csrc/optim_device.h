@@ -7,7 +7,43 @@
 
 namespace dtr {
 
-__device__ __forceinline__ float lr_at(const LrSchedule& s, long step) {
+// Cosine / polynomial decay (optim.h LrSchedule; the step-0 quirk and the fp32 warm-up are
+// lr_at's).  fp64 from the two 64-bit differences on, rounded to fp32 once: the chain's
+// relative error is a few 2^-53 (sinpi and the products; the general power as
+// exp(power * log q) adds power * |log q| * 2^-53, |log q| < 44 for any 64-bit D), far
+// inside an fp32 half-ulp, so the result is the correctly rounded rate except on a
+// rounding boundary.  sinpi(q / 2)^2 is 0.5 (1 + cos(pi p)) at p = 1 - q without the
+// cancellation at the end of the run; its argument is in (0, 1/2], so no large-argument
+// reduction is pulled in.  One lane per workgroup evaluates it, ahead of the update loops'
+// loads: inlined it leaves the four optimizer kernels' VGPR counts where they were and
+// costs fewer SGPR spills in sgd_tiles than a call does (profiles/lr_schedules.md).
+__device__ __forceinline__ float lr_decay_curve(int kind, long long t, long long warm_steps,
+                                                long long decay_steps, float peak, float end,
+                                                float power) {
+  const double q = (double)(decay_steps - t) / (double)(decay_steps - warm_steps);
+  double f;
+  if (kind == LR_COSINE) {
+    const double sn = sinpi(0.5 * q);
+    f = sn * sn;
+  } else if (power == 1.f) {
+    f = q;
+  } else if (power == 2.f) {
+    f = q * q;
+  } else {
+    f = exp((double)power * log(q));   // q in (0, 1]
+  }
+  return (float)((double)end + ((double)peak - (double)end) * f);
+}
+
+__device__ __forceinline__ float lr_decay_at(const LrSchedule& s, long step) {
+  if (step <= 0) return s.init;
+  const long t = step - 1;
+  if (t < s.warm_steps) return s.warm_from + (s.warm_to - s.warm_from) * (float)t / (float)s.warm_steps;
+  if (t >= s.decay_steps) return s.end;
+  return lr_decay_curve(s.kind, t, s.warm_steps, s.decay_steps, s.warm_to, s.end, s.power);
+}
+
+__device__ __forceinline__ float lr_piecewise_at(const LrSchedule& s, long step) {
   // The reference's hook feeds the rate computed after the *previous* run:
   // step 0 uses the initial value from begin(); step t>0 uses f(t-1).
   if (step <= 0) return s.init;
@@ -16,6 +52,11 @@ __device__ __forceinline__ float lr_at(const LrSchedule& s, long step) {
   for (int i = 0; i < s.nb; ++i)
     if (t < s.bound[i]) return s.val[i];
   return s.val[s.nb];
+}
+
+// The rate of `step`: the branch on the kind is uniform over the launch.
+__device__ __forceinline__ float lr_at(const LrSchedule& s, long step) {
+  return s.kind != LR_PIECEWISE ? lr_decay_at(s, step) : lr_piecewise_at(s, step);
 }
 
 constexpr int SEG_LDS_MAX = 640;   // segment tables cached in LDS up to this size (30 KB)
@@ -62,13 +103,19 @@ sgd_pack_body(ParamSeg* sseg, float* __restrict__ w, const float* __restrict__ g
   if constexpr (CLIP) grad_scale = clip[1];
   // the segment table in LDS: one coalesced round trip per block instead of a binary
   // search of dependent global loads per thread (~8 for ResNet-50's 161 tensors)
+  // a decay schedule's rate (fp64) is evaluated by one lane and rides the table's barrier
+  __shared__ float lr_s;
+  const bool decay = update && sched.kind != LR_PIECEWISE;   // uniform over the launch
+  if (decay && threadIdx.x == 0) lr_s = lr_decay_at(sched, gstep ? (long)*gstep : 0L);
   const ParamSeg* S = segs;
   if (nseg <= SEG_LDS_MAX) {
     for (int i = threadIdx.x; i < nseg; i += blockDim.x) sseg[i] = segs[i];
     __syncthreads();
     S = sseg;
+  } else if (decay) {
+    __syncthreads();   // (no table to publish: the barrier is the rate's alone)
   }
-  const float lr = update ? lr_at(sched, gstep ? (long)*gstep : 0L) : 0.f;
+  const float lr = !update ? 0.f : decay ? lr_s : lr_piecewise_at(sched, gstep ? (long)*gstep : 0L);
   if (update && lr_out && blockIdx.x == 0 && threadIdx.x == 0) *lr_out = lr;
   const long nv = (n + 3) / 4;
   const long stride = (long)gridDim.x * blockDim.x;

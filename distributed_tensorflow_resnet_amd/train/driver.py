@@ -27,9 +27,9 @@ from ..utils.flags import build_parser, warn_unsupported
 from ..utils.records import EventWriter
 from . import hooks as H
 from .backends import make_backend
-from .engine import (PersistentStepError, cifar_lr_schedule, imagenet_lr_schedule,
-                     lr_values_scaled, scaled)
+from .engine import PersistentStepError, lr_values_scaled, scaled
 from .evaluator import SidecarEvaluator, make_inference
+from .schedule import schedule_from_flags
 from .session import TrainingSession, run_training
 
 
@@ -202,8 +202,8 @@ def main(argv=None, kind: str = "cifar") -> int:
                                          else None))
     dp_ctx = None if flags.variable_update == "independent" else ctx
     rank, world = ctx.rank, ctx.world_size
-    sched = cifar_lr_schedule() if spec.dataset.startswith("cifar") else imagenet_lr_schedule()
-    sched = lr_values_scaled(scaled(sched, flags.lr_schedule_scale), flags.lr_value_scale)
+    sched = lr_values_scaled(scaled(schedule_from_flags(flags), flags.lr_schedule_scale),
+                             flags.lr_value_scale)
     # real ImageNet on the GPU: uint8 crops from the workers, flip/mean/bf16 pack on device
     u8 = device == "gpu" and spec.dataset == "imagenet" and not flags.synthetic
     # --resident_data: the whole CIFAR split on the device, shuffled there by (--seed,

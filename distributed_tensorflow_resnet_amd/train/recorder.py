@@ -531,7 +531,8 @@ class StepRecorder:
         self.plan.sgd_tiles(e.params.master.data_ptr(), e.grad.data_ptr(), e.mom.data_ptr(),
                             *e.sched.launch_args(), e.gstep.data_ptr(), e.momentum, e.wd, 1.0,
                             int(e.use_momentum), e.segs.data_ptr(), wt.data_ptr(), bt.data_ptr(),
-                            nblk, e.wbf.data_ptr(), lr_slot, ticket, gin, gout, pack)
+                            nblk, e.wbf.data_ptr(), lr_slot, ticket, gin, gout, pack,
+                            *e.sched.extra_launch_args())
 
     def _emit_pack(self, names, stream: int = 0):
         """The all-reduce input of `names`' gradients in ONE launch (sgd_tiles pack mode,
@@ -577,7 +578,8 @@ class StepRecorder:
                                 lo + 8 * e.nseg)
                 plan.lars_update_pack(master, grad, mom, e.params.n_train, *e.sched.launch_args(),
                                       e.gstep.data_ptr(), e.momentum, e.wd, 1.0,
-                                      e.segs.data_ptr(), e.nseg, lo, e.wbf.data_ptr(), sp + 8)
+                                      e.segs.data_ptr(), e.nseg, lo, e.wbf.data_ptr(), sp + 8,
+                                      *e.sched.extra_launch_args())
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits
@@ -588,7 +590,8 @@ class StepRecorder:
                 plan.sgd_clip_update_pack(master, grad, mom, e.params.n_train,
                                           *e.sched.launch_args(), e.gstep.data_ptr(), e.momentum,
                                           e.wd, co, int(e.use_momentum), e.segs.data_ptr(),
-                                          e.nseg, e.wbf.data_ptr(), sp + 8)
+                                          e.nseg, e.wbf.data_ptr(), sp + 8,
+                                          *e.sched.extra_launch_args())
                 if out.op_buffers:   # the overlap plan declares what its ops touch
                     gb = {f"grad:{b}" for b in range(len(e.buckets))}
                     out.op_buffers[i0] = gb | {"clip"}
@@ -598,7 +601,8 @@ class StepRecorder:
             else:
                 plan.sgd_update_pack(master, grad, mom, e.params.n_train, *e.sched.launch_args(),
                                      e.gstep.data_ptr(), e.momentum, e.wd, 1.0, int(e.use_momentum),
-                                     e.segs.data_ptr(), e.nseg, e.wbf.data_ptr(), sp + 8, 1)
+                                     e.segs.data_ptr(), e.nseg, e.wbf.data_ptr(), sp + 8, 1,
+                                     *e.sched.extra_launch_args())
             plan.ohwi_pack(master, e.segs.data_ptr(), e.ohwi_tile0.data_ptr(), e.nseg,
                            e.ohwi_tiles, e.wbf.data_ptr(), e.gstep.data_ptr())   # + global_step += 1
         if e.stem_s2d:

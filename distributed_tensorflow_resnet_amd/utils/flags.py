@@ -12,6 +12,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --resident_data    CIFAR split resident on the GPU, shuffled on the device
   --ema_decay        device-side EMA of the weights, checkpointed; --eval_ema scores it
   --clip_grad_norm   clip the gradient by its global norm on the device (inf: only log it)
+  --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
+                     --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
   --device           auto | gpu | cpu
   --use_graph        capture the training step in a hipGraph
@@ -78,6 +80,16 @@ def _clip_norm(v) -> float:
     return f
 
 
+def _lr_rate(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < float("inf"):   # negative, inf or NaN
+        raise argparse.ArgumentTypeError(f"a learning rate must be finite and >= 0, got {v!r}")
+    return f
+
+
 def _absl_bools(argv, bool_names):
     """Translate absl `--noflag` / bare `--flag` spellings for boolean flags."""
     out = []
@@ -107,6 +119,13 @@ class FlagParser(argparse.ArgumentParser):
         if getattr(ns, "clip_grad_norm", 0.0) > 0 and getattr(ns, "optimizer", "") == "lars":
             self.error("--clip_grad_norm cannot be combined with --optimizer lars: the trust "
                        "ratio already normalises by the gradient norm")
+        if hasattr(ns, "lr_decay"):
+            from ..train.schedule import schedule_from_flags
+
+            try:   # the run's schedule must exist: decay_steps > warm-up, power > 0, ...
+                schedule_from_flags(ns)
+            except ValueError as e:
+                self.error(str(e))
         return ns
 
     def parse_known_args(self, args=None, namespace=None):
@@ -247,6 +266,30 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="Multiply every LR value of the schedule (and its warm-up) by this "
                         "factor: the linear scaling rule when the global batch differs from "
                         "the reference's (ImageNet: 0.4 for 8 x 128 images).")
+    p.add_argument("--lr_decay", default="piecewise", choices=("piecewise", "cosine", "poly"),
+                   help="Shape of the LR schedule after its warm-up: the reference's piecewise "
+                        "steps, or a decay from --lr_peak to --lr_end over --lr_decay_steps, "
+                        "evaluated on the device like the steps: cosine, end + (peak - end) * "
+                        "0.5 (1 + cos(pi p)), or poly, end + (peak - end) * (1 - p)^power, with "
+                        "p = (t - warmup) / (decay_steps - warmup) and t = step - 1 (the "
+                        "reference's hook feeds step s the rate of s - 1).  LARS recipes use "
+                        "warm-up + poly (power 2).")
+    p.add_argument("--lr_peak", type=_lr_rate, default=None,
+                   help="Rate after the warm-up (piecewise: its first value, the drops keep "
+                        "their ratios).  Default: the dataset's (CIFAR 0.1, ImageNet 0.4), "
+                        "before --lr_value_scale.")
+    p.add_argument("--lr_warmup_steps", type=int, default=-1,
+                   help="Linear warm-up length; -1 = the dataset's (CIFAR 0, ImageNet 6240).  "
+                        "A value >= 0 also applies to --lr_decay piecewise.")
+    p.add_argument("--lr_warmup_from", type=_lr_rate, default=None,
+                   help="Rate the warm-up starts from.  Default: the dataset's (ImageNet 0.1), "
+                        "0 where it has none.")
+    p.add_argument("--lr_decay_steps", type=int, default=0,
+                   help="cosine / poly: the step at which the rate reaches --lr_end and stays "
+                        "there; 0 = --train_steps.  Must exceed the warm-up.")
+    p.add_argument("--lr_end", type=_lr_rate, default=0.0, help="cosine / poly: the final rate.")
+    p.add_argument("--lr_poly_power", type=float, default=2.0,
+                   help="poly: the exponent (> 0).")
     p.add_argument("--allreduce_dtype", default="fp32", choices=("fp32", "bf16"),
                    help="Gradient all-reduce precision: bf16 halves the bytes on xGMI (fp32 "
                         "master weights and optimizer are unchanged).")

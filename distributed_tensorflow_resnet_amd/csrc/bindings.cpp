@@ -424,16 +424,33 @@ static void check_xent_opts(const char* op, float label_smoothing, int topk, ptr
                                 "(> 0 with topk_out)");
 }
 
+// Mixup (xent_row.h): two more trailing arguments, labels_b ([N] partner labels) and mix_lam
+// ([N] fp32 lam per row), both or neither; a third arity of the same ops.
+static void check_mix_ptrs(const char* op, ptr_t labels_b, ptr_t mix_lam) {
+  if ((labels_b == 0) != (mix_lam == 0))
+    throw std::invalid_argument(std::string(op) + ": labels_b and mix_lam go together");
+}
+
+static Launch mk_softmax_xent_mix(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam) {
+  check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
+  check_mix_ptrs("softmax_xent", labels_b, mix_lam);
+  return [=](hipStream_t s) {
+    softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
+                 P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
+                 P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s,
+                 P<const int>(labels_b), P<const float>(mix_lam));
+  };
+}
+
 static Launch mk_softmax_xent_ls(ptr_t logits, int ld, ptr_t labels, int N, int classes,
                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
                                  int topk, ptr_t topk_out) {
-  check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
-  return [=](hipStream_t s) {
-    softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
-                 P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
-                 P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s);
-  };
+  return mk_softmax_xent_mix(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
+                             grad_scale, probs, ws, label_smoothing, topk, topk_out, 0, 0);
 }
 
 static Launch mk_softmax_xent(ptr_t logits, int ld, ptr_t labels, int N, int classes,
@@ -458,12 +475,13 @@ static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t
 
 // head_fused(x, bn=[acc, gamma, beta, mmean, mvar, mean, rstd, scale, shift], momentum, eps,
 //            update_moving, w_hwio, bias, labels, shape=[N, HW, C, classes, kpad], grad_scale,
-//            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk])
-static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                               float label_smoothing, int topk) {
+//            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk[, labels_b, mix_lam]])
+static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam) {
   check_xent_opts("head_fused", label_smoothing, topk, 0);
+  check_mix_ptrs("head_fused", labels_b, mix_lam);
   if (bn.size() != 9 || shape.size() != 5 || out.size() != 5)
     throw std::invalid_argument("head_fused: bn needs 9 pointers, shape 5 ints, out 5 pointers");
   HeadArgs a{};
@@ -496,9 +514,20 @@ static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, f
   a.bacc = P<double>(out[4]);
   a.label_smoothing = label_smoothing;
   a.topk = topk;
+  a.labels_b = P<const int>(labels_b);
+  a.mix_lam = P<const float>(mix_lam);
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
   return [a](hipStream_t s) { head_fused(a, s); };
+}
+
+static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                               float label_smoothing, int topk) {
+  return mk_head_fused_mix(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
+                           std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
+                           0, 0);
 }
 
 static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
@@ -513,7 +542,8 @@ static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, floa
 // (pointers as integers; bucket_of_stage a 3-sequence) plus wgrad_wgs, the backward's
 // weight-gradient workgroups; probe and shards are set by the launch functions.  A
 // missing key and a key that is no PrnArgs member both raise, naming the key -- except
-// label_smoothing, topk and topk_out, which may be left out (0, 0, null).
+// label_smoothing, topk and topk_out, which may be left out (0, 0, null), and the mixup
+// pair labels_b and mix_lam (null; both or neither).
 static Launch mk_prn(int mode, py::dict args) {
   std::vector<std::string> known;
   auto get = [&](const char* key) -> py::object {
@@ -563,7 +593,10 @@ static Launch mk_prn(int mode, py::dict args) {
   if (args.contains("label_smoothing")) PRN_VAL(label_smoothing);
   if (args.contains("topk")) PRN_VAL(topk);
   if (args.contains("topk_out")) PRN_PTR(topk_out);
+  if (args.contains("labels_b")) PRN_PTR(labels_b);
+  if (args.contains("mix_lam")) PRN_PTR(mix_lam);
   check_xent_opts("prn", a.label_smoothing, a.topk, (ptr_t)(uintptr_t)a.topk_out);
+  check_mix_ptrs("prn", (ptr_t)(uintptr_t)a.labels_b, (ptr_t)(uintptr_t)a.mix_lam);
 #undef PRN_PTR
 #undef PRN_VAL
   for (auto kv : args) {   // (every key read above exists, so any other is unknown)
@@ -865,14 +898,69 @@ static Launch mk_memset(ptr_t p, long bytes) {
   };
 }
 
-static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
-                               unsigned long long seed, ptr_t gstep, int train, ptr_t crop_log,
-                               ptr_t zero, long zero_bytes) {
+// The input ops take optional trailing mixup arguments (data.h Mixup): the lam table and
+// its length, the batch's labels (host-fed ops only), labels_b, mix_lam and mix_log.  Each
+// op is registered at both arities; without them, or with a null table, the launch is the
+// unmixed one.  Checked here, when the op is made, so a plan never records a bad launch.
+static Mixup mk_mixup(const char* op, bool host_fed, int train, ptr_t table, int table_len,
+                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log) {
+  Mixup mx;
+  if (!table) return mx;
+  if (!train) throw std::invalid_argument(std::string(op) + ": mixup is a training augmentation");
+  if (table_len < 1 || !labels_b || !mix_lam || (host_fed && !labels))
+    throw std::invalid_argument(std::string(op) + ": mixup needs a table of >= 1 entries, " +
+                                (host_fed ? "labels, " : "") + "labels_b and mix_lam");
+  mx.table = P<const float>(table);
+  mx.table_len = table_len;
+  mx.labels = P<const int>(labels);
+  mx.labels_b = P<int>(labels_b);
+  mx.mix_lam = P<float>(mix_lam);
+  mx.mix_log = P<int>(mix_log);
+  return mx;
+}
+
+static Launch mk_cifar_augment_mix(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
+                                   unsigned long long seed, ptr_t gstep, int train,
+                                   ptr_t crop_log, ptr_t zero, long zero_bytes, ptr_t table,
+                                   int table_len, ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
+                                   ptr_t mix_log) {
   if (zero_bytes % 16) throw std::invalid_argument("cifar_augment: zero_bytes % 16 != 0");
+  const Mixup mx = mk_mixup("cifar_augment", true, train, table, table_len, labels, labels_b,
+                            mix_lam, mix_log);
+  if (mx.table && !(H == 32 && W == 32 && Cpad == 8))
+    throw std::invalid_argument("cifar_augment: mixup only for 32x32 images with Cpad 8");
   return [=](hipStream_t s) {
     cifar_augment(P<const uint8_t>(img), P<bf16>(out), N, H, W, Cpad, pad, seed,
                   P<const long long>(gstep), train, P<int>(crop_log), P<void>(zero), zero_bytes,
-                  s);
+                  s, mx);
+  };
+}
+
+static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
+                               unsigned long long seed, ptr_t gstep, int train, ptr_t crop_log,
+                               ptr_t zero, long zero_bytes) {
+  return mk_cifar_augment_mix(img, out, N, H, W, Cpad, pad, seed, gstep, train, crop_log, zero,
+                              zero_bytes, 0, 0, 0, 0, 0, 0);
+}
+
+static Launch mk_cifar_augment_resident_mix(ptr_t records_u8, ptr_t labels_all, ptr_t out,
+                                            ptr_t labels_out, ptr_t pos, int N, int H, int W,
+                                            int Cpad, long records, int rank, int world,
+                                            int shuffle, unsigned long long key_seed, int pad,
+                                            unsigned long long seed, int train, ptr_t crop_log,
+                                            ptr_t idx_log, ptr_t zero, long zero_bytes,
+                                            ptr_t table, int table_len, ptr_t labels_b,
+                                            ptr_t mix_lam, ptr_t mix_log) {
+  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
+  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
+    throw std::invalid_argument("cifar_augment_resident: null buffer");
+  const Mixup mx = mk_mixup("cifar_augment_resident", false, train, table, table_len, 0, labels_b,
+                            mix_lam, mix_log);
+  return [=](hipStream_t s) {
+    cifar_augment_resident(P<const uint8_t>(records_u8), P<const int>(labels_all), P<bf16>(out),
+                           P<int>(labels_out), P<const long long>(pos), N, H, W, Cpad, records,
+                           rank, world, shuffle, key_seed, pad, seed, train, P<int>(crop_log),
+                           P<int>(idx_log), P<void>(zero), zero_bytes, s, mx);
   };
 }
 
@@ -882,26 +970,31 @@ static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_
                                         unsigned long long key_seed, int pad,
                                         unsigned long long seed, int train, ptr_t crop_log,
                                         ptr_t idx_log, ptr_t zero, long zero_bytes) {
-  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
-  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
-    throw std::invalid_argument("cifar_augment_resident: null buffer");
+  return mk_cifar_augment_resident_mix(records_u8, labels_all, out, labels_out, pos, N, H, W, Cpad,
+                                       records, rank, world, shuffle, key_seed, pad, seed, train,
+                                       crop_log, idx_log, zero, zero_bytes, 0, 0, 0, 0, 0);
+}
+
+static Launch mk_imagenet_u8_pack_mix(ptr_t img, ptr_t out, int N, int H, int W,
+                                      unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
+                                      long zero_bytes, int s2d, ptr_t table, int table_len,
+                                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
+                                      ptr_t mix_log) {
+  if (zero_bytes % 16) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16 != 0");
+  if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
+  const Mixup mx = mk_mixup("imagenet_u8_pack", true, train, table, table_len, labels, labels_b,
+                            mix_lam, mix_log);
   return [=](hipStream_t s) {
-    cifar_augment_resident(P<const uint8_t>(records_u8), P<const int>(labels_all), P<bf16>(out),
-                           P<int>(labels_out), P<const long long>(pos), N, H, W, Cpad, records,
-                           rank, world, shuffle, key_seed, pad, seed, train, P<int>(crop_log),
-                           P<int>(idx_log), P<void>(zero), zero_bytes, s);
+    imagenet_u8_pack(P<const uint8_t>(img), P<bf16>(out), N, H, W, seed,
+                     P<const long long>(gstep), train, P<void>(zero), zero_bytes, s2d, s, mx);
   };
 }
 
 static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
                                   unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
                                   long zero_bytes, int s2d) {
-  if (zero_bytes % 16) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16 != 0");
-  if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
-  return [=](hipStream_t s) {
-    imagenet_u8_pack(P<const uint8_t>(img), P<bf16>(out), N, H, W, seed,
-                     P<const long long>(gstep), train, P<void>(zero), zero_bytes, s2d, s);
-  };
+  return mk_imagenet_u8_pack_mix(img, out, N, H, W, seed, gstep, train, zero, zero_bytes, s2d, 0,
+                                 0, 0, 0, 0, 0);
 }
 
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
@@ -1434,6 +1527,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "avgpool_bwd", mk_avgpool_bwd);
   def_op(m, plan, "softmax_xent", mk_softmax_xent);
   def_op(m, plan, "softmax_xent", mk_softmax_xent_ls);
+  def_op(m, plan, "softmax_xent", mk_softmax_xent_mix);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce_k);
   def_op(m, plan, "bn_bwd_apply_acc", mk_bn_bwd_apply_acc);
@@ -1441,6 +1535,7 @@ PYBIND11_MODULE(_C, m) {
         "whether bn_bwd_apply_acc (finalize fused into the apply) covers (M, C)");
   def_op(m, plan, "head_fused", mk_head_fused);
   def_op(m, plan, "head_fused", mk_head_fused_ls);
+  def_op(m, plan, "head_fused", mk_head_fused_mix);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
   def_op(m, plan, "prn_infer", mk_prn_infer);
@@ -1479,8 +1574,11 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "memset", mk_memset);
   def_op(m, plan, "delay", mk_delay);
   def_op(m, plan, "cifar_augment", mk_cifar_augment);
+  def_op(m, plan, "cifar_augment", mk_cifar_augment_mix);
   def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident);
+  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident_mix);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack);
+  def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_mix);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

@@ -10,6 +10,7 @@
 // a counter-based hash of (seed, global_step, image) read on the device, so the
 // augmentation is part of the captured hipGraph and replays with fresh crops.
 #include <stdexcept>
+#include <string>
 
 #include "common.h"
 #include "kernels.h"
@@ -24,6 +25,26 @@ __device__ __forceinline__ unsigned long long splitmix(unsigned long long x) {
   return x ^ (x >> 31);
 }
 
+// ---- mixup (Zhang et al. 2018): x = lam * x_n + (1 - lam) * x_m, m = (n + shift) % N ---
+// One draw per step, shared by the rank's batch: data/cifar.py mixup_draw is the
+// specification this must equal for every input (integers only; the salted seed keeps it
+// off the crop hashes).  lam = table[index], a host-made table of Beta(alpha, alpha) draws
+// (mixup_table), so no sampler runs here.  Every operand is uniform over the grid.  The
+// arguments are data.h's Mixup; a null table launches the kernels' unmixed instantiation.
+struct MixDraw {
+  unsigned index, shift;
+};
+
+__device__ __forceinline__ MixDraw mixup_draw(unsigned long long seed, unsigned long long step,
+                                              int batch, int table_len) {
+  const unsigned long long h =
+      splitmix(splitmix(seed ^ 0x4D4958555021ull) ^ splitmix(step * 0x100000001B3ull));
+  MixDraw d;
+  d.index = (unsigned)h % (unsigned)table_len;
+  d.shift = batch >= 2 ? 1u + (unsigned)(h >> 32) % (unsigned)(batch - 1) : 0u;
+  return d;
+}
+
 // One workgroup per image: the 3 KB record is staged in LDS with 16-B loads, every
 // thread keeps its 4 output pixels' 3 channels in registers across the
 // per-image statistics, and writes each pixel as ONE 16-B NHWC row (3 channels +
@@ -33,17 +54,21 @@ __device__ __forceinline__ unsigned long long splitmix(unsigned long long x) {
 // cifar_augment_image is the body shared by cifar_augment_kernel (record n of a
 // batch buffer) and cifar_augment_resident_kernel (a record the workgroup picks
 // from the resident split): `src` is the image's 3072-B record, `step` the value
-// the crop/flip hash is keyed with.
-template <int CPAD>
-__device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ src,
-                                                    bf16* __restrict__ out, int n, int pad,
-                                                    unsigned long long seed,
-                                                    unsigned long long step, int train,
-                                                    int* crop_log, uint8_t* im, float* red) {
+// the crop/flip hash is keyed with.  MIX: the workgroup also stages `src_b`, the record
+// of batch position m, standardises it with position m's own crop/flip hash -- the two
+// fp32 images are exactly what the unmixed body produces for n and m -- and writes
+// bf16(lam * a + (1.f - lam) * b): blended in fp32, rounded once.
+//
+// cifar_crop_stats: the staged record `im` -> this thread's PPT pixels x 3 channels of
+// batch position n's crop, the image's mean and 1 / adjusted std.  `red`: 8 floats of
+// this call's own.  One barrier inside.
+__device__ __forceinline__ void cifar_crop_stats(const uint8_t* im, int n, int pad,
+                                                 unsigned long long seed,
+                                                 unsigned long long step, int train,
+                                                 int* crop_log, float* red, float (&v)[4][3],
+                                                 float& mean, float& inv) {
   constexpr int H = 32, W = 32, HW = H * W, CHW = 3 * HW, PPT = HW / 256;
   const int tid = threadIdx.x;
-  if (tid < CHW / 16)
-    reinterpret_cast<uint4*>(im)[tid] = reinterpret_cast<const uint4*>(src)[tid];
   int oy = pad, ox = pad, flip = 0;
   if (train) {
     const unsigned long long h = splitmix(seed ^ splitmix(step * 0x100000001B3ull + n));
@@ -56,9 +81,7 @@ __device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ 
     crop_log[n * 3 + 1] = ox;
     crop_log[n * 3 + 2] = flip;
   }
-  __syncthreads();
   // pixel (y,x) of the crop = padded-image pixel (y+oy, x'+ox), x' = flip ? W-1-x : x
-  float v[PPT][3];
   float s = 0.f, q = 0.f;
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
@@ -84,19 +107,89 @@ __device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ 
   const float tot = red[0] + red[1] + red[2] + red[3];
   const float totq = red[4] + red[5] + red[6] + red[7];
   const float nel = (float)CHW;
-  const float mean = tot / nel;
+  mean = tot / nel;
   const float var = fmaxf(totq / nel - mean * mean, 0.f);
   const float adj = fmaxf(sqrtf(var), rsqrtf(nel));
-  const float inv = 1.f / adj;
+  inv = 1.f / adj;
+}
+
+// im / im_b: 3072 B each (im_b only with MIX); red: 8 floats (16 with MIX)
+template <int CPAD, bool MIX>
+__device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ src,
+                                                    const uint8_t* __restrict__ src_b,
+                                                    bf16* __restrict__ out, int n, int m,
+                                                    float lam, int pad, unsigned long long seed,
+                                                    unsigned long long step, int train,
+                                                    int* crop_log, uint8_t* im, uint8_t* im_b,
+                                                    float* red) {
+  constexpr int HW = 32 * 32, CHW = 3 * HW, PPT = HW / 256;
+  const int tid = threadIdx.x;
+  if (tid < CHW / 16) {
+    reinterpret_cast<uint4*>(im)[tid] = reinterpret_cast<const uint4*>(src)[tid];
+    if (MIX) reinterpret_cast<uint4*>(im_b)[tid] = reinterpret_cast<const uint4*>(src_b)[tid];
+  }
+  __syncthreads();
+  float v[PPT][3], mean, inv;
+  cifar_crop_stats(im, n, pad, seed, step, train, crop_log, red, v, mean, inv);
+  float vb[PPT][3], mean_b = 0.f, inv_b = 0.f;
+  if (MIX) cifar_crop_stats(im_b, m, pad, seed, step, train, nullptr, red + 8, vb, mean_b, inv_b);
   bf16* o = out + (long)n * HW * CPAD;
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
     const int p = tid + k * 256;
     bf16x8 r = {};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) r[c] = (bf16)((v[k][c] - mean) * inv);
+    for (int c = 0; c < 3; ++c) {
+      const float a = (v[k][c] - mean) * inv;
+      if (MIX) {
+        const float b = (vb[k][c] - mean_b) * inv_b;
+        r[c] = (bf16)(lam * a + (1.f - lam) * b);
+      } else {
+        r[c] = (bf16)a;
+      }
+    }
     *reinterpret_cast<bf16x8*>(o + (long)p * CPAD) = r;
   }
+}
+
+// the step's draw, and batch position n's side outputs (thread 0 of workgroup n)
+__device__ __forceinline__ MixDraw mix_side_outputs(const Mixup& mx, unsigned long long seed,
+                                                    unsigned long long step, int n, int batch,
+                                                    float& lam) {
+  const MixDraw d = mixup_draw(seed, step, batch, mx.table_len);
+  lam = mx.table[d.index];
+  if (threadIdx.x == 0) {
+    mx.mix_lam[n] = lam;
+    if (mx.mix_log && n == 0) {
+      mx.mix_log[0] = (int)d.index;
+      mx.mix_log[1] = (int)d.shift;
+    }
+  }
+  return d;
+}
+
+// workgroup n of the host-fed launch; im: 3072 B (6144 with MIX), red: 8 floats (16)
+template <int CPAD, bool MIX>
+__device__ __forceinline__ void cifar_augment_wg(const uint8_t* __restrict__ img,
+                                                 bf16* __restrict__ out, int pad,
+                                                 unsigned long long seed, const long long* gstep,
+                                                 int train, int* crop_log, uint4* __restrict__ zero,
+                                                 long zero_vec, const Mixup& mx, uint8_t* im,
+                                                 float* red) {
+  constexpr int CHW = 3 * 32 * 32;
+  const int n = blockIdx.x, tid = threadIdx.x;
+  for (long i = blockIdx.x * 256L + tid; i < zero_vec; i += (long)gridDim.x * 256)
+    zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
+  int m = n;
+  float lam = 1.f;
+  if (MIX) {
+    const MixDraw d = mix_side_outputs(mx, seed, step, n, (int)gridDim.x, lam);
+    m = (int)(((unsigned)n + d.shift) % gridDim.x);
+    if (tid == 0) mx.labels_b[n] = mx.labels[m];
+  }
+  cifar_augment_image<CPAD, MIX>(img + (long)n * CHW, img + (long)m * CHW, out, n, m, lam, pad,
+                                 seed, step, train, crop_log, im, im + (MIX ? CHW : 0), red);
 }
 
 template <int CPAD>
@@ -104,15 +197,22 @@ __global__ void __launch_bounds__(256)
 cifar_augment_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int pad,
                      unsigned long long seed, const long long* gstep, int train, int* crop_log,
                      uint4* __restrict__ zero, long zero_vec) {
-  constexpr int CHW = 3 * 32 * 32;
-  __shared__ __attribute__((aligned(16))) uint8_t im[CHW];
+  __shared__ __attribute__((aligned(16))) uint8_t im[3 * 32 * 32];
   __shared__ float red[8];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  for (long i = blockIdx.x * 256L + tid; i < zero_vec; i += (long)gridDim.x * 256)
-    zero[i] = make_uint4(0u, 0u, 0u, 0u);
-  const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
-  cifar_augment_image<CPAD>(img + (long)n * CHW, out, n, pad, seed, step, train, crop_log, im,
-                            red);
+  cifar_augment_wg<CPAD, false>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec,
+                                Mixup{}, im, red);
+}
+
+// the same launch with mixup (a kernel of its own: the unmixed one keeps its code and budget)
+template <int CPAD>
+__global__ void __launch_bounds__(256)
+cifar_mixup_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int pad,
+                   unsigned long long seed, const long long* gstep, int train, int* crop_log,
+                   uint4* __restrict__ zero, long zero_vec, Mixup mx) {
+  __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
+  __shared__ float red[16];
+  cifar_augment_wg<CPAD, true>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec, mx,
+                               im, red);
 }
 
 // ---- device-resident split: the workgroup picks its own record ----------------------
@@ -170,16 +270,15 @@ __device__ __forceinline__ int resident_record(unsigned long long step, int n, i
   return (int)x;
 }
 
-__global__ void __launch_bounds__(256)
-cifar_augment_resident_kernel(const uint8_t* __restrict__ records_u8,
-                              const int* __restrict__ labels_all, bf16* __restrict__ out,
-                              int* __restrict__ labels_out, const long long* pos, int records,
-                              int rank, int world, int shuffle, unsigned long long key_seed,
-                              int pad, unsigned long long seed, int train, int* crop_log,
-                              int* idx_log, uint4* __restrict__ zero, long zero_vec) {
+// workgroup n of the resident launch; im: 3072 B (6144 with MIX), red: 8 floats (16)
+template <bool MIX>
+__device__ __forceinline__ void cifar_resident_wg(
+    const uint8_t* __restrict__ records_u8, const int* __restrict__ labels_all,
+    bf16* __restrict__ out, int* __restrict__ labels_out, const long long* pos, int records,
+    int rank, int world, int shuffle, unsigned long long key_seed, int pad,
+    unsigned long long seed, int train, int* crop_log, int* idx_log, uint4* __restrict__ zero,
+    long zero_vec, const Mixup& mx, uint8_t* im, float* red) {
   constexpr int CHW = 3 * 32 * 32;
-  __shared__ __attribute__((aligned(16))) uint8_t im[CHW];
-  __shared__ float red[8];
   const int n = blockIdx.x, tid = threadIdx.x;
   // the one global read the record address waits for; the same value in every lane
   const unsigned long long raw = pos ? (unsigned long long)*pos : 0ull;
@@ -193,8 +292,45 @@ cifar_augment_resident_kernel(const uint8_t* __restrict__ records_u8,
     labels_out[n] = labels_all[idx];
     if (idx_log) idx_log[n] = idx;
   }
-  cifar_augment_image<8>(records_u8 + (long)idx * CHW, out, n, pad, seed, step, train, crop_log,
-                         im, red);
+  int m = n, idx_b = idx;
+  float lam = 1.f;
+  if (MIX) {   // the partner's record: position m's own pick
+    const MixDraw d = mix_side_outputs(mx, seed, step, n, (int)gridDim.x, lam);
+    m = (int)(((unsigned)n + d.shift) % gridDim.x);
+    idx_b = resident_record(step, m, (int)gridDim.x, records, rank, world, shuffle, key_seed);
+    if (tid == 0) mx.labels_b[n] = labels_all[idx_b];
+  }
+  cifar_augment_image<8, MIX>(records_u8 + (long)idx * CHW, records_u8 + (long)idx_b * CHW, out, n,
+                              m, lam, pad, seed, step, train, crop_log, im, im + (MIX ? CHW : 0),
+                              red);
+}
+
+__global__ void __launch_bounds__(256)
+cifar_augment_resident_kernel(const uint8_t* __restrict__ records_u8,
+                              const int* __restrict__ labels_all, bf16* __restrict__ out,
+                              int* __restrict__ labels_out, const long long* pos, int records,
+                              int rank, int world, int shuffle, unsigned long long key_seed,
+                              int pad, unsigned long long seed, int train, int* crop_log,
+                              int* idx_log, uint4* __restrict__ zero, long zero_vec) {
+  __shared__ __attribute__((aligned(16))) uint8_t im[3 * 32 * 32];
+  __shared__ float red[8];
+  cifar_resident_wg<false>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
+                           shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec,
+                           Mixup{}, im, red);
+}
+
+__global__ void __launch_bounds__(256)
+cifar_mixup_resident_kernel(const uint8_t* __restrict__ records_u8,
+                            const int* __restrict__ labels_all, bf16* __restrict__ out,
+                            int* __restrict__ labels_out, const long long* pos, int records,
+                            int rank, int world, int shuffle, unsigned long long key_seed, int pad,
+                            unsigned long long seed, int train, int* crop_log, int* idx_log,
+                            uint4* __restrict__ zero, long zero_vec, Mixup mx) {
+  __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
+  __shared__ float red[16];
+  cifar_resident_wg<true>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
+                          shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec, mx,
+                          im, red);
 }
 
 // Generic-shape fallback (any H, W, Cpad): one element per thread iteration.
@@ -256,13 +392,29 @@ cifar_augment_generic_kernel(const uint8_t* __restrict__ img, bf16* __restrict__
   }
 }
 
+// the mixup arguments of an input launch (`host_fed`: the partner labels come from `labels`)
+static Mixup mix_args(const char* op, const Mixup& mix, bool host_fed, int train) {
+  if (!mix.table) return Mixup{};
+  if (!train) throw std::invalid_argument(std::string(op) + ": mixup is a training augmentation");
+  if (mix.table_len < 1 || !mix.labels_b || !mix.mix_lam || (host_fed && !mix.labels))
+    throw std::invalid_argument(std::string(op) + ": mixup needs a table of >= 1 entries, " +
+                                (host_fed ? "labels, " : "") + "labels_b and mix_lam");
+  return mix;
+}
+
 void cifar_augment(const uint8_t* img, bf16* out, int N, int H, int W, int Cpad, int pad,
                    unsigned long long seed, const long long* gstep, int train, int* crop_log,
-                   void* zero, long zero_bytes, hipStream_t s) {
+                   void* zero, long zero_bytes, hipStream_t s, const Mixup& mix) {
   if (zero_bytes % 16) throw std::invalid_argument("cifar_augment: zero_bytes % 16 != 0");
   uint4* z = reinterpret_cast<uint4*>(zero);
   const long zv = zero ? zero_bytes / 16 : 0;
-  if (H == 32 && W == 32 && Cpad == 8)
+  const Mixup mx = mix_args("cifar_augment", mix, true, train);
+  if (mx.table && !(H == 32 && W == 32 && Cpad == 8))
+    throw std::invalid_argument("cifar_augment: mixup only for 32x32 images with Cpad 8");
+  if (mx.table)
+    hipLaunchKernelGGL(cifar_mixup_kernel<8>, dim3(N), dim3(256), 0, s, img, out, pad, seed,
+                       gstep, train, crop_log, z, zv, mx);
+  else if (H == 32 && W == 32 && Cpad == 8)
     hipLaunchKernelGGL(cifar_augment_kernel<8>, dim3(N), dim3(256), 0, s, img, out, pad, seed,
                        gstep, train, crop_log, z, zv);
   else
@@ -276,16 +428,23 @@ void cifar_augment_resident(const uint8_t* records_u8, const int* labels_all, bf
                             long records, int rank, int world, int shuffle,
                             unsigned long long key_seed, int pad, unsigned long long seed,
                             int train, int* crop_log, int* idx_log, void* zero, long zero_bytes,
-                            hipStream_t s) {
+                            hipStream_t s, const Mixup& mix) {
   cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
   if (!records_u8 || !labels_all || !out || !labels_out || !pos)
     throw std::invalid_argument("cifar_augment_resident: null buffer");
   if (reinterpret_cast<uintptr_t>(records_u8) % 16)
     throw std::invalid_argument("cifar_augment_resident: records not 16-B aligned");
-  hipLaunchKernelGGL(cifar_augment_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
-                     labels_all, out, labels_out, pos, (int)records, rank, world, shuffle ? 1 : 0,
-                     key_seed, pad, seed, train, crop_log, idx_log, reinterpret_cast<uint4*>(zero),
-                     zero ? zero_bytes / 16 : 0);
+  const Mixup mx = mix_args("cifar_augment_resident", mix, false, train);
+  if (mx.table)
+    hipLaunchKernelGGL(cifar_mixup_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
+                       labels_all, out, labels_out, pos, (int)records, rank, world,
+                       shuffle ? 1 : 0, key_seed, pad, seed, train, crop_log, idx_log,
+                       reinterpret_cast<uint4*>(zero), zero ? zero_bytes / 16 : 0, mx);
+  else
+    hipLaunchKernelGGL(cifar_augment_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
+                       labels_all, out, labels_out, pos, (int)records, rank, world,
+                       shuffle ? 1 : 0, key_seed, pad, seed, train, crop_log, idx_log,
+                       reinterpret_cast<uint4*>(zero), zero ? zero_bytes / 16 : 0);
   DTR_CHECK_LAUNCH();
 }
 
@@ -362,10 +521,15 @@ namespace dtr {
 // bf16 NHWC packing with the channel dim padded to 8 (one 16-B row per pixel,
 // the stem conv's operand layout).  Optionally clears a buffer in the same launch
 // (the step's BatchNorm accumulators).  One thread per output pixel.
+// MIX (mixup, above): the thread also reads its pixel of the partner crop m = (n + shift)
+// % N, from the same batch buffer and with position m's own flip, and writes
+// bf16(lam * a + (1.f - lam) * b) of the two mean-subtracted fp32 values, rounded once.
+template <bool MIX>
 __global__ void __launch_bounds__(256)
 imagenet_u8_pack_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int H, int W,
                         unsigned long long seed, const long long* gstep, int train,
-                        uint4* __restrict__ zero, long zero_vec, long npix, int s2d) {
+                        uint4* __restrict__ zero, long zero_vec, long npix, int s2d, int N,
+                        Mixup mx) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < zero_vec; i += (long)gridDim.x * 256)
     zero[i] = make_uint4(0u, 0u, 0u, 0u);
   const long p = blockIdx.x * 256L + threadIdx.x;
@@ -374,16 +538,34 @@ imagenet_u8_pack_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out,
   const long n = p / HW;
   const int rem = (int)(p - n * HW);
   const int y = rem / W, x = rem - y * W;
+  const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
   int flip = 0;
-  if (train) {
-    const unsigned long long step = gstep ? (unsigned long long)*gstep : 0ull;
+  if (train)
     flip = (int)((splitmix(seed ^ splitmix(step * 0x100000001B3ull + (unsigned long long)n)) >> 32) & 1);
-  }
   const int xs = flip ? W - 1 - x : x;
   const uint8_t* src = img + ((n * H + y) * (long)W + xs) * 3;
-  const bf16 c0 = (bf16)((float)src[0] - 123.68f);
-  const bf16 c1 = (bf16)((float)src[1] - 116.78f);
-  const bf16 c2 = (bf16)((float)src[2] - 103.94f);
+  float f0 = (float)src[0] - 123.68f, f1 = (float)src[1] - 116.78f, f2 = (float)src[2] - 103.94f;
+  if (MIX) {
+    const MixDraw d = mixup_draw(seed, step, N, mx.table_len);
+    const float lam = mx.table[d.index];
+    const long m = (long)(((unsigned)n + d.shift) % (unsigned)N);
+    const int flip_b =
+        (int)((splitmix(seed ^ splitmix(step * 0x100000001B3ull + (unsigned long long)m)) >> 32) & 1);
+    const int xb = flip_b ? W - 1 - x : x;
+    const uint8_t* sb = img + ((m * H + y) * (long)W + xb) * 3;
+    f0 = lam * f0 + (1.f - lam) * ((float)sb[0] - 123.68f);
+    f1 = lam * f1 + (1.f - lam) * ((float)sb[1] - 116.78f);
+    f2 = lam * f2 + (1.f - lam) * ((float)sb[2] - 103.94f);
+    if (rem == 0) {   // the image's first pixel writes its side outputs
+      mx.labels_b[n] = mx.labels[m];
+      mx.mix_lam[n] = lam;
+      if (mx.mix_log && n == 0) {
+        mx.mix_log[0] = (int)d.index;
+        mx.mix_log[1] = (int)d.shift;
+      }
+    }
+  }
+  const bf16 c0 = (bf16)f0, c1 = (bf16)f1, c2 = (bf16)f2;
   if (s2d) {   // space-to-depth stem operand [N][H/2][W/2][16] (stem_s2d_pack below)
     bf16x4 r = {c0, c1, c2, (bf16)0.f};
     const long q = (n * (H >> 1) + (y >> 1)) * (long)(W >> 1) + (x >> 1);
@@ -399,14 +581,20 @@ imagenet_u8_pack_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out,
 
 void imagenet_u8_pack(const uint8_t* img, bf16* out, int N, int H, int W,
                       unsigned long long seed, const long long* gstep, int train, void* zero,
-                      long zero_bytes, int s2d, hipStream_t s) {
+                      long zero_bytes, int s2d, hipStream_t s, const Mixup& mix) {
   if (zero_bytes % 16 != 0) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16");
   if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
+  const Mixup mx = mix_args("imagenet_u8_pack", mix, true, train);
   const long npix = (long)N * H * W;
   const int grid = (int)((npix + 255) / 256);
-  hipLaunchKernelGGL(imagenet_u8_pack_kernel, dim3(grid), dim3(256), 0, s, img, out, H, W, seed,
-                     gstep, train, reinterpret_cast<uint4*>(zero), zero ? zero_bytes / 16 : 0,
-                     npix, s2d);
+  if (mx.table)
+    hipLaunchKernelGGL(imagenet_u8_pack_kernel<true>, dim3(grid), dim3(256), 0, s, img, out, H, W,
+                       seed, gstep, train, reinterpret_cast<uint4*>(zero),
+                       zero ? zero_bytes / 16 : 0, npix, s2d, N, mx);
+  else
+    hipLaunchKernelGGL(imagenet_u8_pack_kernel<false>, dim3(grid), dim3(256), 0, s, img, out, H, W,
+                       seed, gstep, train, reinterpret_cast<uint4*>(zero),
+                       zero ? zero_bytes / 16 : 0, npix, s2d, N, mx);
   DTR_CHECK_LAUNCH();
 }
 

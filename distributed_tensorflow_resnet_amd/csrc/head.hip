@@ -99,7 +99,8 @@ __global__ void __launch_bounds__(1024)
 softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                     int N, int classes, float* loss_sum, float* correct,
                     bf16* __restrict__ dlogits, float* __restrict__ dbias, float grad_scale,
-                    float* __restrict__ probs, float eps, int topk, float* topk_out) {
+                    float* __restrict__ probs, float eps, int topk, float* topk_out,
+                    const int* __restrict__ labels_b, const float* __restrict__ mix_lam) {
   extern __shared__ __attribute__((aligned(16))) float sh[];  // [16 waves][ld] dbias partial + misc
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nw = blockDim.x >> 6;
@@ -113,8 +114,11 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
     const float* z = logits + (long)row * ld;
     const int y = labels[row];
     const float zy = (y >= 0 && y < classes) ? z[y] : 0.f;
+    const int yb = labels_b ? labels_b[row] : -1;   // mixup: the partner's label, the row's lam
+    const float lam = mix_lam ? mix_lam[row] : 1.f;
+    const float zyb = (yb >= 0 && yb < classes) ? z[yb] : 0.f;
     const XentRow r = xent_row<0>([&](int j) { return z[lane + 64 * j]; }, lane, classes, y, zy,
-                                  eps, topk);
+                                  eps, topk, yb, zyb, lam);
     if (lane == 0) {
       lsum += r.loss;
       csum += r.top1;
@@ -125,7 +129,7 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
       if (c < classes) {
         const float p = r.prob(z[c]);
         if (probs) probs[(long)row * ld + c] = p;
-        g = r.grad(p, c == y, grad_scale);
+        g = r.grad(p, c == y, c == yb, grad_scale);
       }
       if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
       db[wave * ld + c] += g;
@@ -167,7 +171,8 @@ __global__ void __launch_bounds__(256)
 softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                          int N, int classes, bf16* __restrict__ dlogits, float grad_scale,
                          float* __restrict__ probs, float* __restrict__ ws, bool want_g,
-                         float eps, int topk) {
+                         float eps, int topk, const int* __restrict__ labels_b,
+                         const float* __restrict__ mix_lam) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;   // wave-uniform
@@ -180,7 +185,11 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
   }
   const int y = labels[row];
   const float zy = (y >= 0 && y < classes) ? z[y] : 0.f;
-  const XentRow r = xent_row<VPL>([&](int j) { return v[j]; }, lane, classes, y, zy, eps, topk);
+  const int yb = labels_b ? labels_b[row] : -1;   // mixup: the partner's label, the row's lam
+  const float lam = mix_lam ? mix_lam[row] : 1.f;
+  const float zyb = (yb >= 0 && yb < classes) ? z[yb] : 0.f;
+  const XentRow r = xent_row<VPL>([&](int j) { return v[j]; }, lane, classes, y, zy, eps, topk,
+                                  yb, zyb, lam);
   float* gw = ws + (long)row * ld;
 #pragma unroll
   for (int k = 0; k < VPL; ++k) {
@@ -190,7 +199,7 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
     if (c < classes) {
       const float p = r.prob(v[k]);
       if (probs) probs[(long)row * ld + c] = p;
-      g = r.grad(p, c == y, grad_scale);
+      g = r.grad(p, c == y, c == yb, grad_scale);
     }
     if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
     if (want_g) gw[c] = g;
@@ -364,10 +373,13 @@ __global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
       z = acc + a.bias[lane];
     }
     const float zy = __shfl(z, (y >= 0 && y < a.classes) ? y : 0, 64);
+    const int yb = a.labels_b ? a.labels_b[n] : -1;   // mixup: partner label, the row's lam
+    const float lam = a.mix_lam ? a.mix_lam[n] : 1.f;
+    const float zyb = __shfl(z, (yb >= 0 && yb < a.classes) ? yb : 0, 64);
     const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
-                                  a.label_smoothing, a.topk);
+                                  a.label_smoothing, a.topk, yb, zyb, lam);
     float g = 0.f;
-    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, a.grad_scale);
+    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, lane == yb, a.grad_scale);
     if (lane < kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)n * kpad + lane] = gb;
@@ -452,21 +464,26 @@ void head_fused(const HeadArgs& a, hipStream_t s) {
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias, float grad_scale,
                   float* probs, float* ws, float label_smoothing, int topk, float* topk_out,
-                  hipStream_t s) {
+                  hipStream_t s, const int* labels_b, const float* mix_lam) {
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
     throw std::invalid_argument("softmax_xent: label_smoothing in [0, 1), topk >= 0 (> 0 with topk_out)");
+  if ((labels_b == nullptr) != (mix_lam == nullptr))
+    throw std::invalid_argument("softmax_xent: labels_b and mix_lam go together");
   if (ws != nullptr && ld <= 1024) {
     const dim3 grid((unsigned)((N + 3) / 4));
     const bool want_g = dbias != nullptr;
     if (ld <= 64)
       hipLaunchKernelGGL(softmax_xent_rows_kernel<1>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
+                         labels_b, mix_lam);
     else if (ld <= 256)
       hipLaunchKernelGGL(softmax_xent_rows_kernel<4>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
+                         labels_b, mix_lam);
     else
       hipLaunchKernelGGL(softmax_xent_rows_kernel<16>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk);
+                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
+                         labels_b, mix_lam);
     DTR_CHECK_LAUNCH();
     softmax_xent_reduce(ws, ld, N, classes, loss_sum, correct, dbias, topk_out, s);
     return;
@@ -475,7 +492,7 @@ void softmax_xent(const float* logits, int ld, const int* labels, int N, int cla
   const size_t lds = ((size_t)nw * ld + 3 * nw) * sizeof(float);
   hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels, N,
                      classes, loss_sum, correct, dlogits, dbias, grad_scale, probs, label_smoothing,
-                     topk, topk_out);
+                     topk, topk_out, labels_b, mix_lam);
   DTR_CHECK_LAUNCH();
 }
 

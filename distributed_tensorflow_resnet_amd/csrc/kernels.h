@@ -312,6 +312,8 @@ struct PrnArgs {
   int bucket_of_stage[3] = {-1, -1, -1};   // stage 0..2 -> bucket (overlap mode)
   int fault_bar = -1;        // tests only (DTR_PRN_FAULT_BAR): forward workgroup 0 abandons the
                              // launch at this barrier, as a lost workgroup would; -1 off
+  const int* labels_b = nullptr;    // mixup: [N] partner labels and [N] lam per row
+  const float* mix_lam = nullptr;   // (both or neither; xent_row.h)
 };
 enum { PRN_THREADS = 512 };
 void prn_set_probe(long long* p);   // diagnostics (scripts/prn_probe.py); nullptr = off
@@ -489,6 +491,8 @@ struct HeadArgs {
   double* bacc;             // final BN backward accumulators (sum g, sum g*xhat)
   float label_smoothing = 0.f;   // target smoothing in [0, 1) (xent_row.h)
   int topk = 0;             // k of the in-top-k flags (0: none written)
+  const int* labels_b = nullptr;    // mixup: [N] partner labels and [N] lam per row
+  const float* mix_lam = nullptr;   // (both or neither; xent_row.h)
 };
 bool head_fused_supported(int N, int HW, int C, int classes, int kpad);
 void head_fused(const HeadArgs& a, hipStream_t s);
@@ -499,7 +503,8 @@ void avgpool_bwd(const bf16* dpooled, bf16* dx, int N, int HW, int C, hipStream_
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias,
                   float grad_scale, float* probs, float* ws, float label_smoothing, int topk,
-                  float* topk_out, hipStream_t s);
+                  float* topk_out, hipStream_t s, const int* labels_b = nullptr,
+                  const float* mix_lam = nullptr);   // mixup: [N] partner labels, [N] lam (xent_row.h)
 long softmax_xent_ws_floats(int N, int ld);
 
 // ---- max pool (ImageNet stem) ----

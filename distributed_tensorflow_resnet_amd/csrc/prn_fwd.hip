@@ -239,10 +239,13 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
       z = acc + a.dense_b[lane];
     }
     const float zy = __shfl(z, (y >= 0 && y < a.classes) ? y : 0, 64);
+    const int yb = a.labels_b ? a.labels_b[x.img] : -1;   // mixup: partner label, the row's lam
+    const float lam = a.mix_lam ? a.mix_lam[x.img] : 1.f;
+    const float zyb = __shfl(z, (yb >= 0 && yb < a.classes) ? yb : 0, 64);
     const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
-                                  a.label_smoothing, a.topk);
+                                  a.label_smoothing, a.topk, yb, zyb, lam);
     float g = 0.f;
-    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, a.grad_scale);
+    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, lane == yb, a.grad_scale);
     if (lane < a.kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)x.img * a.kpad + lane] = gb;

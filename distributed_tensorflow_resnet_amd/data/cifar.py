@@ -247,6 +247,41 @@ def resident_batch(key_seed: int, step: int, batch: int, records: int, rank: int
                      for n in range(batch)], dtype=np.int64)
 
 
+# ---------------------------------------------------------------- mixup
+# Mixup (Zhang et al. 2018) in the input launches (csrc/data.hip): batch position n trains on
+# lam * x_n + (1 - lam) * x_m with the target lam * T(y_n) + (1 - lam) * T(y_m), m = (n +
+# shift) % batch.  One (lam, shift) per step for the rank's whole batch, as in the paper's
+# code.  The two functions below are the specification the kernels must equal: the device
+# only indexes the table and evaluates the integer draw, so no sampler runs there.
+MIXUP_TABLE_LEN = 4096
+_MIXUP_SALT = 0x4D4958555021   # "MIXUP!"
+
+
+def mixup_table(alpha: float, seed: int, length: int = MIXUP_TABLE_LEN) -> np.ndarray:
+    """`length` draws from Beta(alpha, alpha) as fp32: the lam values a run cycles through
+    (computed once on the host and uploaded once).  The values depend on numpy's Beta
+    sampler (Generator(PCG64(seed)).beta)."""
+    if not (alpha > 0 and np.isfinite(alpha)):
+        raise ValueError(f"mixup alpha must be finite and > 0, got {alpha!r}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return rng.beta(alpha, alpha, length).astype(np.float32)
+
+
+def mixup_draw(seed: int, step: int, batch: int, table_len: int) -> tuple[int, int]:
+    """(index, shift) of step `step`: lam = table[index], the partner of batch position n is
+    (n + shift) % batch.  index in [0, table_len); shift in [1, batch - 1] (a rotation
+    without fixed points) for batch >= 2, 0 for batch 1.  Keyed like the crops, with the
+    input kernels' seed and the 64-bit step, but the seed is salted and hashed first, so the
+    draw is not the crop hash splitmix(seed ^ splitmix(step * P + n)) of any image."""
+    if step < 0 or batch < 1 or table_len < 1:
+        raise ValueError("need step >= 0, batch >= 1, table_len >= 1")
+    h = splitmix(splitmix((seed & _M64) ^ _MIXUP_SALT) ^
+                 splitmix((step * 0x100000001B3) & _M64))
+    index = (h & 0xFFFFFFFF) % table_len
+    shift = 1 + (h >> 32) % (batch - 1) if batch >= 2 else 0
+    return index, shift
+
+
 def synthetic_batches(batch_size: int, num_classes: int = 10, seed: int = 0):
     """Endless random uint8 CIFAR-shaped records (for --synthetic)."""
     g = torch.Generator().manual_seed(seed)

@@ -105,9 +105,11 @@ class TorchResNet:
             wd = _W.apply(wd)
         return q(x @ wd + self._p("dense/bias"), False)
 
-    def loss(self, logits, labels, weight_decay: float, label_smoothing: float = 0.0):
+    def loss(self, logits, labels, weight_decay: float, label_smoothing: float = 0.0,
+             labels_b=None, lam=None):
         """cost = xent + wd * sum(l2_loss(v) for v in trainables) (resnet_model.py:78-86);
-        xent with smoothed targets when label_smoothing > 0."""
-        xent = ref.softmax_cross_entropy(logits, labels, label_smoothing)
+        xent with smoothed targets when label_smoothing > 0, and against the mixup target
+        lam * T(labels) + (1 - lam) * T(labels_b) when the two are given."""
+        xent = ref.softmax_cross_entropy(logits, labels, label_smoothing, labels_b, lam)
         l2 = (self.master * self.master).sum() * 0.5
         return xent, xent + weight_decay * l2

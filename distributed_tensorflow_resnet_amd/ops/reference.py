@@ -77,17 +77,28 @@ def max_pool_same(x: torch.Tensor, k: int = 3, stride: int = 2) -> torch.Tensor:
 
 
 def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor,
-                          label_smoothing: float = 0.0) -> torch.Tensor:
+                          label_smoothing: float = 0.0, labels_b: torch.Tensor | None = None,
+                          lam=None) -> torch.Tensor:
     """tf.losses.softmax_cross_entropy(onehot, logits, label_smoothing): mean over the
     batch.  The smoothed target is (1 - eps) * onehot + eps / classes, so a row's loss is
-    lse - (1 - eps) * z[y] - (eps / classes) * sum(z)."""
+    lse - (1 - eps) * z[y] - (eps / classes) * sum(z).
+
+    Mixup (``labels_b`` and ``lam``, a number or a tensor [N]): the target is lam * T(y) +
+    (1 - lam) * T(y_b), so z[y] above becomes lam * z[y] + (1 - lam) * z[y_b]."""
     if not 0.0 <= label_smoothing < 1.0:
         raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
-    if label_smoothing == 0.0:
+    if (labels_b is None) != (lam is None):
+        raise ValueError("labels_b and lam go together")
+    if label_smoothing == 0.0 and labels_b is None:
         return F.cross_entropy(logits, labels.long(), reduction="mean")
     eps, K = float(label_smoothing), logits.shape[1]
     lse = torch.logsumexp(logits, dim=1)
     zy = logits.gather(1, labels.long()[:, None])[:, 0]
+    if labels_b is not None:
+        lam = torch.as_tensor(lam, dtype=logits.dtype, device=logits.device)
+        zy = lam * zy + (1.0 - lam) * logits.gather(1, labels_b.long()[:, None])[:, 0]
+    if eps == 0.0:
+        return (lse - zy).mean()
     return (lse - (1.0 - eps) * zy - (eps / K) * logits.sum(dim=1)).mean()
 
 

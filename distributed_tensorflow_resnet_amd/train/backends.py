@@ -15,14 +15,14 @@ import os
 
 import torch
 
-from ..data.cifar import augment_cpu
+from ..data.cifar import augment_cpu, mixup_draw, mixup_table
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_state
-from .layout import check_clip_grad_norm
+from .layout import check_clip_grad_norm, check_mixup_alpha
 
 
 class GPUBackend:
@@ -98,6 +98,9 @@ class GPUBackend:
     def clip_state(self):
         return self.engine.clip_state()
 
+    def mixup_state(self):
+        return self.engine.mixup_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -112,7 +115,12 @@ class CPUBackend:
                  allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0, data_seed: int = 1234):
+        # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
+        self.mixup_alpha = check_mixup_alpha(mixup_alpha)
+        self.data_seed = data_seed
+        self.mix_table = mixup_table(self.mixup_alpha, data_seed) if self.mixup_alpha > 0 else None
+        self._mixup_state = None
         # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self._clip_state = None
@@ -180,8 +188,18 @@ class CPUBackend:
         master = self.store.master
         if master.grad is not None:
             master.grad = None
-        logits = m(self._x, True)
-        xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing)
+        x, y, mix = self._x, self._y, {}
+        if self.mix_table is not None:
+            # one draw per step for the whole batch; the partner of n is (n + shift) % N
+            idx, shift = mixup_draw(self.data_seed, self.step_count, self.N, len(self.mix_table))
+            lam = torch.tensor(self.mix_table[idx])
+            x = lam * x + (1.0 - lam) * torch.roll(x, -shift, 0)
+            mix = {"labels_b": torch.roll(y, -shift, 0), "lam": lam}
+            self._mixup_state = (float(lam), shift)
+            if not float(lam) >= 0.5:   # precision is counted against the dominant label
+                y = mix["labels_b"]
+        logits = m(x, True)
+        xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing, **mix)
         # mean over the GLOBAL batch: local mean * (local/global), then sum-allreduce
         (xent * (self.N / self.global_batch)).backward()
         g = master.grad
@@ -208,8 +226,8 @@ class CPUBackend:
             else:
                 master.sub_(lr * gp)
             l2 = 0.5 * float((master * master).sum())
-            correct = float((logits.argmax(1) == self._y).float().sum())
-            top5 = float(ref.in_top_k(logits, self._y, 5).float().sum())
+            correct = float((logits.argmax(1) == y).float().sum())
+            top5 = float(ref.in_top_k(logits, y, 5).float().sum())
             self.last_logits = logits.detach()
         loss_sum = float(xent.detach()) * self.N
         if self.dist is not None and self.world > 1:
@@ -261,6 +279,10 @@ class CPUBackend:
         """(norm, scale) of the last step (None: clipping off, or no step yet)."""
         return self._clip_state
 
+    def mixup_state(self):
+        """(lam, shift) of the last step (None: mixup off, or no step yet)."""
+        return self._mixup_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -298,6 +320,8 @@ class CPUBackend:
             m["precision_top5"] = self._last_top5
         if self._clip_state is not None:
             m["grad_norm"], m["clip_scale"] = self._clip_state
+        if self._mixup_state is not None:
+            m["mixup_lam"] = self._mixup_state[0]
         return m
 
     def synchronize(self):
@@ -344,7 +368,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  allreduce_dtype: str = "fp32", resident=None, shuffle_seed: int = 0,
                  lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
                  lars_skip: str = "vectors", label_smoothing: float = 0.0,
-                 ema_decay: float = 0.0, ema_warmup: bool = True, clip_grad_norm: float = 0.0):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, clip_grad_norm: float = 0.0,
+                 mixup_alpha: float = 0.0):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -362,7 +387,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      shuffle_seed=shuffle_seed, lars_eeta=lars_eeta,
                      lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                      label_smoothing=label_smoothing, ema_decay=ema_decay,
-                     ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm)
+                     ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
+                     mixup_alpha=mixup_alpha)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -371,4 +397,5 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       global_batch=global_batch, allreduce_dtype=allreduce_dtype,
                       lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                       label_smoothing=label_smoothing, ema_decay=ema_decay,
-                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm)
+                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
+                      mixup_alpha=mixup_alpha, data_seed=data_seed)

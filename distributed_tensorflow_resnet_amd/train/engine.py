@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .. import native
-from ..data.cifar import resident_steps_per_epoch, upload_resident
+from ..data.cifar import mixup_table, resident_steps_per_epoch, upload_resident
 from ..models.params import ParamStore
 from ..models.spec import BNSpec, ConvSpec, ModelSpec
 from ..parallel.buckets import assign_buckets, schedule_buckets
@@ -48,7 +48,8 @@ from ..utils import tune
 from ..utils.streamcheck import check_plan
 from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa: F401
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
-                     OPT_FUSED_CLIP_REASON, CLIP_CHUNK, check_clip_grad_norm,
+                     OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
+                     check_mixup_alpha,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
@@ -123,7 +124,7 @@ class Engine:
                  resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -154,6 +155,12 @@ class Engine:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
         self.label_smoothing = float(label_smoothing)
         self.topk = min(5, spec.num_classes)   # k of the `precision_top5` count
+        # mixup in the step's input launch (csrc/data.hip) and two-label targets in whichever
+        # head the plan records: lam ~ Beta(alpha, alpha) from a host-made table, one draw per
+        # step keyed by (data_seed, global_step) (data/cifar.py mixup_draw).  0 = off: nothing
+        # allocated, every plan op for op the same.  The eval plans never mix; training
+        # precision is counted against the dominant label.
+        self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -203,6 +210,9 @@ class Engine:
         if input_mode == "auto":
             input_mode = "cifar_u8" if spec.dataset.startswith("cifar") else "nhwc"
         self.input_mode = input_mode
+        if self.mixup_alpha > 0 and input_mode not in MIXUP_INPUT_MODES:
+            raise ValueError(f"mixup_alpha > 0 needs an input launch to mix in (input_mode one of "
+                             f"{MIXUP_INPUT_MODES}), got input_mode={input_mode!r}")
         # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
         # the device and the step's input launch picks its own records through the keyed
         # permutation of global_step (data/cifar.py resident_index; csrc/data.hip).  Uploaded
@@ -450,6 +460,14 @@ class Engine:
             self.img_u8 = torch.zeros((N, H, W, 3), dtype=torch.uint8, device=dev)
         self.x_in = torch.zeros(self._x_in_shape(N), dtype=BF16, device=dev)
         self.labels = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.mix_table = self.labels_b = self.mix_lam = self.mix_log = None
+        if self.mixup_alpha > 0:
+            # the lam table (uploaded once), the input launch's side outputs the heads read
+            # (partner labels, lam per row) and its {index, shift} log: fixed pointers
+            self.mix_table = torch.from_numpy(mixup_table(self.mixup_alpha, self.data_seed)).to(dev)
+            self.labels_b = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.mix_lam = torch.ones(N, device=dev)
+            self.mix_log = torch.zeros(2, dtype=torch.int32, device=dev)
         st = spec.stem
         self.stem_out = torch.empty((N, st.ho, st.wo, st.cout), dtype=BF16, device=dev)
         if spec.maxpool:
@@ -640,6 +658,18 @@ class Engine:
         torch.cuda.synchronize(self.device)
         norm, scale = self.clip_out.cpu().tolist()
         return norm, scale
+
+    def mixup_state(self):
+        """(lam, shift) of the last step's mixup: batch position n was blended with position
+        (n + shift) % batch at weight lam (synchronises).  None: mixup off."""
+        if self.mix_log is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        return float(self.mix_lam[0].item()), int(self.mix_log[1].item())
+
+    def mix_head_ptrs(self) -> tuple:
+        """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""
+        return () if self.labels_b is None else (self.labels_b.data_ptr(), self.mix_lam.data_ptr())
 
     def ema_state(self):
         """{tensor name: view of its shadow in the flat EMA buffer} (None: --ema_decay 0)."""
@@ -892,7 +922,8 @@ class Engine:
         that EVERY rank must call at the same point; False: this rank's batch.
         ``top5`` adds `precision_top5` (in-top-k, k = min(5, classes)); without it the
         keys are the ones callers that store every scalar have always got.  With clipping
-        on, `grad_norm` and `clip_scale` of the last step are added (clip_state())."""
+        on, `grad_norm` and `clip_scale` of the last step are added (clip_state()); with mixup
+        on, `mixup_lam` (mixup_state())."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
@@ -913,6 +944,8 @@ class Engine:
             m["precision_top5"] = top5_sum / n
         if self.clip_out is not None:
             m["grad_norm"], m["clip_scale"] = self.clip_out.cpu().tolist()
+        if self.mix_lam is not None:
+            m["mixup_lam"] = float(self.mix_lam[0].item())
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -134,6 +134,22 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
+# input modes whose step has an input launch mixup can be built into
+MIXUP_INPUT_MODES = ("cifar_u8", "cifar_resident", "imagenet_u8")
+
+
+def check_mixup_alpha(alpha) -> float:
+    """--mixup_alpha as both backends take it: 0 = off, else the (finite, positive)
+    parameter of the Beta(alpha, alpha) the blend weights are drawn from."""
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"mixup_alpha must be a number, got {alpha!r}") from None
+    if not 0.0 <= alpha < float("inf"):   # negative, inf or NaN
+        raise ValueError(f"mixup_alpha must be finite and >= 0, got {alpha!r}")
+    return alpha
+
+
 def check_clip_grad_norm(c, optimizer: str) -> float:
     """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
     the norm is measured, the scale is exactly 1); not together with lars, whose trust

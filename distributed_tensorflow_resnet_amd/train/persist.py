@@ -410,8 +410,9 @@ class PersistStep:
         # backward / head-fold launches: the head's batch folds' outputs (loss, precision,
         # dense bias and weight gradients; prn_head)
         sp = eng.scalars.data_ptr()
+        mix = dict(zip(("labels_b", "mix_lam"), eng.mix_head_ptrs()))   # {} with mixup off
         return dict(
-            blocks=self.block_dev.data_ptr(), nblocks=self.nblocks, bns=self.bn_dev.data_ptr(),
+            **mix, blocks=self.block_dev.data_ptr(), nblocks=self.nblocks, bns=self.bn_dev.data_ptr(),
             x_in=eng.x_in.data_ptr(), stem_w=eng.convs[spec.stem.name].ohwi, pool_acc=pool_ptr,
             bar=bar_ptr, err=self.err.data_ptr(), dense_w=eng.dense_hwio,
             dense_b=eng.dense_bias, labels=eng.labels.data_ptr(), pooled=eng.pooled.data_ptr(),

@@ -635,9 +635,15 @@ class StepRecorder:
         modes without a launch of their own get a memset, when there is something to clear."""
         e, plan, spec = self.e, self.plan, self.e.spec
         H, W = spec.image_h, spec.image_w
+        # mixup on: the ops' trailing arguments (lam table, [labels,] labels_b, mix_lam, log)
+        mix = lambda *labels: (  # noqa: E731
+            () if e.mix_table is None else
+            (e.mix_table.data_ptr(), e.mix_table.numel(), *labels, e.labels_b.data_ptr(),
+             e.mix_lam.data_ptr(), e.mix_log.data_ptr()))
         if e.input_mode == "cifar_u8":
             plan.cifar_augment(e.img_u8.data_ptr(), e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,
-                               e.data_seed, e.gstep.data_ptr(), 1, 0, *zero)
+                               e.data_seed, e.gstep.data_ptr(), 1, 0, *zero,
+                               *mix(e.labels.data_ptr()))
         elif e.input_mode == "cifar_resident":
             # records and labels are picked on the device from global_step, so the step
             # (and its hipGraph) needs nothing from the host
@@ -645,10 +651,11 @@ class StepRecorder:
                 e.records_u8.data_ptr(), e.labels_all.data_ptr(), e.x_in.data_ptr(),
                 e.labels.data_ptr(), e.gstep.data_ptr(), e.N, H, W, e.cpad_in, e.records,
                 e.rank, e.world, 1, e.shuffle_seed & (2 ** 64 - 1), 4, e.data_seed, 1, 0, 0,
-                *zero)
+                *zero, *mix())
         elif e.input_mode == "imagenet_u8":
             plan.imagenet_u8_pack(e.img_u8.data_ptr(), e.x_in.data_ptr(), e.N, H, W,
-                                  e.data_seed, e.gstep.data_ptr(), 1, *zero, int(e.stem_s2d))
+                                  e.data_seed, e.gstep.data_ptr(), 1, *zero, int(e.stem_s2d),
+                                  *mix(e.labels.data_ptr()))
         elif zero[0]:
             plan.memset(*zero)
 
@@ -740,7 +747,7 @@ class StepRecorder:
                             [N, HL * WL, F, spec.num_classes, e.kpad], 1.0 / e.global_batch,
                             [e.pooled.data_ptr(), e.dlogits.data_ptr(),
                              e.xent_ws.data_ptr(), dact.data_ptr(), fbn.bacc.data_ptr()],
-                            e.label_smoothing, e.topk)
+                            e.label_smoothing, e.topk, *e.mix_head_ptrs())
         else:
             self._bn_finalize(fbn, consumer_conv=False)   # consumer: bnrelu_avgpool
             plan.bnrelu_avgpool(XL.data_ptr(), fbn.scale.data_ptr(), fbn.shift.data_ptr(),
@@ -751,7 +758,7 @@ class StepRecorder:
             plan.softmax_xent(e.logits.data_ptr(), e.kpad, e.labels.data_ptr(), N,
                               spec.num_classes, sp, sp + 4, e.dlogits.data_ptr(),
                               e.dense_bias_grad, 1.0 / e.global_batch, 0, e.xent_ws.data_ptr(),
-                              e.label_smoothing, e.topk, sp + 20)
+                              e.label_smoothing, e.topk, sp + 20, *e.mix_head_ptrs())
         return dact
 
     def _backward(self, dact):

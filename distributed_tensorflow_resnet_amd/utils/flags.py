@@ -80,6 +80,16 @@ def _clip_norm(v) -> float:
     return f
 
 
+def _mixup_alpha(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < float("inf"):   # negative, inf or NaN
+        raise argparse.ArgumentTypeError(f"mixup alpha must be finite and >= 0, got {v!r}")
+    return f
+
+
 def _lr_rate(v) -> float:
     try:
         f = float(v)
@@ -119,6 +129,9 @@ class FlagParser(argparse.ArgumentParser):
         if getattr(ns, "clip_grad_norm", 0.0) > 0 and getattr(ns, "optimizer", "") == "lars":
             self.error("--clip_grad_norm cannot be combined with --optimizer lars: the trust "
                        "ratio already normalises by the gradient norm")
+        if getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "synthetic", False):
+            self.error("--mixup_alpha cannot be combined with --synthetic: the synthetic "
+                       "input has no input launch to mix in")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -222,6 +235,14 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "non-finite norm gives a NaN scale.  0 = off, inf = only measure.  Not "
                         "with --optimizer lars.  On the persistent step it replaces the "
                         "one-launch optimizer by the generic one.")
+    p.add_argument("--mixup_alpha", type=_mixup_alpha, default=0.0,
+                   help="Mixup (Zhang et al. 2018) on the device: every step trains on lam * x + "
+                        "(1 - lam) * x' with the targets mixed the same way, x' the batch rotated "
+                        "by a per-step shift, lam ~ Beta(alpha, alpha) (one draw per step and "
+                        "rank, a function of the seed and global_step, so a resumed run continues "
+                        "the sequence).  Training precision is counted against the dominant "
+                        "label; evaluation never mixes.  0 = off.  Needs real data (not "
+                        "--synthetic); on the GPU, CIFAR or the uint8 ImageNet feed.")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

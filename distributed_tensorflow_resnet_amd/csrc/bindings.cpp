@@ -902,9 +902,20 @@ static Launch mk_memset(ptr_t p, long bytes) {
 // its length, the batch's labels (host-fed ops only), labels_b, mix_lam and mix_log.  Each
 // op is registered at both arities; without them, or with a null table, the launch is the
 // unmixed one.  Checked here, when the op is made, so a plan never records a bad launch.
+// A third arity adds CutMix: cut_table, cut_thresh (of 2^24; 0 = the mixup-only launch) and
+// cut_log after mix_log.
 static Mixup mk_mixup(const char* op, bool host_fed, int train, ptr_t table, int table_len,
-                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log) {
+                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
+                      ptr_t cut_table = 0, long long cut_thresh = 0, ptr_t cut_log = 0) {
   Mixup mx;
+  if (cut_thresh < 0 || cut_thresh > (1 << 24))
+    throw std::invalid_argument(std::string(op) + ": cut_thresh must be in [0, 2^24]");
+  if (cut_thresh > 0 && !cut_table)
+    throw std::invalid_argument(std::string(op) + ": cut_thresh > 0 needs a cut_table");
+  if (cut_thresh > 0 && !train)
+    throw std::invalid_argument(std::string(op) + ": CutMix is a training augmentation");
+  if (cut_thresh > 0 && !table)
+    throw std::invalid_argument(std::string(op) + ": cut_thresh > 0 needs the mixup arguments");
   if (!table) return mx;
   if (!train) throw std::invalid_argument(std::string(op) + ": mixup is a training augmentation");
   if (table_len < 1 || !labels_b || !mix_lam || (host_fed && !labels))
@@ -916,19 +927,26 @@ static Mixup mk_mixup(const char* op, bool host_fed, int train, ptr_t table, int
   mx.labels_b = P<int>(labels_b);
   mx.mix_lam = P<float>(mix_lam);
   mx.mix_log = P<int>(mix_log);
+  if (cut_thresh > 0) {
+    mx.cut_table = P<const int>(cut_table);
+    mx.cut_thresh = (unsigned)cut_thresh;
+    mx.cut_log = P<int>(cut_log);
+  }
   return mx;
 }
 
-static Launch mk_cifar_augment_mix(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
+static Launch mk_cifar_augment_cut(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
                                    unsigned long long seed, ptr_t gstep, int train,
                                    ptr_t crop_log, ptr_t zero, long zero_bytes, ptr_t table,
                                    int table_len, ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
-                                   ptr_t mix_log) {
+                                   ptr_t mix_log, ptr_t cut_table, long long cut_thresh,
+                                   ptr_t cut_log) {
   if (zero_bytes % 16) throw std::invalid_argument("cifar_augment: zero_bytes % 16 != 0");
   const Mixup mx = mk_mixup("cifar_augment", true, train, table, table_len, labels, labels_b,
-                            mix_lam, mix_log);
+                            mix_lam, mix_log, cut_table, cut_thresh, cut_log);
   if (mx.table && !(H == 32 && W == 32 && Cpad == 8))
-    throw std::invalid_argument("cifar_augment: mixup only for 32x32 images with Cpad 8");
+    throw std::invalid_argument(
+        "cifar_augment: mixup and CutMix only for 32x32 images with Cpad 8");
   return [=](hipStream_t s) {
     cifar_augment(P<const uint8_t>(img), P<bf16>(out), N, H, W, Cpad, pad, seed,
                   P<const long long>(gstep), train, P<int>(crop_log), P<void>(zero), zero_bytes,
@@ -936,11 +954,43 @@ static Launch mk_cifar_augment_mix(ptr_t img, ptr_t out, int N, int H, int W, in
   };
 }
 
+static Launch mk_cifar_augment_mix(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
+                                   unsigned long long seed, ptr_t gstep, int train,
+                                   ptr_t crop_log, ptr_t zero, long zero_bytes, ptr_t table,
+                                   int table_len, ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
+                                   ptr_t mix_log) {
+  return mk_cifar_augment_cut(img, out, N, H, W, Cpad, pad, seed, gstep, train, crop_log, zero,
+                              zero_bytes, table, table_len, labels, labels_b, mix_lam, mix_log, 0,
+                              0, 0);
+}
+
 static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
                                unsigned long long seed, ptr_t gstep, int train, ptr_t crop_log,
                                ptr_t zero, long zero_bytes) {
   return mk_cifar_augment_mix(img, out, N, H, W, Cpad, pad, seed, gstep, train, crop_log, zero,
                               zero_bytes, 0, 0, 0, 0, 0, 0);
+}
+
+static Launch mk_cifar_augment_resident_cut(ptr_t records_u8, ptr_t labels_all, ptr_t out,
+                                            ptr_t labels_out, ptr_t pos, int N, int H, int W,
+                                            int Cpad, long records, int rank, int world,
+                                            int shuffle, unsigned long long key_seed, int pad,
+                                            unsigned long long seed, int train, ptr_t crop_log,
+                                            ptr_t idx_log, ptr_t zero, long zero_bytes,
+                                            ptr_t table, int table_len, ptr_t labels_b,
+                                            ptr_t mix_lam, ptr_t mix_log, ptr_t cut_table,
+                                            long long cut_thresh, ptr_t cut_log) {
+  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
+  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
+    throw std::invalid_argument("cifar_augment_resident: null buffer");
+  const Mixup mx = mk_mixup("cifar_augment_resident", false, train, table, table_len, 0, labels_b,
+                            mix_lam, mix_log, cut_table, cut_thresh, cut_log);
+  return [=](hipStream_t s) {
+    cifar_augment_resident(P<const uint8_t>(records_u8), P<const int>(labels_all), P<bf16>(out),
+                           P<int>(labels_out), P<const long long>(pos), N, H, W, Cpad, records,
+                           rank, world, shuffle, key_seed, pad, seed, train, P<int>(crop_log),
+                           P<int>(idx_log), P<void>(zero), zero_bytes, s, mx);
+  };
 }
 
 static Launch mk_cifar_augment_resident_mix(ptr_t records_u8, ptr_t labels_all, ptr_t out,
@@ -951,17 +1001,10 @@ static Launch mk_cifar_augment_resident_mix(ptr_t records_u8, ptr_t labels_all, 
                                             ptr_t idx_log, ptr_t zero, long zero_bytes,
                                             ptr_t table, int table_len, ptr_t labels_b,
                                             ptr_t mix_lam, ptr_t mix_log) {
-  cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
-  if (!records_u8 || !labels_all || !out || !labels_out || !pos)
-    throw std::invalid_argument("cifar_augment_resident: null buffer");
-  const Mixup mx = mk_mixup("cifar_augment_resident", false, train, table, table_len, 0, labels_b,
-                            mix_lam, mix_log);
-  return [=](hipStream_t s) {
-    cifar_augment_resident(P<const uint8_t>(records_u8), P<const int>(labels_all), P<bf16>(out),
-                           P<int>(labels_out), P<const long long>(pos), N, H, W, Cpad, records,
-                           rank, world, shuffle, key_seed, pad, seed, train, P<int>(crop_log),
-                           P<int>(idx_log), P<void>(zero), zero_bytes, s, mx);
-  };
+  return mk_cifar_augment_resident_cut(records_u8, labels_all, out, labels_out, pos, N, H, W, Cpad,
+                                       records, rank, world, shuffle, key_seed, pad, seed, train,
+                                       crop_log, idx_log, zero, zero_bytes, table, table_len,
+                                       labels_b, mix_lam, mix_log, 0, 0, 0);
 }
 
 static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_t out,
@@ -975,19 +1018,30 @@ static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_
                                        crop_log, idx_log, zero, zero_bytes, 0, 0, 0, 0, 0);
 }
 
+static Launch mk_imagenet_u8_pack_cut(ptr_t img, ptr_t out, int N, int H, int W,
+                                      unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
+                                      long zero_bytes, int s2d, ptr_t table, int table_len,
+                                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
+                                      ptr_t cut_table, long long cut_thresh, ptr_t cut_log) {
+  if (zero_bytes % 16) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16 != 0");
+  if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
+  const Mixup mx = mk_mixup("imagenet_u8_pack", true, train, table, table_len, labels, labels_b,
+                            mix_lam, mix_log, cut_table, cut_thresh, cut_log);
+  if (mx.cut_thresh && (H >= (1 << 15) || W >= (1 << 15) || (long)H * W > (1L << 24)))
+    throw std::invalid_argument("imagenet_u8_pack: CutMix needs H, W < 2^15 and H * W <= 2^24");
+  return [=](hipStream_t s) {
+    imagenet_u8_pack(P<const uint8_t>(img), P<bf16>(out), N, H, W, seed,
+                     P<const long long>(gstep), train, P<void>(zero), zero_bytes, s2d, s, mx);
+  };
+}
+
 static Launch mk_imagenet_u8_pack_mix(ptr_t img, ptr_t out, int N, int H, int W,
                                       unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
                                       long zero_bytes, int s2d, ptr_t table, int table_len,
                                       ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
                                       ptr_t mix_log) {
-  if (zero_bytes % 16) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16 != 0");
-  if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
-  const Mixup mx = mk_mixup("imagenet_u8_pack", true, train, table, table_len, labels, labels_b,
-                            mix_lam, mix_log);
-  return [=](hipStream_t s) {
-    imagenet_u8_pack(P<const uint8_t>(img), P<bf16>(out), N, H, W, seed,
-                     P<const long long>(gstep), train, P<void>(zero), zero_bytes, s2d, s, mx);
-  };
+  return mk_imagenet_u8_pack_cut(img, out, N, H, W, seed, gstep, train, zero, zero_bytes, s2d,
+                                 table, table_len, labels, labels_b, mix_lam, mix_log, 0, 0, 0);
 }
 
 static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
@@ -1575,10 +1629,13 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "delay", mk_delay);
   def_op(m, plan, "cifar_augment", mk_cifar_augment);
   def_op(m, plan, "cifar_augment", mk_cifar_augment_mix);
+  def_op(m, plan, "cifar_augment", mk_cifar_augment_cut);
   def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident);
   def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident_mix);
+  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident_cut);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_mix);
+  def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_cut);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

@@ -9,6 +9,10 @@ namespace dtr {
 // mixup, the launch is the unmixed one.  Workgroup n blends its image with that of batch
 // position m = (n + shift) % N; {index, shift} are data/cifar.py mixup_draw(seed, step, N,
 // table_len).
+// CutMix (cut_thresh > 0): a step whose draw falls under cut_thresh (of 2^24; data/cifar.py
+// cutmix_draw) pastes one box of position m's image into this one instead of blending: the
+// box size is cut_table[index] (ch << 16 | cw, cutmix_table), mix_lam gets 1 - area / (H * W)
+// and the fp32 table is not read.  cut_thresh 0 launches the mixup-only kernels.
 struct Mixup {
   const float* table = nullptr;   // [table_len] fp32 in [0, 1]
   int table_len = 0;
@@ -16,6 +20,9 @@ struct Mixup {
   int* labels_b = nullptr;        // [N] the partner's label
   float* mix_lam = nullptr;       // [N] the step's lam in every row
   int* mix_log = nullptr;         // optional {index, shift}
+  const int* cut_table = nullptr; // [table_len] ch << 16 | cw
+  unsigned cut_thresh = 0;        // 0 = never CutMix, 2^24 = always
+  int* cut_log = nullptr;         // optional {cut, y0, y1, x0, x1, area, cy, cx} (0s: mixup step)
 };
 
 void cifar_augment(const uint8_t* img, bf16* out, int N, int H, int W, int Cpad, int pad,

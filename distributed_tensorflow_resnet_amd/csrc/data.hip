@@ -35,13 +35,75 @@ struct MixDraw {
   unsigned index, shift;
 };
 
-__device__ __forceinline__ MixDraw mixup_draw(unsigned long long seed, unsigned long long step,
-                                              int batch, int table_len) {
-  const unsigned long long h =
-      splitmix(splitmix(seed ^ 0x4D4958555021ull) ^ splitmix(step * 0x100000001B3ull));
+__device__ __forceinline__ unsigned long long mix_hash(unsigned long long seed,
+                                                       unsigned long long step) {
+  return splitmix(splitmix(seed ^ 0x4D4958555021ull) ^ splitmix(step * 0x100000001B3ull));
+}
+
+__device__ __forceinline__ MixDraw mix_draw_of(unsigned long long h, int batch, int table_len) {
   MixDraw d;
   d.index = (unsigned)h % (unsigned)table_len;
   d.shift = batch >= 2 ? 1u + (unsigned)(h >> 32) % (unsigned)(batch - 1) : 0u;
+  return d;
+}
+
+__device__ __forceinline__ MixDraw mixup_draw(unsigned long long seed, unsigned long long step,
+                                              int batch, int table_len) {
+  return mix_draw_of(mix_hash(seed, step), batch, table_len);
+}
+
+// ---- CutMix (Yun et al. 2019): x = box ? x_m : x_n, one box per step ---------------------
+// data/cifar.py cutmix_draw is the specification: the same {index, shift}; a salted rehash of
+// the same hash decides, against Mixup::cut_thresh (of 2^24), whether the step pastes or
+// blends, and places the box; its size is cut_table[index] (ch << 16 | cw, made on the host
+// from a Beta draw, so no sqrt runs here).  lam = (H*W - area) / (H*W), one correctly rounded
+// fp32 division (this file is built without fast-math).  In a CutMix step the fp32 table is
+// not read.  Every operand is uniform over the grid.
+enum { MIX_OFF = 0, MIX_BLEND = 1, MIX_CUT = 2 };   // the input kernels' MIX template argument
+
+struct CutBox {
+  int cut, y0, y1, x0, x1;
+  __device__ __forceinline__ bool has(int y, int x) const {
+    return y >= y0 && y < y1 && x >= x0 && x < x1;
+  }
+};
+
+// the step's draw with CutMix on: the mode, the box and lam; `log` (one thread of the grid)
+// also writes mix_log and cut_log
+__device__ __forceinline__ MixDraw cutmix_draw(const Mixup& mx, unsigned long long seed,
+                                               unsigned long long step, int batch, int H, int W,
+                                               bool log, CutBox& b, float& lam) {
+  const unsigned long long h = mix_hash(seed, step);
+  const MixDraw d = mix_draw_of(h, batch, mx.table_len);
+  const unsigned long long h2 = splitmix(h ^ 0x4355544D4958ull);
+  b = CutBox{};
+  int area = 0, cy = 0, cx = 0;
+  b.cut = (unsigned)(h2 >> 40) < mx.cut_thresh;
+  if (b.cut) {
+    const int e = mx.cut_table[d.index];
+    const int ch2 = ((e >> 16) & 0xFFFF) >> 1, cw2 = (e & 0xFFFF) >> 1;
+    cy = (int)(((unsigned)h2 & 0xFFFFu) % (unsigned)H);
+    cx = (int)(((unsigned)(h2 >> 16) & 0xFFFFu) % (unsigned)W);
+    b.y0 = max(cy - ch2, 0);
+    b.y1 = min(cy + ch2, H);
+    b.x0 = max(cx - cw2, 0);
+    b.x1 = min(cx + cw2, W);
+    area = (b.y1 - b.y0) * (b.x1 - b.x0);
+    lam = (float)(H * W - area) / (float)(H * W);
+  } else {
+    lam = mx.table[d.index];
+  }
+  if (log) {
+    if (mx.mix_log) {
+      mx.mix_log[0] = (int)d.index;
+      mx.mix_log[1] = (int)d.shift;
+    }
+    if (mx.cut_log) {
+      const int v[8] = {b.cut, b.y0, b.y1, b.x0, b.x1, area, cy, cx};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) mx.cut_log[i] = v[i];
+    }
+  }
   return d;
 }
 
@@ -57,7 +119,9 @@ __device__ __forceinline__ MixDraw mixup_draw(unsigned long long seed, unsigned 
 // the crop/flip hash is keyed with.  MIX: the workgroup also stages `src_b`, the record
 // of batch position m, standardises it with position m's own crop/flip hash -- the two
 // fp32 images are exactly what the unmixed body produces for n and m -- and writes
-// bf16(lam * a + (1.f - lam) * b): blended in fp32, rounded once.
+// bf16(lam * a + (1.f - lam) * b): blended in fp32, rounded once.  MIX == MIX_CUT: the same
+// launch with CutMix; in a step with box.cut the pixel is bf16(box.has(y, x) ? b : a), a
+// select, so every output pixel is bit for bit the unmixed body's for n or for m.
 //
 // cifar_crop_stats: the staged record `im` -> this thread's PPT pixels x 3 channels of
 // batch position n's crop, the image's mean and 1 / adjusted std.  `red`: 8 floats of
@@ -114,11 +178,12 @@ __device__ __forceinline__ void cifar_crop_stats(const uint8_t* im, int n, int p
 }
 
 // im / im_b: 3072 B each (im_b only with MIX); red: 8 floats (16 with MIX)
-template <int CPAD, bool MIX>
+template <int CPAD, int MIX>
 __device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ src,
                                                     const uint8_t* __restrict__ src_b,
                                                     bf16* __restrict__ out, int n, int m,
-                                                    float lam, int pad, unsigned long long seed,
+                                                    float lam, const CutBox& box, int pad,
+                                                    unsigned long long seed,
                                                     unsigned long long step, int train,
                                                     int* crop_log, uint8_t* im, uint8_t* im_b,
                                                     float* red) {
@@ -137,13 +202,17 @@ __device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ 
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
     const int p = tid + k * 256;
+    const bool paste = MIX == MIX_CUT && box.cut && box.has(p >> 5, p & 31);
     bf16x8 r = {};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float a = (v[k][c] - mean) * inv;
       if (MIX) {
         const float b = (vb[k][c] - mean_b) * inv_b;
-        r[c] = (bf16)(lam * a + (1.f - lam) * b);
+        if (MIX == MIX_CUT && box.cut)
+          r[c] = (bf16)(paste ? b : a);
+        else
+          r[c] = (bf16)(lam * a + (1.f - lam) * b);
       } else {
         r[c] = (bf16)a;
       }
@@ -153,9 +222,16 @@ __device__ __forceinline__ void cifar_augment_image(const uint8_t* __restrict__ 
 }
 
 // the step's draw, and batch position n's side outputs (thread 0 of workgroup n)
+template <int MIX>
 __device__ __forceinline__ MixDraw mix_side_outputs(const Mixup& mx, unsigned long long seed,
                                                     unsigned long long step, int n, int batch,
-                                                    float& lam) {
+                                                    float& lam, CutBox& box) {
+  if (MIX == MIX_CUT) {   // 32x32: the CIFAR launches
+    const MixDraw d =
+        cutmix_draw(mx, seed, step, batch, 32, 32, threadIdx.x == 0 && n == 0, box, lam);
+    if (threadIdx.x == 0) mx.mix_lam[n] = lam;
+    return d;
+  }
   const MixDraw d = mixup_draw(seed, step, batch, mx.table_len);
   lam = mx.table[d.index];
   if (threadIdx.x == 0) {
@@ -169,7 +245,7 @@ __device__ __forceinline__ MixDraw mix_side_outputs(const Mixup& mx, unsigned lo
 }
 
 // workgroup n of the host-fed launch; im: 3072 B (6144 with MIX), red: 8 floats (16)
-template <int CPAD, bool MIX>
+template <int CPAD, int MIX>
 __device__ __forceinline__ void cifar_augment_wg(const uint8_t* __restrict__ img,
                                                  bf16* __restrict__ out, int pad,
                                                  unsigned long long seed, const long long* gstep,
@@ -183,13 +259,14 @@ __device__ __forceinline__ void cifar_augment_wg(const uint8_t* __restrict__ img
   const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
   int m = n;
   float lam = 1.f;
+  CutBox box = {};
   if (MIX) {
-    const MixDraw d = mix_side_outputs(mx, seed, step, n, (int)gridDim.x, lam);
+    const MixDraw d = mix_side_outputs<MIX>(mx, seed, step, n, (int)gridDim.x, lam, box);
     m = (int)(((unsigned)n + d.shift) % gridDim.x);
     if (tid == 0) mx.labels_b[n] = mx.labels[m];
   }
-  cifar_augment_image<CPAD, MIX>(img + (long)n * CHW, img + (long)m * CHW, out, n, m, lam, pad,
-                                 seed, step, train, crop_log, im, im + (MIX ? CHW : 0), red);
+  cifar_augment_image<CPAD, MIX>(img + (long)n * CHW, img + (long)m * CHW, out, n, m, lam, box,
+                                 pad, seed, step, train, crop_log, im, im + (MIX ? CHW : 0), red);
 }
 
 template <int CPAD>
@@ -199,8 +276,8 @@ cifar_augment_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, in
                      uint4* __restrict__ zero, long zero_vec) {
   __shared__ __attribute__((aligned(16))) uint8_t im[3 * 32 * 32];
   __shared__ float red[8];
-  cifar_augment_wg<CPAD, false>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec,
-                                Mixup{}, im, red);
+  cifar_augment_wg<CPAD, MIX_OFF>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec,
+                                  Mixup{}, im, red);
 }
 
 // the same launch with mixup (a kernel of its own: the unmixed one keeps its code and budget)
@@ -211,8 +288,21 @@ cifar_mixup_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int 
                    uint4* __restrict__ zero, long zero_vec, Mixup mx) {
   __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
   __shared__ float red[16];
-  cifar_augment_wg<CPAD, true>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec, mx,
-                               im, red);
+  cifar_augment_wg<CPAD, MIX_BLEND>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec,
+                                    mx, im, red);
+}
+
+// the same launch with mixup and CutMix, switched per step (a kernel of its own again: the
+// mixup-only one keeps its code and budget)
+template <int CPAD>
+__global__ void __launch_bounds__(256)
+cifar_cutmix_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int pad,
+                    unsigned long long seed, const long long* gstep, int train, int* crop_log,
+                    uint4* __restrict__ zero, long zero_vec, Mixup mx) {
+  __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
+  __shared__ float red[16];
+  cifar_augment_wg<CPAD, MIX_CUT>(img, out, pad, seed, gstep, train, crop_log, zero, zero_vec, mx,
+                                  im, red);
 }
 
 // ---- device-resident split: the workgroup picks its own record ----------------------
@@ -271,7 +361,7 @@ __device__ __forceinline__ int resident_record(unsigned long long step, int n, i
 }
 
 // workgroup n of the resident launch; im: 3072 B (6144 with MIX), red: 8 floats (16)
-template <bool MIX>
+template <int MIX>
 __device__ __forceinline__ void cifar_resident_wg(
     const uint8_t* __restrict__ records_u8, const int* __restrict__ labels_all,
     bf16* __restrict__ out, int* __restrict__ labels_out, const long long* pos, int records,
@@ -294,15 +384,16 @@ __device__ __forceinline__ void cifar_resident_wg(
   }
   int m = n, idx_b = idx;
   float lam = 1.f;
+  CutBox box = {};
   if (MIX) {   // the partner's record: position m's own pick
-    const MixDraw d = mix_side_outputs(mx, seed, step, n, (int)gridDim.x, lam);
+    const MixDraw d = mix_side_outputs<MIX>(mx, seed, step, n, (int)gridDim.x, lam, box);
     m = (int)(((unsigned)n + d.shift) % gridDim.x);
     idx_b = resident_record(step, m, (int)gridDim.x, records, rank, world, shuffle, key_seed);
     if (tid == 0) mx.labels_b[n] = labels_all[idx_b];
   }
   cifar_augment_image<8, MIX>(records_u8 + (long)idx * CHW, records_u8 + (long)idx_b * CHW, out, n,
-                              m, lam, pad, seed, step, train, crop_log, im, im + (MIX ? CHW : 0),
-                              red);
+                              m, lam, box, pad, seed, step, train, crop_log, im,
+                              im + (MIX ? CHW : 0), red);
 }
 
 __global__ void __launch_bounds__(256)
@@ -314,9 +405,9 @@ cifar_augment_resident_kernel(const uint8_t* __restrict__ records_u8,
                               int* idx_log, uint4* __restrict__ zero, long zero_vec) {
   __shared__ __attribute__((aligned(16))) uint8_t im[3 * 32 * 32];
   __shared__ float red[8];
-  cifar_resident_wg<false>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
-                           shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec,
-                           Mixup{}, im, red);
+  cifar_resident_wg<MIX_OFF>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
+                             shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec,
+                             Mixup{}, im, red);
 }
 
 __global__ void __launch_bounds__(256)
@@ -328,9 +419,23 @@ cifar_mixup_resident_kernel(const uint8_t* __restrict__ records_u8,
                             uint4* __restrict__ zero, long zero_vec, Mixup mx) {
   __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
   __shared__ float red[16];
-  cifar_resident_wg<true>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
-                          shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec, mx,
-                          im, red);
+  cifar_resident_wg<MIX_BLEND>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
+                               shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero,
+                               zero_vec, mx, im, red);
+}
+
+__global__ void __launch_bounds__(256)
+cifar_cutmix_resident_kernel(const uint8_t* __restrict__ records_u8,
+                             const int* __restrict__ labels_all, bf16* __restrict__ out,
+                             int* __restrict__ labels_out, const long long* pos, int records,
+                             int rank, int world, int shuffle, unsigned long long key_seed, int pad,
+                             unsigned long long seed, int train, int* crop_log, int* idx_log,
+                             uint4* __restrict__ zero, long zero_vec, Mixup mx) {
+  __shared__ __attribute__((aligned(16))) uint8_t im[2 * 3 * 32 * 32];
+  __shared__ float red[16];
+  cifar_resident_wg<MIX_CUT>(records_u8, labels_all, out, labels_out, pos, records, rank, world,
+                             shuffle, key_seed, pad, seed, train, crop_log, idx_log, zero, zero_vec,
+                             mx, im, red);
 }
 
 // Generic-shape fallback (any H, W, Cpad): one element per thread iteration.
@@ -394,11 +499,20 @@ cifar_augment_generic_kernel(const uint8_t* __restrict__ img, bf16* __restrict__
 
 // the mixup arguments of an input launch (`host_fed`: the partner labels come from `labels`)
 static Mixup mix_args(const char* op, const Mixup& mix, bool host_fed, int train) {
-  if (!mix.table) return Mixup{};
-  if (!train) throw std::invalid_argument(std::string(op) + ": mixup is a training augmentation");
+  if (!mix.table) {
+    if (mix.cut_thresh)
+      throw std::invalid_argument(std::string(op) + ": cut_thresh > 0 needs the mixup arguments");
+    return Mixup{};
+  }
+  if (!train)
+    throw std::invalid_argument(std::string(op) + ": mixup and CutMix are training augmentations");
   if (mix.table_len < 1 || !mix.labels_b || !mix.mix_lam || (host_fed && !mix.labels))
     throw std::invalid_argument(std::string(op) + ": mixup needs a table of >= 1 entries, " +
                                 (host_fed ? "labels, " : "") + "labels_b and mix_lam");
+  if (mix.cut_thresh > (1u << 24))
+    throw std::invalid_argument(std::string(op) + ": cut_thresh is out of 2^24");
+  if (mix.cut_thresh && !mix.cut_table)
+    throw std::invalid_argument(std::string(op) + ": cut_thresh > 0 needs a cut_table");
   return mix;
 }
 
@@ -411,7 +525,10 @@ void cifar_augment(const uint8_t* img, bf16* out, int N, int H, int W, int Cpad,
   const Mixup mx = mix_args("cifar_augment", mix, true, train);
   if (mx.table && !(H == 32 && W == 32 && Cpad == 8))
     throw std::invalid_argument("cifar_augment: mixup only for 32x32 images with Cpad 8");
-  if (mx.table)
+  if (mx.cut_thresh)
+    hipLaunchKernelGGL(cifar_cutmix_kernel<8>, dim3(N), dim3(256), 0, s, img, out, pad, seed,
+                       gstep, train, crop_log, z, zv, mx);
+  else if (mx.table)
     hipLaunchKernelGGL(cifar_mixup_kernel<8>, dim3(N), dim3(256), 0, s, img, out, pad, seed,
                        gstep, train, crop_log, z, zv, mx);
   else if (H == 32 && W == 32 && Cpad == 8)
@@ -435,7 +552,12 @@ void cifar_augment_resident(const uint8_t* records_u8, const int* labels_all, bf
   if (reinterpret_cast<uintptr_t>(records_u8) % 16)
     throw std::invalid_argument("cifar_augment_resident: records not 16-B aligned");
   const Mixup mx = mix_args("cifar_augment_resident", mix, false, train);
-  if (mx.table)
+  if (mx.cut_thresh)
+    hipLaunchKernelGGL(cifar_cutmix_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
+                       labels_all, out, labels_out, pos, (int)records, rank, world,
+                       shuffle ? 1 : 0, key_seed, pad, seed, train, crop_log, idx_log,
+                       reinterpret_cast<uint4*>(zero), zero ? zero_bytes / 16 : 0, mx);
+  else if (mx.table)
     hipLaunchKernelGGL(cifar_mixup_resident_kernel, dim3(N), dim3(256), 0, s, records_u8,
                        labels_all, out, labels_out, pos, (int)records, rank, world,
                        shuffle ? 1 : 0, key_seed, pad, seed, train, crop_log, idx_log,
@@ -579,6 +701,62 @@ imagenet_u8_pack_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out,
   *reinterpret_cast<bf16x8*>(out + p * 8) = r;
 }
 
+// The mixed launch with CutMix (a kernel of its own: the two above keep their code).  The box
+// is in the flipped image's coordinates, before the space-to-depth packing.  In a CutMix step
+// the thread reads only the one source pixel it writes -- the partner's inside the box, with
+// the partner's own flip, its own outside; in a mixup step it blends as the kernel above.
+__global__ void __launch_bounds__(256)
+imagenet_u8_cutmix_kernel(const uint8_t* __restrict__ img, bf16* __restrict__ out, int H, int W,
+                          unsigned long long seed, const long long* gstep, int train,
+                          uint4* __restrict__ zero, long zero_vec, long npix, int s2d, int N,
+                          Mixup mx) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < zero_vec; i += (long)gridDim.x * 256)
+    zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  const long p = blockIdx.x * 256L + threadIdx.x;
+  if (p >= npix) return;
+  const long HW = (long)H * W;
+  const long n = p / HW;
+  const int rem = (int)(p - n * HW);
+  const int y = rem / W, x = rem - y * W;
+  const unsigned long long step = (train && gstep) ? (unsigned long long)*gstep : 0ull;
+  CutBox box;
+  float lam;
+  const MixDraw d = cutmix_draw(mx, seed, step, N, H, W, p == 0, box, lam);
+  const long m = (long)(((unsigned)n + d.shift) % (unsigned)N);
+  const bool paste = box.cut && box.has(y, x);
+  const long own = paste ? m : n;   // the image of the one pixel a CutMix step reads
+  const int flip =
+      (int)((splitmix(seed ^ splitmix(step * 0x100000001B3ull + (unsigned long long)own)) >> 32) & 1);
+  const int xs = flip ? W - 1 - x : x;
+  const uint8_t* src = img + ((own * H + y) * (long)W + xs) * 3;
+  float f0 = (float)src[0] - 123.68f, f1 = (float)src[1] - 116.78f, f2 = (float)src[2] - 103.94f;
+  if (!box.cut) {
+    const int flip_b =
+        (int)((splitmix(seed ^ splitmix(step * 0x100000001B3ull + (unsigned long long)m)) >> 32) & 1);
+    const int xb = flip_b ? W - 1 - x : x;
+    const uint8_t* sb = img + ((m * H + y) * (long)W + xb) * 3;
+    f0 = lam * f0 + (1.f - lam) * ((float)sb[0] - 123.68f);
+    f1 = lam * f1 + (1.f - lam) * ((float)sb[1] - 116.78f);
+    f2 = lam * f2 + (1.f - lam) * ((float)sb[2] - 103.94f);
+  }
+  if (rem == 0) {   // the image's first pixel writes its side outputs
+    mx.labels_b[n] = mx.labels[m];
+    mx.mix_lam[n] = lam;
+  }
+  const bf16 c0 = (bf16)f0, c1 = (bf16)f1, c2 = (bf16)f2;
+  if (s2d) {
+    bf16x4 r = {c0, c1, c2, (bf16)0.f};
+    const long q = (n * (H >> 1) + (y >> 1)) * (long)(W >> 1) + (x >> 1);
+    *reinterpret_cast<bf16x4*>(out + q * 16 + ((y & 1) * 2 + (x & 1)) * 4) = r;
+    return;
+  }
+  bf16x8 r = {};
+  r[0] = c0;
+  r[1] = c1;
+  r[2] = c2;
+  *reinterpret_cast<bf16x8*>(out + p * 8) = r;
+}
+
 void imagenet_u8_pack(const uint8_t* img, bf16* out, int N, int H, int W,
                       unsigned long long seed, const long long* gstep, int train, void* zero,
                       long zero_bytes, int s2d, hipStream_t s, const Mixup& mix) {
@@ -587,7 +765,13 @@ void imagenet_u8_pack(const uint8_t* img, bf16* out, int N, int H, int W,
   const Mixup mx = mix_args("imagenet_u8_pack", mix, true, train);
   const long npix = (long)N * H * W;
   const int grid = (int)((npix + 255) / 256);
-  if (mx.table)
+  if (mx.cut_thresh && (H >= (1 << 15) || W >= (1 << 15) || (long)H * W > (1L << 24)))
+    throw std::invalid_argument("imagenet_u8_pack: CutMix needs H, W < 2^15 and H * W <= 2^24");
+  if (mx.cut_thresh)
+    hipLaunchKernelGGL(imagenet_u8_cutmix_kernel, dim3(grid), dim3(256), 0, s, img, out, H, W,
+                       seed, gstep, train, reinterpret_cast<uint4*>(zero),
+                       zero ? zero_bytes / 16 : 0, npix, s2d, N, mx);
+  else if (mx.table)
     hipLaunchKernelGGL(imagenet_u8_pack_kernel<true>, dim3(grid), dim3(256), 0, s, img, out, H, W,
                        seed, gstep, train, reinterpret_cast<uint4*>(zero),
                        zero ? zero_bytes / 16 : 0, npix, s2d, N, mx);

@@ -282,6 +282,79 @@ def mixup_draw(seed: int, step: int, batch: int, table_len: int) -> tuple[int, i
     return index, shift
 
 
+# ---------------------------------------------------------------- cutmix
+# CutMix (Yun et al. 2019) in the same launches: batch position n trains on its own image with
+# one box replaced by the same box of position m's image, m = (n + shift) % batch as above,
+# and the two-label target at lam = 1 - area / (H * W).  One box per step for the rank's whole
+# batch, as in the paper's code, in the coordinates of the augmented output image (after crop
+# and flip, before the space-to-depth packing).  A pasted pixel is a select, never a blend:
+# every output pixel is bit for bit a pixel of one of the two unmixed images.  With both
+# augmentations on, a step is a CutMix step with probability mix_switch_prob, a mixup step
+# otherwise.  The functions below are the specification the kernels must equal.
+_CUTMIX_SALT = 0x4355544D4958   # "CUTMIX"
+CUTMIX_THRESH_ONE = 1 << 24
+
+
+def _mix_hash(seed: int, step: int) -> int:
+    """The 64-bit hash mixup_draw takes (index, shift) from."""
+    return splitmix(splitmix((seed & _M64) ^ _MIXUP_SALT) ^
+                    splitmix((step * 0x100000001B3) & _M64))
+
+
+def cutmix_table(alpha: float, seed: int, H: int, W: int,
+                 length: int = MIXUP_TABLE_LEN) -> np.ndarray:
+    """`length` box sizes as int32 ``ch << 16 | cw``: lam ~ Beta(alpha, alpha) (mixup_table
+    under a salted seed), r = sqrt(1 - lam) in fp64, ch = int(H * r), cw = int(W * r) -- the
+    paper's rand_bbox.  Computed once on the host and uploaded once, so neither a sqrt nor a
+    sampler runs on the device."""
+    if not (0 < H < 1 << 15 and 0 < W < 1 << 15):
+        raise ValueError(f"cutmix needs 0 < H, W < 2**15, got {H}x{W}")
+    lam = mixup_table(alpha, seed ^ _CUTMIX_SALT, length)
+    r = np.sqrt(1.0 - lam.astype(np.float64))
+    ch = (H * r).astype(np.int64)
+    cw = (W * r).astype(np.int64)
+    return ((ch << 16) | cw).astype(np.int32)
+
+
+def cutmix_thresh(mixup_alpha: float, cutmix_alpha: float, switch_prob: float) -> int:
+    """The 24-bit threshold a step's draw is compared with, in [0, 2**24]: 0 = never CutMix
+    (cutmix_alpha 0), 2**24 = always (mixup_alpha 0), else round(switch_prob * 2**24)."""
+    if not cutmix_alpha > 0:
+        return 0
+    if not mixup_alpha > 0:
+        return CUTMIX_THRESH_ONE
+    if not 0.0 <= switch_prob <= 1.0:
+        raise ValueError(f"mix_switch_prob must be in [0, 1], got {switch_prob!r}")
+    return int(round(switch_prob * CUTMIX_THRESH_ONE))
+
+
+def cutmix_draw(seed: int, step: int, batch: int, table_len: int, H: int, W: int,
+                cut_entry_of, thresh: int) -> dict:
+    """The step's draw with CutMix: ``index``, ``shift`` exactly mixup_draw's; ``cut`` whether
+    this is a CutMix step ((h2 >> 40) < thresh, h2 a salted rehash of mixup_draw's hash).  A
+    CutMix step also has ``cy, cx`` (the box centre), ``y0, y1, x0, x1`` (the box, clipped to
+    the image), ``area`` and ``lam`` = fp32(H*W - area) / fp32(H*W), one correctly rounded
+    fp32 division; (ch, cw) come from ``cut_entry_of[index]``.  A mixup step has ``lam`` None
+    (it is the fp32 table's) and the box fields 0.  Integers only, but for that quotient."""
+    index, shift = mixup_draw(seed, step, batch, table_len)
+    if not 0 <= thresh <= CUTMIX_THRESH_ONE:
+        raise ValueError(f"thresh must be in [0, 2**24], got {thresh!r}")
+    h2 = splitmix(_mix_hash(seed, step) ^ _CUTMIX_SALT)
+    d = {"index": index, "shift": shift, "cut": (h2 >> 40) < thresh, "lam": None,
+         "cy": 0, "cx": 0, "y0": 0, "y1": 0, "x0": 0, "x1": 0, "area": 0}
+    if not d["cut"]:
+        return d
+    entry = int(cut_entry_of[index])
+    ch, cw = (entry >> 16) & 0xFFFF, entry & 0xFFFF
+    cy, cx = (h2 & 0xFFFF) % H, ((h2 >> 16) & 0xFFFF) % W
+    y0, y1 = max(cy - ch // 2, 0), min(cy + ch // 2, H)
+    x0, x1 = max(cx - cw // 2, 0), min(cx + cw // 2, W)
+    area = (y1 - y0) * (x1 - x0)
+    d.update(cy=cy, cx=cx, y0=y0, y1=y1, x0=x0, x1=x1, area=area,
+             lam=np.float32(H * W - area) / np.float32(H * W))
+    return d
+
+
 def synthetic_batches(batch_size: int, num_classes: int = 10, seed: int = 0):
     """Endless random uint8 CIFAR-shaped records (for --synthetic)."""
     g = torch.Generator().manual_seed(seed)

@@ -13,16 +13,19 @@ from __future__ import annotations
 import math
 import os
 
+import numpy as np
 import torch
 
-from ..data.cifar import augment_cpu, mixup_draw, mixup_table
+from ..data.cifar import (MIXUP_TABLE_LEN, augment_cpu, cutmix_draw, cutmix_table, cutmix_thresh,
+                          mixup_draw, mixup_table)
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_state
-from .layout import check_clip_grad_norm, check_mixup_alpha
+from .layout import (check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
+                     check_mixup_alpha)
 
 
 class GPUBackend:
@@ -101,6 +104,9 @@ class GPUBackend:
     def mixup_state(self):
         return self.engine.mixup_state()
 
+    def mix_state(self):
+        return self.engine.mix_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -115,12 +121,26 @@ class CPUBackend:
                  allreduce_dtype: str = "fp32", lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0, data_seed: int = 1234):
+                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0, data_seed: int = 1234,
+                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
         self.mix_table = mixup_table(self.mixup_alpha, data_seed) if self.mixup_alpha > 0 else None
         self._mixup_state = None
+        # CutMix, the same launches' paste on the augmented fp32 batch (0 = off); with CutMix
+        # alone every step pastes and the lam table (all 1, as the engine's) is never read
+        self.cutmix_alpha = check_cutmix_alpha(cutmix_alpha)
+        self.cut_thresh = cutmix_thresh(self.mixup_alpha, self.cutmix_alpha,
+                                        check_mix_switch_prob(mix_switch_prob))
+        self.cut_table = None
+        if self.cutmix_alpha > 0:
+            self.cut_table = cutmix_table(self.cutmix_alpha, data_seed, spec.image_h, spec.image_w)
+            if self.mix_table is None:
+                self.mix_table = np.ones(MIXUP_TABLE_LEN, dtype=np.float32)
+        self._mix_state = None
+        self._cut_area = None
+        self.last_input = None     # the batch the last step fed the model (mixup / CutMix on)
         # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self._clip_state = None
@@ -192,10 +212,25 @@ class CPUBackend:
         if self.mix_table is not None:
             # one draw per step for the whole batch; the partner of n is (n + shift) % N
             idx, shift = mixup_draw(self.data_seed, self.step_count, self.N, len(self.mix_table))
-            lam = torch.tensor(self.mix_table[idx])
-            x = lam * x + (1.0 - lam) * torch.roll(x, -shift, 0)
+            d = {"cut": False}
+            if self.cut_table is not None:
+                d = cutmix_draw(self.data_seed, self.step_count, self.N, len(self.mix_table),
+                                x.shape[1], x.shape[2], self.cut_table, self.cut_thresh)
+            if d["cut"]:   # a select: the partner's pixels inside the box, its own outside
+                lam = torch.tensor(d["lam"])
+                box = torch.zeros((x.shape[1], x.shape[2], 1), dtype=torch.bool)   # x is NHWC
+                box[d["y0"]:d["y1"], d["x0"]:d["x1"]] = True
+                x = torch.where(box, torch.roll(x, -shift, 0), x)
+            else:
+                lam = torch.tensor(self.mix_table[idx])
+                x = lam * x + (1.0 - lam) * torch.roll(x, -shift, 0)
             mix = {"labels_b": torch.roll(y, -shift, 0), "lam": lam}
             self._mixup_state = (float(lam), shift)
+            self._mix_state = {"mode": "cutmix" if d["cut"] else "mixup", "lam": float(lam),
+                               "shift": shift,
+                               "box": (d["y0"], d["y1"], d["x0"], d["x1"]) if d["cut"] else None}
+            self._cut_area = d["area"] if d["cut"] else None
+            self.last_input = x
             if not float(lam) >= 0.5:   # precision is counted against the dominant label
                 y = mix["labels_b"]
         logits = m(x, True)
@@ -283,6 +318,10 @@ class CPUBackend:
         """(lam, shift) of the last step (None: mixup off, or no step yet)."""
         return self._mixup_state
 
+    def mix_state(self):
+        """As Engine.mix_state (None: mixup and CutMix off, or no step yet)."""
+        return self._mix_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -322,6 +361,9 @@ class CPUBackend:
             m["grad_norm"], m["clip_scale"] = self._clip_state
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
+            m["mix_mode"] = int(self._cut_area is not None)
+            if self._cut_area is not None:
+                m["cutmix_area"] = self._cut_area
         return m
 
     def synchronize(self):
@@ -369,7 +411,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  lars_eeta: float = 0.001, lars_epsilon: float = 0.0,
                  lars_skip: str = "vectors", label_smoothing: float = 0.0,
                  ema_decay: float = 0.0, ema_warmup: bool = True, clip_grad_norm: float = 0.0,
-                 mixup_alpha: float = 0.0):
+                 mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+                 mix_switch_prob: float = 0.5):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -388,7 +431,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                      label_smoothing=label_smoothing, ema_decay=ema_decay,
                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
-                     mixup_alpha=mixup_alpha)
+                     mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha,
+                     mix_switch_prob=mix_switch_prob)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -398,4 +442,5 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, lars_skip=lars_skip,
                       label_smoothing=label_smoothing, ema_decay=ema_decay,
                       ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
-                      mixup_alpha=mixup_alpha, data_seed=data_seed)
+                      mixup_alpha=mixup_alpha, data_seed=data_seed, cutmix_alpha=cutmix_alpha,
+                      mix_switch_prob=mix_switch_prob)

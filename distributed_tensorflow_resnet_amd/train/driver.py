@@ -224,7 +224,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            lars_eeta=flags.lars_eeta, lars_epsilon=flags.lars_epsilon,
                            lars_skip=flags.lars_skip, label_smoothing=flags.label_smoothing,
                            ema_decay=flags.ema_decay, ema_warmup=flags.ema_warmup,
-                           clip_grad_norm=flags.clip_grad_norm, mixup_alpha=flags.mixup_alpha)
+                           clip_grad_norm=flags.clip_grad_norm, mixup_alpha=flags.mixup_alpha,
+                           cutmix_alpha=flags.cutmix_alpha,
+                           mix_switch_prob=flags.mix_switch_prob)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

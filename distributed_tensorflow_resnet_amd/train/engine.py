@@ -40,7 +40,8 @@ import numpy as np
 import torch
 
 from .. import native
-from ..data.cifar import mixup_table, resident_steps_per_epoch, upload_resident
+from ..data.cifar import (MIXUP_TABLE_LEN, cutmix_table, cutmix_thresh, mixup_table,
+                          resident_steps_per_epoch, upload_resident)
 from ..models.params import ParamStore
 from ..models.spec import BNSpec, ConvSpec, ModelSpec
 from ..parallel.buckets import assign_buckets, schedule_buckets
@@ -49,7 +50,7 @@ from ..utils.streamcheck import check_plan
 from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa: F401
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
-                     check_mixup_alpha,
+                     check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
@@ -124,7 +125,8 @@ class Engine:
                  resident=None, shuffle_seed: int = 0, lars_eeta: float = 0.001,
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0):
+                 clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0,
+                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -161,6 +163,13 @@ class Engine:
         # allocated, every plan op for op the same.  The eval plans never mix; training
         # precision is counted against the dominant label.
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
+        # CutMix in the same launch (data/cifar.py cutmix_draw): a step whose draw falls under
+        # cut_thresh (of 2^24) pastes one box of the partner's image instead of blending, and
+        # the heads see lam = 1 - area / (H * W).  With both on, mix_switch_prob is the share
+        # of CutMix steps.  0 = off: every plan records what it records without it.
+        self.cutmix_alpha = check_cutmix_alpha(cutmix_alpha)
+        self.mix_switch_prob = check_mix_switch_prob(mix_switch_prob)
+        self.cut_thresh = cutmix_thresh(self.mixup_alpha, self.cutmix_alpha, self.mix_switch_prob)
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -213,6 +222,9 @@ class Engine:
         if self.mixup_alpha > 0 and input_mode not in MIXUP_INPUT_MODES:
             raise ValueError(f"mixup_alpha > 0 needs an input launch to mix in (input_mode one of "
                              f"{MIXUP_INPUT_MODES}), got input_mode={input_mode!r}")
+        if self.cutmix_alpha > 0 and input_mode not in MIXUP_INPUT_MODES:
+            raise ValueError(f"cutmix_alpha > 0 needs an input launch to paste in (input_mode one "
+                             f"of {MIXUP_INPUT_MODES}), got input_mode={input_mode!r}")
         # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
         # the device and the step's input launch picks its own records through the keyed
         # permutation of global_step (data/cifar.py resident_index; csrc/data.hip).  Uploaded
@@ -461,13 +473,22 @@ class Engine:
         self.x_in = torch.zeros(self._x_in_shape(N), dtype=BF16, device=dev)
         self.labels = torch.zeros(N, dtype=torch.int32, device=dev)
         self.mix_table = self.labels_b = self.mix_lam = self.mix_log = None
-        if self.mixup_alpha > 0:
+        self.cut_table = self.cut_log = None
+        if self.mixup_alpha > 0 or self.cutmix_alpha > 0:
             # the lam table (uploaded once), the input launch's side outputs the heads read
-            # (partner labels, lam per row) and its {index, shift} log: fixed pointers
-            self.mix_table = torch.from_numpy(mixup_table(self.mixup_alpha, self.data_seed)).to(dev)
+            # (partner labels, lam per row) and its {index, shift} log: fixed pointers.  With
+            # CutMix alone every step pastes and the lam table (all 1) is never read.
+            self.mix_table = (
+                torch.from_numpy(mixup_table(self.mixup_alpha, self.data_seed)).to(dev)
+                if self.mixup_alpha > 0 else torch.ones(MIXUP_TABLE_LEN, device=dev))
             self.labels_b = torch.zeros(N, dtype=torch.int32, device=dev)
             self.mix_lam = torch.ones(N, device=dev)
             self.mix_log = torch.zeros(2, dtype=torch.int32, device=dev)
+        if self.cutmix_alpha > 0:
+            # the box sizes (uploaded once) and the launch's {cut, y0, y1, x0, x1, area, cy, cx}
+            self.cut_table = torch.from_numpy(
+                cutmix_table(self.cutmix_alpha, self.data_seed, H, W)).to(dev)
+            self.cut_log = torch.zeros(8, dtype=torch.int32, device=dev)
         st = spec.stem
         self.stem_out = torch.empty((N, st.ho, st.wo, st.cout), dtype=BF16, device=dev)
         if spec.maxpool:
@@ -666,6 +687,17 @@ class Engine:
             return None
         torch.cuda.synchronize(self.device)
         return float(self.mix_lam[0].item()), int(self.mix_log[1].item())
+
+    def mix_state(self):
+        """The last step's input mixing (synchronises): {"mode": "mixup" | "cutmix", "lam" (the
+        applied one), "shift", "box": (y0, y1, x0, x1) of a CutMix step, else None}.  None:
+        mixup and CutMix off."""
+        if self.mix_log is None:
+            return None
+        lam, shift = self.mixup_state()
+        cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
+        return {"mode": "cutmix" if cut[0] else "mixup", "lam": lam, "shift": shift,
+                "box": tuple(cut[1:5]) if cut[0] else None}
 
     def mix_head_ptrs(self) -> tuple:
         """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""
@@ -923,7 +955,8 @@ class Engine:
         ``top5`` adds `precision_top5` (in-top-k, k = min(5, classes)); without it the
         keys are the ones callers that store every scalar have always got.  With clipping
         on, `grad_norm` and `clip_scale` of the last step are added (clip_state()); with mixup
-        on, `mixup_lam` (mixup_state())."""
+        on, `mixup_lam` (mixup_state()); with mixup or CutMix on, also `mix_mode` (0 mixup,
+        1 CutMix) and, for a CutMix step, `cutmix_area` (mix_state())."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
@@ -946,6 +979,10 @@ class Engine:
             m["grad_norm"], m["clip_scale"] = self.clip_out.cpu().tolist()
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
+            cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
+            m["mix_mode"] = int(cut[0])
+            if cut[0]:
+                m["cutmix_area"] = int(cut[5])
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -84,8 +84,12 @@ class LoggingTensorHook(Hook):
                     f"{ls['lars_trust_median']:.4g}/{ls['lars_trust_max']:.4g}") if ls else ""
             clip = (f", grad norm = {m['grad_norm']:.6g} (scale {m['clip_scale']:.6g})"
                     if "grad_norm" in m else "")   # --clip_grad_norm
+            mix = ""
+            if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
+                mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"
+                       if m["mix_mode"] else f", mixup lam = {m['mixup_lam']:.6g}")
             log(f"INFO:tensorflow:step = {m['global_step']}, loss = {m['cost']:.6f}, "
-                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}{clip}")
+                f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}{clip}{mix}")
 
 
 class StepCounterHook(Hook):

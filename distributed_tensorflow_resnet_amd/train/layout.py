@@ -150,6 +150,30 @@ def check_mixup_alpha(alpha) -> float:
     return alpha
 
 
+def check_cutmix_alpha(alpha) -> float:
+    """--cutmix_alpha as both backends take it: 0 = off, else the (finite, positive)
+    parameter of the Beta(alpha, alpha) the pasted box's area share is drawn from."""
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"cutmix_alpha must be a number, got {alpha!r}") from None
+    if not 0.0 <= alpha < float("inf"):   # negative, inf or NaN
+        raise ValueError(f"cutmix_alpha must be finite and >= 0, got {alpha!r}")
+    return alpha
+
+
+def check_mix_switch_prob(p) -> float:
+    """--mix_switch_prob as both backends take it: the probability, in [0, 1], that a step
+    is a CutMix step when mixup and CutMix are both on."""
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"mix_switch_prob must be a number, got {p!r}") from None
+    if not 0.0 <= p <= 1.0:   # NaN included
+        raise ValueError(f"mix_switch_prob must be in [0, 1], got {p!r}")
+    return p
+
+
 def check_clip_grad_norm(c, optimizer: str) -> float:
     """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
     the norm is measured, the scale is exactly 1); not together with lars, whose trust

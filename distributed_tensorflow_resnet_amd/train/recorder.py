@@ -635,11 +635,14 @@ class StepRecorder:
         modes without a launch of their own get a memset, when there is something to clear."""
         e, plan, spec = self.e, self.plan, self.e.spec
         H, W = spec.image_h, spec.image_w
-        # mixup on: the ops' trailing arguments (lam table, [labels,] labels_b, mix_lam, log)
+        # mixup on: the ops' trailing arguments (lam table, [labels,] labels_b, mix_lam, log);
+        # CutMix on: three more (box-size table, threshold, log)
+        cut = () if e.cut_table is None else (e.cut_table.data_ptr(), e.cut_thresh,
+                                              e.cut_log.data_ptr())
         mix = lambda *labels: (  # noqa: E731
             () if e.mix_table is None else
             (e.mix_table.data_ptr(), e.mix_table.numel(), *labels, e.labels_b.data_ptr(),
-             e.mix_lam.data_ptr(), e.mix_log.data_ptr()))
+             e.mix_lam.data_ptr(), e.mix_log.data_ptr(), *cut))
         if e.input_mode == "cifar_u8":
             plan.cifar_augment(e.img_u8.data_ptr(), e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,
                                e.data_seed, e.gstep.data_ptr(), 1, 0, *zero,

@@ -90,6 +90,26 @@ def _mixup_alpha(v) -> float:
     return f
 
 
+def _cutmix_alpha(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < float("inf"):   # negative, inf or NaN
+        raise argparse.ArgumentTypeError(f"cutmix alpha must be finite and >= 0, got {v!r}")
+    return f
+
+
+def _switch_prob(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f <= 1.0:   # NaN included
+        raise argparse.ArgumentTypeError(f"a switch probability must be in [0, 1], got {v!r}")
+    return f
+
+
 def _lr_rate(v) -> float:
     try:
         f = float(v)
@@ -132,6 +152,15 @@ class FlagParser(argparse.ArgumentParser):
         if getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "synthetic", False):
             self.error("--mixup_alpha cannot be combined with --synthetic: the synthetic "
                        "input has no input launch to mix in")
+        if getattr(ns, "cutmix_alpha", 0.0) > 0 and getattr(ns, "synthetic", False):
+            self.error("--cutmix_alpha cannot be combined with --synthetic: the synthetic "
+                       "input has no input launch to paste in")
+        if hasattr(ns, "mix_switch_prob"):
+            if ns.mix_switch_prob is None:   # not given
+                ns.mix_switch_prob = 0.5
+            elif not (getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "cutmix_alpha", 0.0) > 0):
+                self.error("--mix_switch_prob chooses between mixup and CutMix per step: it needs "
+                           "--mixup_alpha > 0 and --cutmix_alpha > 0")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -243,6 +272,17 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "the sequence).  Training precision is counted against the dominant "
                         "label; evaluation never mixes.  0 = off.  Needs real data (not "
                         "--synthetic); on the GPU, CIFAR or the uint8 ImageNet feed.")
+    p.add_argument("--cutmix_alpha", type=_cutmix_alpha, default=0.0,
+                   help="CutMix (Yun et al. 2019) on the device: a step pastes one box of x' (the "
+                        "batch rotated by the per-step shift) into x and trains against both "
+                        "labels at lam = 1 - box area / image area.  The box's area share is "
+                        "1 - Beta(alpha, alpha), its centre uniform, clipped at the borders; one "
+                        "box per step and rank, a function of the seed and global_step.  0 = off. "
+                        " With --mixup_alpha > 0 too, each step is one or the other "
+                        "(--mix_switch_prob).  Same input requirements as --mixup_alpha.")
+    p.add_argument("--mix_switch_prob", type=_switch_prob, default=None,
+                   help="Probability in [0, 1] that a step is a CutMix step when --mixup_alpha "
+                        "and --cutmix_alpha are both > 0 (default 0.5).  An error otherwise.")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

@@ -862,6 +862,52 @@ static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long 
                                        segs, nseg, bf, lr_out, kPiecewise);
 }
 
+// adam_update_pack: clip = 0 takes grad_scale, else the scale is the device value clip[1];
+// decay_mode "decoupled" | "l2"
+static Launch mk_adam_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, long n,
+                                        float init, long long warm_steps, float warm_from,
+                                        float warm_to, std::vector<long long> bounds,
+                                        std::vector<float> vals, ptr_t gstep, ptr_t start_step,
+                                        float beta1, float beta2, float epsilon,
+                                        float grad_scale, ptr_t clip, std::string decay_mode,
+                                        ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
+                                        ptr_t lr_out, ptr_t adam_out, LrDecayArgs decay) {
+  if ((master | grad | m | v) & 15)
+    throw std::invalid_argument("adam_update_pack: master, grad, m and v must be 16-byte aligned");
+  if (!master || !grad || !m || !v || !segs || !wd_seg || !gstep || !start_step)
+    throw std::invalid_argument("adam_update_pack: null buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("adam_update_pack: n >= 0 and nseg > 0");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    throw std::invalid_argument("adam_update_pack: beta1 and beta2 in [0, 1)");
+  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
+    throw std::invalid_argument("adam_update_pack: epsilon must be positive and finite");
+  if (decay_mode != "decoupled" && decay_mode != "l2")
+    throw std::invalid_argument("adam_update_pack: decay mode '" + decay_mode +
+                                "' (decoupled, l2)");
+  const int decoupled = decay_mode == "decoupled";
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    adam_update_pack(P<float>(master), P<const float>(grad), P<float>(m), P<float>(v), n, sc,
+                     P<const long long>(gstep), P<const long long>(start_step), beta1, beta2,
+                     epsilon, grad_scale, P<const float>(clip), decoupled,
+                     P<const ParamSeg>(segs), nseg, P<const float>(wd_seg), P<bf16>(bf),
+                     P<float>(lr_out), P<float>(adam_out), s);
+  };
+}
+
+static Launch mk_adam_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                  float epsilon, float grad_scale, ptr_t clip,
+                                  std::string decay_mode, ptr_t segs, int nseg, ptr_t wd_seg,
+                                  ptr_t bf, ptr_t lr_out, ptr_t adam_out) {
+  return mk_adam_update_pack_decay(master, grad, m, v, n, init, warm_steps, warm_from, warm_to,
+                                   bounds, vals, gstep, start_step, beta1, beta2, epsilon,
+                                   grad_scale, clip, decay_mode, segs, nseg, wd_seg, bf, lr_out,
+                                   adam_out, kPiecewise);
+}
+
 static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
                             float one_minus_decay, int warm) {
   if ((master | shadow) & 15)
@@ -1621,6 +1667,8 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "clip_scale", mk_clip_scale);
   def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack);
   def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack_decay);
+  def_op(m, plan, "adam_update_pack", mk_adam_update_pack);
+  def_op(m, plan, "adam_update_pack", mk_adam_update_pack_decay);
   def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);

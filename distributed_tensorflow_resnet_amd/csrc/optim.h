@@ -90,6 +90,18 @@ void sgd_clip_update_pack(float* master, const float* grad, float* mom, long n,
                           const LrSchedule& s, const long long* gstep, float momentum, float wd,
                           const float* clip, int use_momentum, const ParamSeg* segs, int nseg,
                           bf16* bf, float* lr_out, hipStream_t st);
+// AdamW (adam.hip) in one launch of sgd_update_pack's shape: m (the momentum buffer) and v
+// are the two moments, t = *gstep - *start_step + 1 (both only read), the gradient's scale
+// is grad_scale or, clip non-null, the device value clip[1]; wd_seg[nseg] is the decay of
+// each segment, applied to the gradient (decoupled = 0: l2) or to the weight at the rate
+// lr * wd_seg (decoupled = 1).  adam_out (optional): {lr, alpha, (float)t}.  master, grad,
+// m and v must be 16-byte aligned; 0 <= beta < 1 and epsilon > 0.
+void adam_update_pack(float* master, const float* grad, float* m, float* v, long n,
+                      const LrSchedule& s, const long long* gstep, const long long* start_step,
+                      float beta1, float beta2, float epsilon, float grad_scale,
+                      const float* clip, int decoupled, const ParamSeg* segs, int nseg,
+                      const float* wd_seg, bf16* bf, float* lr_out, float* adam_out,
+                      hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

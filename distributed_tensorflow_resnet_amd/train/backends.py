@@ -23,8 +23,8 @@ from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
-from ..utils.checkpoint import state_to_tf, tf_to_state
-from .layout import (check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
+from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_state
+from .layout import (OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha)
 
 
@@ -79,14 +79,25 @@ class GPUBackend:
 
     def state_tensors(self):
         self.check_health()
-        return state_to_tf(self.engine.params, self.engine.mom, self.global_step,
-                           ema=self.engine.ema)
+        eng = self.engine
+        adam = None
+        if eng.adam:
+            adam = {"v": eng.adam_v, "start_step": int(eng.adam_start.item()),
+                    "beta1": eng.adam_beta1, "beta2": eng.adam_beta2}
+        return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam)
 
     def load_state(self, tensors):
         eng = self.engine
-        gs = tf_to_state(tensors, eng.params, eng.mom, strict=True, ema=eng.ema)
+        # adamw: the momentum buffer is the first moment, loaded from the Adam slots
+        gs = tf_to_state(tensors, eng.params, None if eng.adam else eng.mom, strict=True,
+                         ema=eng.ema)
+        if eng.adam:
+            eng.set_adam_start(tf_to_adam(tensors, eng.params, eng.mom, eng.adam_v))
         eng.sync_from_params(ema_loaded=True)
         self._host_step = gs
+
+    def adam_state(self):
+        return self.engine.adam_state()
 
     @property
     def ema_decay(self) -> float:
@@ -122,7 +133,10 @@ class CPUBackend:
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
                  clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0, data_seed: int = 1234,
-                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5):
+                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5,
+                 adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
+                 adam_decay_skip: str = "none"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -171,8 +185,21 @@ class CPUBackend:
         self.last_logits = None    # the last step's logits (detached)
         self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
-        if optimizer not in ("mom", "sgd", "lars"):
-            raise ValueError(f"optimizer must be mom, sgd or lars, got {optimizer!r}")
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be mom, sgd, lars or adamw, got {optimizer!r}")
+        # adamw, csrc/adam.hip's expressions in fp32 torch: the first moment in `mom`, the
+        # second in `adam_v`; t counts from adam_start
+        self.adam = optimizer == "adamw"
+        self.adam_beta1, self.adam_beta2, self.adam_epsilon = check_adam(
+            adam_beta1, adam_beta2, adam_epsilon, adam_decay, adam_decay_skip)
+        self.adam_decay = adam_decay
+        self.adam_v, self.adam_start, self._adam_state = None, 0, None
+        if self.adam:
+            self.adam_v = torch.zeros(self.store.n_train)
+            wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
+                                      adam_decay_skip)
+            self.adam_wd = torch.repeat_interleave(
+                torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
         if lars_skip not in ("vectors", "none"):
             raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
         self.lars = optimizer == "lars"
@@ -247,12 +274,16 @@ class CPUBackend:
                 self.dist.all_reduce_sum(g)
         lr = self.sched.at(self.step_count)
         with torch.no_grad():
-            if self.clip_grad_norm > 0:
+            if self.adam:
+                gp = None   # (its decay is per tensor and per mode: _adam_update)
+            elif self.clip_grad_norm > 0:
                 # after the all-reduce: every rank forms the same norm from the same bits
                 gp = self._clip_scale(g) * g + self.wd * master
             else:
                 gp = g + self.wd * master
-            if self.lars:
+            if self.adam:
+                self._adam_update(master, g, lr)
+            elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
             elif self.use_momentum:
@@ -277,6 +308,30 @@ class CPUBackend:
                       "cost": loss_sum / n + self.wd * l2, "precision": correct / n, "lr": lr,
                       "l2": l2}
         self._last_top5 = top5 / n
+
+    def _adam_update(self, master, g, lr):
+        """csrc/adam.hip's update in fp32 torch; alpha in fp64 from the step, rounded once."""
+        f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
+        b1, b2, eps = f(self.adam_beta1), f(self.adam_beta2), f(self.adam_epsilon)
+        omb1, omb2 = f(1.0 - float(b1)), f(1.0 - float(b2))
+        lr32 = f(lr)
+        t = max(1, self.step_count - self.adam_start + 1)
+        alpha = f(adam_alpha(float(lr32), t, self.adam_beta1, self.adam_beta2))
+        w, wd = master, self.adam_wd
+        gp = g * self._clip_scale(g) if self.clip_grad_norm > 0 else g.clone()
+        if self.adam_decay == "l2":
+            gp = gp + wd * w
+        dec = (lr32 * wd) * w   # decoupled: of the old w
+        self.mom.mul_(b1).add_(omb1 * gp)
+        self.adam_v.mul_(b2).add_(omb2 * (gp * gp))
+        w.sub_(alpha * (self.mom / (torch.sqrt(self.adam_v) + eps)))
+        if self.adam_decay == "decoupled":
+            w.sub_(dec)
+        self._adam_state = (t, float(alpha))
+
+    def adam_state(self):
+        """(t, alpha) of the last step (None: not adamw, or no step yet)."""
+        return self._adam_state
 
     def _ema_update(self):
         """shadow -= om * (shadow - master), k = the steps completed (csrc/ema.hip)."""
@@ -359,6 +414,8 @@ class CPUBackend:
             m["precision_top5"] = self._last_top5
         if self._clip_state is not None:
             m["grad_norm"], m["clip_scale"] = self._clip_state
+        if self._adam_state is not None:
+            m["adam_alpha"] = self._adam_state[1]
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -373,21 +430,29 @@ class CPUBackend:
         pass
 
     def state_tensors(self):
-        return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema)
+        adam = None
+        if self.adam:
+            adam = {"v": self.adam_v, "start_step": self.adam_start, "beta1": self.adam_beta1,
+                    "beta2": self.adam_beta2}
+        return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam)
 
     def load_state(self, tensors):
         with torch.no_grad():
-            self.step_count = tf_to_state(tensors, self.store, self.mom, ema=self.ema)
+            self.step_count = tf_to_state(tensors, self.store, None if self.adam else self.mom,
+                                          ema=self.ema)
+            if self.adam:
+                self.adam_start = tf_to_adam(tensors, self.store, self.mom, self.adam_v)
 
     def broadcast_parameters(self, src: int = 0):
         if self.dist is not None and self.world > 1:
             with torch.no_grad():
                 for t in (self.store.master, self.store.stats, self.mom) + (
-                        (self.ema,) if self.ema is not None else ()):
+                        (self.ema,) if self.ema is not None else ()) + (
+                        (self.adam_v,) if self.adam else ()):
                     self.dist.broadcast(t.data, src)
-                s = torch.tensor([self.step_count])
+                s = torch.tensor([self.step_count, self.adam_start])
                 self.dist.broadcast(s, src)
-                self.step_count = int(s.item())
+                self.step_count, self.adam_start = (int(x) for x in s.tolist())
 
     # -------------------------------------------------------------- eval
     def evaluate_batch(self, images, labels):
@@ -412,11 +477,15 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  lars_skip: str = "vectors", label_smoothing: float = 0.0,
                  ema_decay: float = 0.0, ema_warmup: bool = True, clip_grad_norm: float = 0.0,
                  mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
-                 mix_switch_prob: float = 0.5):
+                 mix_switch_prob: float = 0.5, adam_beta1: float = 0.9,
+                 adam_beta2: float = 0.999, adam_epsilon: float = 1e-8,
+                 adam_decay: str = "decoupled", adam_decay_skip: str = "none"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
         device = "gpu" if torch.cuda.is_available() else "cpu"
+    adam = dict(adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
+                adam_decay=adam_decay, adam_decay_skip=adam_decay_skip)
     if device == "gpu":
         from .engine import Engine
 
@@ -432,7 +501,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      label_smoothing=label_smoothing, ema_decay=ema_decay,
                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
                      mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha,
-                     mix_switch_prob=mix_switch_prob)
+                     mix_switch_prob=mix_switch_prob, **adam)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -443,4 +512,4 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       label_smoothing=label_smoothing, ema_decay=ema_decay,
                       ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
                       mixup_alpha=mixup_alpha, data_seed=data_seed, cutmix_alpha=cutmix_alpha,
-                      mix_switch_prob=mix_switch_prob)
+                      mix_switch_prob=mix_switch_prob, **adam)

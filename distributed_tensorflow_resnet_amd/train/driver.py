@@ -226,7 +226,10 @@ def main(argv=None, kind: str = "cifar") -> int:
                            ema_decay=flags.ema_decay, ema_warmup=flags.ema_warmup,
                            clip_grad_norm=flags.clip_grad_norm, mixup_alpha=flags.mixup_alpha,
                            cutmix_alpha=flags.cutmix_alpha,
-                           mix_switch_prob=flags.mix_switch_prob)
+                           mix_switch_prob=flags.mix_switch_prob,
+                           adam_beta1=flags.adam_beta1, adam_beta2=flags.adam_beta2,
+                           adam_epsilon=flags.adam_epsilon, adam_decay=flags.adam_decay,
+                           adam_decay_skip=flags.adam_decay_skip)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

@@ -51,7 +51,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob,
-                     lars_trust_summary, opt_tile, param_segments, sgd_tiles_work)
+                     lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
+                     OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -126,7 +127,10 @@ class Engine:
                  lars_epsilon: float = 0.0, lars_skip: str = "vectors",
                  label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
                  clip_grad_norm: float = 0.0, mixup_alpha: float = 0.0,
-                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5):
+                 cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5,
+                 adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
+                 adam_decay_skip: str = "none"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -140,8 +144,8 @@ class Engine:
         self.global_batch = global_batch or batch_size * self.world
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
-        if optimizer not in ("mom", "sgd", "lars"):
-            raise ValueError(f"optimizer must be mom, sgd or lars, got {optimizer!r}")
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be mom, sgd, lars or adamw, got {optimizer!r}")
         if lars_skip not in LARS_SKIPS:
             raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
         # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
@@ -150,6 +154,14 @@ class Engine:
         self.lars_eeta, self.lars_epsilon = float(lars_eeta), float(lars_epsilon)
         self.lars_skip = lars_skip
         self.use_momentum = optimizer in ("mom", "lars")
+        # adamw: Adam in tf.train.AdamOptimizer's form with decoupled (or l2) weight decay, one
+        # launch on the generic optimizer path (csrc/adam.hip).  The first moment lives in the
+        # momentum buffer; the second moment, the start-step slot and the {lr, alpha, t} slot
+        # exist only for adamw
+        self.adam = optimizer == "adamw"
+        self.adam_beta1, self.adam_beta2, self.adam_epsilon = check_adam(
+            adam_beta1, adam_beta2, adam_epsilon, adam_decay, adam_decay_skip)
+        self.adam_decay, self.adam_decay_skip = adam_decay, adam_decay_skip
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -257,6 +269,13 @@ class Engine:
         self.grad = torch.zeros(self.params.n_train, device=dev)
         self.mom = torch.zeros(self.params.n_train, device=dev)
         self.ema = self.params.master.detach().clone() if self.ema_decay > 0 else None
+        self.adam_v = self.adam_start = self.adam_out = self.adam_wd = None
+        if self.adam:
+            self.adam_v = torch.zeros(self.params.n_train, device=dev)
+            # the step the moments started at (t = global_step - start + 1): kernels only read
+            # it; the host writes it here and on restore
+            self.adam_start = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.adam_out = torch.zeros(3, device=dev)   # {lr, alpha, t} of the last step
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
         # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
         self.scalars = torch.zeros(8, device=dev)
@@ -306,6 +325,9 @@ class Engine:
             self.opt_fused = False
             self.opt_fused_reason = ("optimizer lars: the norms are taken over the complete "
                                      "fp32 gradient, before the update")
+        if self.adam and self.opt_fused:   # (before clipping: with both, adamw is the reason)
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_ADAM_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -409,6 +431,10 @@ class Engine:
             self.lars_blk = torch.tensor(blk, dtype=torch.int32, device=dev)
             self.lars_part = torch.zeros(2 * len(blk), dtype=torch.float64, device=dev)
             self.lars_out = torch.ones(3, self.nseg, device=dev)
+        if self.adam:
+            # the per-segment decay the kernel reads, as the LARS kernel reads trust[]
+            self.adam_wd = torch.from_numpy(adam_decay_table(
+                [s.shape for s in ps.train_slots], self.wd, self.adam_decay_skip)).to(dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:
             # chunk partials and the {norm, scale} slot: fixed pointers
@@ -679,6 +705,23 @@ class Engine:
         torch.cuda.synchronize(self.device)
         norm, scale = self.clip_out.cpu().tolist()
         return norm, scale
+
+    def adam_state(self):
+        """(t, alpha) of the last step's adamw update: the step count of the bias correction
+        (global_step - adam_start_step + 1 when the step began; read back from an fp32 slot,
+        so exact below 2^24) and the bias-corrected rate lr * sqrt(1 - b2^t) / (1 - b1^t)
+        (synchronises).  None unless the optimizer is adamw."""
+        if not self.adam:
+            return None
+        torch.cuda.synchronize(self.device)
+        _, alpha, t = self.adam_out.cpu().tolist()
+        return int(t), alpha
+
+    def set_adam_start(self, step: int):
+        """The step the moments count from (a restore's: the checkpoint's adam_start_step, or
+        global_step when the moments restart from zero)."""
+        if self.adam:
+            self.adam_start.fill_(int(step))
 
     def mixup_state(self):
         """(lam, shift) of the last step's mixup: batch position n was blended with position
@@ -977,6 +1020,8 @@ class Engine:
             m["precision_top5"] = top5_sum / n
         if self.clip_out is not None:
             m["grad_norm"], m["clip_scale"] = self.clip_out.cpu().tolist()
+        if self.adam:
+            m["adam_alpha"] = float(self.adam_out[1].item())
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
@@ -996,6 +1041,8 @@ class Engine:
     def _replicated(self):
         """The state every rank holds a copy of (the shadows too when EMA is on)."""
         ts = (self.params.master, self.params.stats, self.mom, self.gstep)
+        if self.adam:
+            ts += (self.adam_v, self.adam_start)
         return ts + (self.ema,) if self.ema is not None else ts
 
     def broadcast_parameters(self, src: int = 0):

@@ -84,6 +84,8 @@ class LoggingTensorHook(Hook):
                     f"{ls['lars_trust_median']:.4g}/{ls['lars_trust_max']:.4g}") if ls else ""
             clip = (f", grad norm = {m['grad_norm']:.6g} (scale {m['clip_scale']:.6g})"
                     if "grad_norm" in m else "")   # --clip_grad_norm
+            if "adam_alpha" in m:   # --optimizer adamw
+                clip += f", adam alpha = {m['adam_alpha']:.6g}"
             mix = ""
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"

@@ -134,6 +134,62 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
+OPTIMIZERS = ("mom", "sgd", "lars", "adamw")
+ADAM_DECAYS = ("decoupled", "l2")
+ADAM_DECAY_SKIPS = ("none", "vectors")
+OPT_FUSED_ADAM_REASON = ("optimizer adamw: the one-launch optimizer is SGD-momentum; adamw takes "
+                         "the generic optimizer launches")
+
+
+def check_adam(beta1, beta2, epsilon, decay: str = "decoupled", decay_skip: str = "none"):
+    """The adamw flags as both backends take them: (beta1, beta2, epsilon) as floats.  The
+    betas are in [0, 1); epsilon > 0 (with 0 an element whose gradient is zero would be
+    0 / 0) and finite."""
+    try:
+        b1, b2, eps = float(beta1), float(beta2), float(epsilon)
+    except (TypeError, ValueError):
+        raise ValueError(f"adam_beta1, adam_beta2 and adam_epsilon must be numbers, got "
+                         f"{beta1!r}, {beta2!r}, {epsilon!r}") from None
+    for name, b in (("adam_beta1", b1), ("adam_beta2", b2)):
+        if not 0.0 <= b < 1.0:   # NaN included
+            raise ValueError(f"{name} must be in [0, 1), got {b!r}")
+    # (as the kernel's float argument: a positive value fp32 rounds to 0 is no epsilon)
+    if not 0.0 < float(np.float32(eps)) < float("inf"):
+        raise ValueError(f"adam_epsilon must be positive (and finite in fp32), got {eps!r}")
+    if float(np.float32(b1)) >= 1.0 or float(np.float32(b2)) >= 1.0:
+        raise ValueError(f"adam_beta1 and adam_beta2 must be below 1 in fp32, got {b1!r}, {b2!r}")
+    if decay not in ADAM_DECAYS:
+        raise ValueError(f"adam_decay must be one of {ADAM_DECAYS}, got {decay!r}")
+    if decay_skip not in ADAM_DECAY_SKIPS:
+        raise ValueError(f"adam_decay_skip must be one of {ADAM_DECAY_SKIPS}, got {decay_skip!r}")
+    return b1, b2, eps
+
+
+def adam_decay_table(shapes, wd: float, decay_skip: str = "none"):
+    """wd_seg of adam_update_pack (csrc/adam.hip): the fp32 weight decay of each parameter
+    segment, in slot order.  `shapes`: the trainables' shapes.  'none' decays every
+    trainable (this project's rule); 'vectors' gives every rank-1 tensor (BN gamma / beta,
+    the dense bias) 0."""
+    if decay_skip not in ADAM_DECAY_SKIPS:
+        raise ValueError(f"adam_decay_skip must be one of {ADAM_DECAY_SKIPS}, got {decay_skip!r}")
+    return np.array([0.0 if decay_skip == "vectors" and len(s) == 1 else wd for s in shapes],
+                    dtype=np.float32)
+
+
+def adam_alpha(lr: float, t: int, beta1: float, beta2: float) -> float:
+    """Host mirror of the device's bias-corrected rate (csrc/adam.hip): lr * sqrt(1 - b2^t) /
+    (1 - b1^t) in fp64 from the fp32 coefficients, 1 - b^t as -expm1(t * log(b)), rounded to
+    fp32 once."""
+    import math
+
+    def om_pow(b):
+        b = float(np.float32(b))
+        return 1.0 if b == 0.0 else -math.expm1(t * math.log(b))
+
+    t = max(1, int(t))
+    return float(np.float32(float(np.float32(lr)) * math.sqrt(om_pow(beta2)) / om_pow(beta1)))
+
+
 # input modes whose step has an input launch mixup can be built into
 MIXUP_INPUT_MODES = ("cifar_u8", "cifar_resident", "imagenet_u8")
 

@@ -580,6 +580,30 @@ class StepRecorder:
                                       e.gstep.data_ptr(), e.momentum, e.wd, 1.0,
                                       e.segs.data_ptr(), e.nseg, lo, e.wbf.data_ptr(), sp + 8,
                                       *e.sched.extra_launch_args())
+            elif e.adam:
+                # one launch (csrc/adam.hip); with clipping the norm launches go in front and
+                # the update reads the scale from the device slot, as sgd_clip_update_pack does
+                clip, co = e.clip_grad_norm > 0, 0
+                i0 = plan.size()
+                if clip:
+                    co = e.clip_out.data_ptr()
+                    plan.grad_sqnorm(grad, e.params.n_train, e.clip_part.data_ptr())
+                    plan.clip_scale(e.clip_part.data_ptr(), e.clip_chunks,
+                                    float(np.float32(e.clip_grad_norm)), co)
+                i1 = plan.adam_update_pack(master, grad, mom, e.adam_v.data_ptr(),
+                                           e.params.n_train, *e.sched.launch_args(),
+                                           e.gstep.data_ptr(), e.adam_start.data_ptr(),
+                                           e.adam_beta1, e.adam_beta2, e.adam_epsilon, 1.0, co,
+                                           e.adam_decay, e.segs.data_ptr(), e.nseg,
+                                           e.adam_wd.data_ptr(), e.wbf.data_ptr(), sp + 8,
+                                           e.adam_out.data_ptr(), *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    if clip:
+                        out.op_buffers[i0] = gb | {"clip"}
+                        out.op_buffers[i0 + 1] = {"clip"}
+                    out.op_buffers[i1] = (gb | {f"param:{b}" for b in range(len(e.buckets))}
+                                          | {"adam", "lr", "gstep"} | ({"clip"} if clip else set()))
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

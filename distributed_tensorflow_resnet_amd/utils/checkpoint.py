@@ -5,7 +5,9 @@ Variables saved exactly as the reference's MonitoredTrainingSession did
 under its TF name (HWIO conv kernels, BN gamma/beta, dense kernel/bias), its
 ``<name>/Momentum`` optimizer slot, the BN moving statistics and the int64
 ``global_step``; a run with ``--ema_decay`` adds ``<name>/ExponentialMovingAverage`` per
-trainable (tf.train.ExponentialMovingAverage's shadow variables).  ``max_to_keep``
+trainable (tf.train.ExponentialMovingAverage's shadow variables); a run with ``--optimizer
+adamw`` saves ``<name>/Adam`` and ``<name>/Adam_1`` in place of ``<name>/Momentum``, plus
+``beta1_power``, ``beta2_power`` and ``adam_start_step``.  ``max_to_keep``
 = 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
@@ -23,26 +25,77 @@ from . import tensor_bundle as tb
 EMA_SUFFIX = "/ExponentialMovingAverage"   # tf.train.ExponentialMovingAverage's shadow name
 
 
+ADAM_M_SUFFIX, ADAM_V_SUFFIX = "/Adam", "/Adam_1"   # tf.train.AdamOptimizer's slot names
+ADAM_START = "adam_start_step"                     # ours: the step the moments count from
+
+
+def adam_beta_powers(t_done: int, beta1: float, beta2: float):
+    """TF 1.12's beta1_power / beta2_power variables after t_done Adam steps: b^(t_done + 1)
+    (they start at b and are multiplied by b after every step), from the fp32 betas in fp64,
+    as fp32."""
+    return (np.float32(float(np.float32(beta1)) ** (int(t_done) + 1)),
+            np.float32(float(np.float32(beta2)) ** (int(t_done) + 1)))
+
+
 def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
-                ema: torch.Tensor | None = None) -> dict[str, np.ndarray]:
+                ema: torch.Tensor | None = None, adam: dict | None = None) -> dict[str, np.ndarray]:
     """ParamStore (+flat momentum, +flat EMA shadows, in the same layout) -> {TF name: array}.
     ``ema`` adds ``<name>/ExponentialMovingAverage`` per trainable; without it the entries
-    are exactly the reference's."""
+    are exactly the reference's.  ``adam`` (an adamw run: {"v": flat second moment,
+    "start_step", "beta1", "beta2"}): `momentum` is the first moment and goes out as
+    ``<name>/Adam``, v as ``<name>/Adam_1`` (TF's slot names), no ``/Momentum``; plus the fp32
+    scalars beta1_power / beta2_power (TF 1.12's variables after global_step - start_step
+    Adam steps) and the int64 ``adam_start_step``, which restore goes by."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
     mom = momentum.detach().float().cpu().numpy() if momentum is not None else None
     sh = ema.detach().float().cpu().numpy() if ema is not None else None
+    v = adam["v"].detach().float().cpu().numpy() if adam is not None else None
+    m_suffix = ADAM_M_SUFFIX if adam is not None else "/Momentum"
     for s in store.train_slots:
         out[s.name] = master[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if mom is not None:
-            out[f"{s.name}/Momentum"] = mom[s.offset:s.offset + s.numel].reshape(s.shape).copy()
+            out[s.name + m_suffix] = mom[s.offset:s.offset + s.numel].reshape(s.shape).copy()
+        if v is not None:
+            out[s.name + ADAM_V_SUFFIX] = v[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if sh is not None:
             out[s.name + EMA_SUFFIX] = sh[s.offset:s.offset + s.numel].reshape(s.shape).copy()
     for s in store.stat_slots:
         out[s.name] = stats[s.offset:s.offset + s.numel].reshape(s.shape).copy()
     out["global_step"] = np.array(int(global_step), dtype=np.int64)
+    if adam is not None:
+        start = int(adam["start_step"])
+        p1, p2 = adam_beta_powers(int(global_step) - start, adam["beta1"], adam["beta2"])
+        out["beta1_power"], out["beta2_power"] = np.array(p1), np.array(p2)
+        out[ADAM_START] = np.array(start, dtype=np.int64)
     return out
+
+
+def tf_to_adam(tensors: dict, store, m: torch.Tensor, v: torch.Tensor) -> int:
+    """Load the two Adam moments of an adamw run from {TF name: array}; returns the step the
+    bias correction counts from.  With every ``<name>/Adam`` and ``<name>/Adam_1`` present:
+    both are loaded and the start step is the checkpoint's ``adam_start_step`` (0 without
+    that entry: a file TF wrote).  Otherwise (e.g. a `mom` checkpoint, whose ``/Momentum`` is
+    ignored): both moments are zero and the start step is the checkpoint's global_step, so
+    the bias correction restarts with the moments; one log line says so."""
+    gs = int(np.asarray(tensors.get("global_step", 0)))
+    absent = [s.name for s in store.train_slots
+              if s.name + ADAM_M_SUFFIX not in tensors or s.name + ADAM_V_SUFFIX not in tensors]
+    if absent:
+        print(f"INFO:tensorflow:checkpoint has no Adam slots for {len(absent)} of "
+              f"{len(store.train_slots)} variables (e.g. {absent[0] + ADAM_M_SUFFIX}): both moments "
+              f"start from zero and the bias correction restarts at step {gs}", flush=True)
+        m.data.zero_()
+        v.data.zero_()
+        return gs
+    for buf, suffix in ((m, ADAM_M_SUFFIX), (v, ADAM_V_SUFFIX)):
+        for s in store.train_slots:
+            a = np.asarray(tensors[s.name + suffix], dtype=np.float32).reshape(-1)
+            if a.size != s.numel:
+                raise ValueError(f"{s.name + suffix}: {a.size} elements, expected {s.numel}")
+            buf.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
+    return int(np.asarray(tensors.get(ADAM_START, 0)))
 
 
 def ema_weights(tensors: dict, store) -> dict:

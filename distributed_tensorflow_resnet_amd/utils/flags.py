@@ -12,6 +12,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --resident_data    CIFAR split resident on the GPU, shuffled on the device
   --ema_decay        device-side EMA of the weights, checkpointed; --eval_ema scores it
   --clip_grad_norm   clip the gradient by its global norm on the device (inf: only log it)
+  --optimizer adamw  Adam with decoupled (or l2) weight decay in one device launch:
+                     --adam_beta1/_beta2/_epsilon, --adam_decay, --adam_decay_skip
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -67,6 +69,26 @@ def _ema_decay(v) -> float:
         raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
     if not 0.0 <= f < 1.0:
         raise argparse.ArgumentTypeError(f"EMA decay must be in [0, 1), got {v!r}")
+    return f
+
+
+def _adam_beta(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < 1.0:   # NaN included
+        raise argparse.ArgumentTypeError(f"an Adam beta must be in [0, 1), got {v!r}")
+    return f
+
+
+def _adam_epsilon(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 < f < float("inf"):   # zero, negative, inf or NaN
+        raise argparse.ArgumentTypeError(f"the Adam epsilon must be positive and finite, got {v!r}")
     return f
 
 
@@ -149,6 +171,14 @@ class FlagParser(argparse.ArgumentParser):
         if getattr(ns, "clip_grad_norm", 0.0) > 0 and getattr(ns, "optimizer", "") == "lars":
             self.error("--clip_grad_norm cannot be combined with --optimizer lars: the trust "
                        "ratio already normalises by the gradient norm")
+        if hasattr(ns, "adam_beta1"):
+            from ..train.layout import check_adam
+
+            try:   # (the fp32 values the kernel gets: a beta that rounds to 1, an epsilon to 0)
+                check_adam(ns.adam_beta1, ns.adam_beta2, ns.adam_epsilon, ns.adam_decay,
+                           ns.adam_decay_skip)
+            except ValueError as e:
+                self.error(str(e))
         if getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "synthetic", False):
             self.error("--mixup_alpha cannot be combined with --synthetic: the synthetic "
                        "input has no input launch to mix in")
@@ -235,10 +265,28 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars"),
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw"),
                    help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
                         "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
-                        "epsilon) (layer-wise adaptive rate scaling, for large global batches).")
+                        "epsilon) (layer-wise adaptive rate scaling, for large global batches).  "
+                        "adamw: Adam (tf.train.AdamOptimizer's form) with decoupled weight "
+                        "decay; the presets' learning rates are SGD rates, so set --lr_peak "
+                        "(e.g. 1e-3) or --lr_value_scale with it.")
+    p.add_argument("--adam_beta1", type=_adam_beta, default=0.9,
+                   help="adamw: decay of the first moment, in [0, 1).")
+    p.add_argument("--adam_beta2", type=_adam_beta, default=0.999,
+                   help="adamw: decay of the second moment, in [0, 1).")
+    p.add_argument("--adam_epsilon", type=_adam_epsilon, default=1e-8,
+                   help="adamw: added to sqrt(v), outside the bias correction (TF's epsilon "
+                        "hat); > 0.")
+    p.add_argument("--adam_decay", default="decoupled", choices=("decoupled", "l2"),
+                   help="adamw: 'decoupled' = w -= lr * wd * w beside the Adam step (Loshchilov "
+                        "& Hutter), 'l2' = wd * w added to the gradient (plain Adam on the "
+                        "reference's cost).")
+    p.add_argument("--adam_decay_skip", default="none", choices=("none", "vectors"),
+                   help="adamw: tensors without weight decay: 'none' = every trainable is "
+                        "decayed (this project's rule), 'vectors' = every rank-1 tensor (BN "
+                        "gamma / beta, the dense bias) is not.")
     p.add_argument("--lars_eeta", type=float, default=0.001,
                    help="LARS trust coefficient.")
     p.add_argument("--lars_epsilon", type=float, default=0.0,

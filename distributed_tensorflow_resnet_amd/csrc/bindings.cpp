@@ -908,6 +908,84 @@ static Launch mk_adam_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, lo
                                    adam_out, kPiecewise);
 }
 
+// The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
+static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
+                      const std::string& decay_mode) {
+  const std::string o(op);
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    throw std::invalid_argument(o + ": beta1 and beta2 in [0, 1)");
+  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
+    throw std::invalid_argument(o + ": epsilon must be positive and finite");
+  if (decay_mode != "decoupled" && decay_mode != "l2")
+    throw std::invalid_argument(o + ": decay mode '" + decay_mode + "' (decoupled, l2)");
+  return decay_mode == "decoupled";
+}
+
+static Launch mk_lamb_moments_norms(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, ptr_t gstep,
+                                    ptr_t start_step, float beta1, float beta2, float epsilon,
+                                    float grad_scale, ptr_t clip, std::string decay_mode,
+                                    ptr_t segs, ptr_t lsegs, ptr_t blk_seg, int nblocks,
+                                    ptr_t wd_seg, ptr_t part) {
+  if ((master | grad | m | v) & 15)
+    throw std::invalid_argument(
+        "lamb_moments_norms: master, grad, m and v must be 16-byte aligned");
+  if (!master || !grad || !m || !v || !segs || !lsegs || !blk_seg || !wd_seg || !part ||
+      !gstep || !start_step)
+    throw std::invalid_argument("lamb_moments_norms: null buffer");
+  if (nblocks < 0) throw std::invalid_argument("lamb_moments_norms: nblocks >= 0");
+  const int decoupled = lamb_check("lamb_moments_norms", beta1, beta2, epsilon, decay_mode);
+  return [=](hipStream_t s) {
+    lamb_moments_norms(P<const float>(master), P<const float>(grad), P<float>(m), P<float>(v),
+                       P<const long long>(gstep), P<const long long>(start_step), beta1, beta2,
+                       epsilon, grad_scale, P<const float>(clip), decoupled,
+                       P<const ParamSeg>(segs), P<const LarsSeg>(lsegs), P<const int>(blk_seg),
+                       nblocks, P<const float>(wd_seg), P<double>(part), s);
+  };
+}
+
+static Launch mk_lamb_trust(ptr_t part, ptr_t lsegs, int nseg, ptr_t trust, ptr_t wn, ptr_t un) {
+  if (!part || !lsegs || !trust || !wn || !un)
+    throw std::invalid_argument("lamb_trust: null buffer");
+  return [=](hipStream_t s) {
+    lamb_trust(P<const double>(part), P<const LarsSeg>(lsegs), nseg, P<float>(trust),
+               P<float>(wn), P<float>(un), s);
+  };
+}
+
+static Launch mk_lamb_update_pack_decay(ptr_t master, ptr_t m, ptr_t v, long n, float init,
+                                        long long warm_steps, float warm_from, float warm_to,
+                                        std::vector<long long> bounds, std::vector<float> vals,
+                                        ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                        float epsilon, std::string decay_mode, ptr_t segs,
+                                        int nseg, ptr_t wd_seg, ptr_t trust, ptr_t bf,
+                                        ptr_t lr_out, ptr_t adam_out, LrDecayArgs decay) {
+  if ((master | m | v) & 15)
+    throw std::invalid_argument("lamb_update_pack: master, m and v must be 16-byte aligned");
+  if (!master || !m || !v || !segs || !wd_seg || !trust || !gstep || !start_step)
+    throw std::invalid_argument("lamb_update_pack: null buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("lamb_update_pack: n >= 0 and nseg > 0");
+  const int decoupled = lamb_check("lamb_update_pack", beta1, beta2, epsilon, decay_mode);
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    lamb_update_pack(P<float>(master), P<const float>(m), P<const float>(v), n, sc,
+                     P<const long long>(gstep), P<const long long>(start_step), beta1, beta2,
+                     epsilon, decoupled, P<const ParamSeg>(segs), nseg, P<const float>(wd_seg),
+                     P<const float>(trust), P<bf16>(bf), P<float>(lr_out), P<float>(adam_out), s);
+  };
+}
+
+static Launch mk_lamb_update_pack(ptr_t master, ptr_t m, ptr_t v, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                  float epsilon, std::string decay_mode, ptr_t segs, int nseg,
+                                  ptr_t wd_seg, ptr_t trust, ptr_t bf, ptr_t lr_out,
+                                  ptr_t adam_out) {
+  return mk_lamb_update_pack_decay(master, m, v, n, init, warm_steps, warm_from, warm_to, bounds,
+                                   vals, gstep, start_step, beta1, beta2, epsilon, decay_mode,
+                                   segs, nseg, wd_seg, trust, bf, lr_out, adam_out, kPiecewise);
+}
+
 static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
                             float one_minus_decay, int warm) {
   if ((master | shadow) & 15)
@@ -1669,6 +1747,10 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack_decay);
   def_op(m, plan, "adam_update_pack", mk_adam_update_pack);
   def_op(m, plan, "adam_update_pack", mk_adam_update_pack_decay);
+  def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
+  def_op(m, plan, "lamb_trust", mk_lamb_trust);
+  def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);
+  def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack_decay);
   def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);

@@ -102,6 +102,28 @@ void adam_update_pack(float* master, const float* grad, float* m, float* v, long
                       const float* clip, int decoupled, const ParamSeg* segs, int nseg,
                       const float* wd_seg, bf16* bf, float* lr_out, float* adam_out,
                       hipStream_t st);
+// LAMB (lamb.hip): adamw's direction u = m' k1 / (sqrt(v' k2) + epsilon) (+ wd_seg w,
+// decoupled) at the per-segment rate lr * trust, trust = ||w|| / ||u|| -- three launches,
+// with ohwi_pack after them.  Arguments mean what adam_update_pack's mean; the chunk table
+// (lsegs, blk_seg, nblocks) is LARS's.  lamb_moments_norms updates m and v in place and writes
+// part[b] = (sum w^2, sum u^2) over chunk b (fp64); master, grad, m and v 16-byte aligned.
+void lamb_moments_norms(const float* master, const float* grad, float* m, float* v,
+                        const long long* gstep, const long long* start_step, float beta1,
+                        float beta2, float epsilon, float grad_scale, const float* clip,
+                        int decoupled, const ParamSeg* segs, const LarsSeg* lsegs,
+                        const int* blk_seg, int nblocks, const float* wd_seg, double* part,
+                        hipStream_t st);
+// Per segment: wn = ||w||, un = ||u|| from its chunks' partials in chunk order; trust =
+// wn / un, or exactly 1 for a skipped segment or a norm that is not > 0.
+void lamb_trust(const double* part, const LarsSeg* lsegs, int nseg, float* trust, float* wn,
+                float* un, hipStream_t st);
+// w -= (lr * trust[segment]) * u with u formed again from w and the updated m, v (neither the
+// gradient nor the clip slot is read), and the bf16 HWIO copy.  adam_out: {lr, alpha, t}.
+void lamb_update_pack(float* master, const float* m, const float* v, long n,
+                      const LrSchedule& s, const long long* gstep, const long long* start_step,
+                      float beta1, float beta2, float epsilon, int decoupled,
+                      const ParamSeg* segs, int nseg, const float* wd_seg, const float* trust,
+                      bf16* bf, float* lr_out, float* adam_out, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

@@ -24,7 +24,8 @@ from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_state
-from .layout import (OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
+from .layout import (check_adam_trust, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
+                     OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha)
 
 
@@ -109,6 +110,12 @@ class GPUBackend:
     def lars_summary(self):
         return self.engine.lars_summary()
 
+    def lamb_state(self):
+        return self.engine.lamb_state()
+
+    def lamb_summary(self):
+        return self.engine.lamb_summary()
+
     def clip_state(self):
         return self.engine.clip_state()
 
@@ -136,7 +143,8 @@ class CPUBackend:
                  cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5,
                  adam_beta1: float = 0.9, adam_beta2: float = 0.999,
                  adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
-                 adam_decay_skip: str = "none"):
+                 adam_decay_skip: str = "none", adam_trust="off",
+                 adam_trust_skip: str = "vectors"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -194,6 +202,10 @@ class CPUBackend:
             adam_beta1, adam_beta2, adam_epsilon, adam_decay, adam_decay_skip)
         self.adam_decay = adam_decay
         self.adam_v, self.adam_start, self._adam_state = None, 0, None
+        # adam_trust on: LAMB, csrc/lamb.hip's expressions in fp32 torch
+        self.lamb = check_adam_trust(adam_trust, adam_trust_skip, optimizer)
+        self.adam_trust_skip = adam_trust_skip
+        self._lamb_state = None
         if self.adam:
             self.adam_v = torch.zeros(self.store.n_train)
             wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
@@ -281,7 +293,9 @@ class CPUBackend:
                 gp = self._clip_scale(g) * g + self.wd * master
             else:
                 gp = g + self.wd * master
-            if self.adam:
+            if self.lamb:
+                self._lamb_update(master, g, lr)
+            elif self.adam:
                 self._adam_update(master, g, lr)
             elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
@@ -332,6 +346,52 @@ class CPUBackend:
     def adam_state(self):
         """(t, alpha) of the last step (None: not adamw, or no step yet)."""
         return self._adam_state
+
+    def _lamb_update(self, master, g, lr):
+        """csrc/lamb.hip's three stages in fp32 torch (the norms in fp64, as the kernels'
+        are from the wave on); k1, k2 in fp64 from the step, each rounded once."""
+        f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
+        b1, b2, eps = f(self.adam_beta1), f(self.adam_beta2), f(self.adam_epsilon)
+        omb1, omb2 = f(1.0 - float(b1)), f(1.0 - float(b2))
+        lr32 = f(lr)
+        t = max(1, self.step_count - self.adam_start + 1)
+        k1, k2 = (f(k) for k in lamb_bias_corrections(t, self.adam_beta1, self.adam_beta2))
+        w, wd = master, self.adam_wd
+        gp = g * self._clip_scale(g) if self.clip_grad_norm > 0 else g.clone()
+        if self.adam_decay == "l2":
+            gp = gp + wd * w
+        self.mom.mul_(b1).add_(omb1 * gp)
+        self.adam_v.mul_(b2).add_(omb2 * (gp * gp))
+        u = (self.mom * k1) / (torch.sqrt(self.adam_v * k2) + eps)
+        if self.adam_decay == "decoupled":
+            u = u + wd * w
+        rate = torch.empty_like(w)
+        self._lamb_state = {}
+        for s in self.store.train_slots:
+            sl = slice(s.offset, s.offset + s.numel)
+            wn = float(torch.sqrt((w[sl].double() ** 2).sum()))
+            un = float(torch.sqrt((u[sl].double() ** 2).sum()))
+            skipped = self.adam_trust_skip == "vectors" and len(s.shape) == 1
+            tr = 1.0
+            if not skipped and wn > 0 and un > 0:
+                tr = wn / un
+            tr = f(tr)
+            rate[sl] = lr32 * tr
+            self._lamb_state[s.name] = (float(f(wn)), float(f(un)), float(tr), skipped)
+        w.sub_(rate * u)
+        self._adam_state = (t, adam_alpha(float(lr32), t, self.adam_beta1, self.adam_beta2))
+
+    def lamb_state(self):
+        """{tensor name: (wn, un, trust)} of the last step (None: adam_trust off, or no step
+        yet)."""
+        if self._lamb_state is None:
+            return None
+        return {n: v[:3] for n, v in self._lamb_state.items()}
+
+    def lamb_summary(self):
+        if self._lamb_state is None:
+            return None
+        return lamb_trust_summary({n: v[:3] for n, v in self._lamb_state.items() if not v[3]})
 
     def _ema_update(self):
         """shadow -= om * (shadow - master), k = the steps completed (csrc/ema.hip)."""
@@ -479,13 +539,15 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
                  mix_switch_prob: float = 0.5, adam_beta1: float = 0.9,
                  adam_beta2: float = 0.999, adam_epsilon: float = 1e-8,
-                 adam_decay: str = "decoupled", adam_decay_skip: str = "none"):
+                 adam_decay: str = "decoupled", adam_decay_skip: str = "none",
+                 adam_trust="off", adam_trust_skip: str = "vectors"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
         device = "gpu" if torch.cuda.is_available() else "cpu"
     adam = dict(adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
-                adam_decay=adam_decay, adam_decay_skip=adam_decay_skip)
+                adam_decay=adam_decay, adam_decay_skip=adam_decay_skip, adam_trust=adam_trust,
+                adam_trust_skip=adam_trust_skip)
     if device == "gpu":
         from .engine import Engine
 

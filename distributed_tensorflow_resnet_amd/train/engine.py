@@ -52,7 +52,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
-                     OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam)
+                     OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
+                     OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -130,7 +131,8 @@ class Engine:
                  cutmix_alpha: float = 0.0, mix_switch_prob: float = 0.5,
                  adam_beta1: float = 0.9, adam_beta2: float = 0.999,
                  adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
-                 adam_decay_skip: str = "none"):
+                 adam_decay_skip: str = "none", adam_trust="off",
+                 adam_trust_skip: str = "vectors"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -162,6 +164,11 @@ class Engine:
         self.adam_beta1, self.adam_beta2, self.adam_epsilon = check_adam(
             adam_beta1, adam_beta2, adam_epsilon, adam_decay, adam_decay_skip)
         self.adam_decay, self.adam_decay_skip = adam_decay, adam_decay_skip
+        # adam_trust on: LAMB, adamw's direction at a per-tensor rate lr * |w| / |u| in three
+        # launches (csrc/lamb.hip) over LARS's chunk table; no state of its own, so checkpoints
+        # move between trust on and off.  Off: nothing allocated, every plan as adamw's
+        self.lamb = check_adam_trust(adam_trust, adam_trust_skip, optimizer)
+        self.adam_trust_skip = adam_trust_skip
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -327,7 +334,7 @@ class Engine:
                                      "fp32 gradient, before the update")
         if self.adam and self.opt_fused:   # (before clipping: with both, adamw is the reason)
             self.opt_fused = False
-            self.opt_fused_reason = OPT_FUSED_ADAM_REASON
+            self.opt_fused_reason = OPT_FUSED_LAMB_REASON if self.lamb else OPT_FUSED_ADAM_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -420,9 +427,11 @@ class Engine:
         self.ohwi_tile0 = torch.tensor(np.concatenate([[0], np.cumsum(tiles)[:-1]]).astype(np.int64),
                                        device=dev)
         self.wbf = torch.zeros(max(bf_total, 1), dtype=BF16, device=dev)
-        if self.lars:
-            # chunk / skip table, chunk partials and (trust, wn, gn): fixed pointers
-            skip = [self.lars_skip == "vectors" and len(s.shape) == 1 for s in ps.train_slots]
+        if self.lars or self.lamb:
+            # chunk / skip table, chunk partials and (trust, wn, gn): fixed pointers (lamb:
+            # the same tables under adam_trust_skip, gn holding the norm of the direction u)
+            by = self.lars_skip if self.lars else self.adam_trust_skip
+            skip = [by == "vectors" and len(s.shape) == 1 for s in ps.train_slots]
             tab, blk = lars_tables(seg_arr, skip)
             assert LARS_DTYPE.itemsize == self.nat.lars_seg_bytes()
             assert LARS_CHUNK == self.nat.LARS_CHUNK
@@ -695,6 +704,25 @@ class Engine:
         if st is None:
             return None
         return lars_trust_summary({n: v for (n, v), skip in zip(st.items(), self.lars_skipped)
+                                   if not skip})
+
+    def lamb_state(self):
+        """{tensor name: (wn, un, trust)} of the last step's LAMB update: the norms of the fp32
+        master and of the direction u it was moved along, and their ratio (1 for a skipped
+        tensor or a zero norm; synchronises).  None before the first step, and unless the
+        optimizer is adamw with adam_trust on."""
+        if not self.lamb or self._steps_run == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        t, wn, un = self.lars_out.cpu().tolist()
+        return {n: (wn[i], un[i], t[i]) for i, n in enumerate(self.seg_names)}
+
+    def lamb_summary(self):
+        """min / median / max trust ratio over the adapted tensors (None: as lamb_state)."""
+        st = self.lamb_state()
+        if st is None:
+            return None
+        return lamb_trust_summary({n: v for (n, v), skip in zip(st.items(), self.lars_skipped)
                                    if not skip})
 
     def clip_state(self):

@@ -68,6 +68,12 @@ def _lars_summary(session):
     return fn() if fn is not None else None
 
 
+def _lamb_summary(session):
+    """The last step's LAMB trust ratios, as _lars_summary (None: --adam_trust off)."""
+    fn = getattr(session.backend, "lamb_summary", None)
+    return fn() if fn is not None else None
+
+
 class LoggingTensorHook(Hook):
     def __init__(self, every_n_iter: int = 20, precision_key: str = "precision"):
         self.n = every_n_iter
@@ -82,6 +88,10 @@ class LoggingTensorHook(Hook):
             ls = _lars_summary(session)
             lars = (f", lars trust min/median/max = {ls['lars_trust_min']:.4g}/"
                     f"{ls['lars_trust_median']:.4g}/{ls['lars_trust_max']:.4g}") if ls else ""
+            lb = _lamb_summary(session)
+            if lb:   # --optimizer adamw --adam_trust on
+                lars += (f", lamb trust min/median/max = {lb['lamb_trust_min']:.4g}/"
+                         f"{lb['lamb_trust_median']:.4g}/{lb['lamb_trust_max']:.4g}")
             clip = (f", grad norm = {m['grad_norm']:.6g} (scale {m['clip_scale']:.6g})"
                     if "grad_norm" in m else "")   # --clip_grad_norm
             if "adam_alpha" in m:   # --optimizer adamw
@@ -169,6 +179,7 @@ class JsonlMetricsHook(Hook):
                 m["step_path"] = "persistent" if getattr(eng, "persist", False) else "per-layer"
                 m["persist_disabled_reason"] = getattr(eng, "persist_reason", "") or None
             m.update(_lars_summary(session) or {})   # lars_trust_min / _median / _max
+            m.update(_lamb_summary(session) or {})   # lamb_trust_min / _median / _max
             ema = getattr(session.backend, "ema_decay", 0.0)
             if ema:
                 m["ema_decay"] = ema

@@ -165,6 +165,50 @@ def check_adam(beta1, beta2, epsilon, decay: str = "decoupled", decay_skip: str 
     return b1, b2, eps
 
 
+ADAM_TRUSTS = ("off", "on")
+ADAM_TRUST_SKIPS = ("vectors", "none")
+OPT_FUSED_LAMB_REASON = ("optimizer adamw with adam_trust on (LAMB): the trust ratio needs the "
+                         "norm of the whole Adam direction, after the moments and before any "
+                         "weight moves; it takes three generic launches")
+
+
+def check_adam_trust(trust="off", trust_skip: str = "vectors", optimizer: str = "adamw") -> bool:
+    """--adam_trust / --adam_trust_skip as both backends take them: whether layer-wise
+    adaptation (LAMB, csrc/lamb.hip) is on.  `trust` is 'off' / 'on' (or a bool); 'on' needs
+    the adamw optimizer; the skip is accepted and unused without it, as lars_skip is."""
+    if isinstance(trust, bool):
+        trust = "on" if trust else "off"
+    if trust not in ADAM_TRUSTS:
+        raise ValueError(f"adam_trust must be one of {ADAM_TRUSTS}, got {trust!r}")
+    if trust_skip not in ADAM_TRUST_SKIPS:
+        raise ValueError(f"adam_trust_skip must be one of {ADAM_TRUST_SKIPS}, got {trust_skip!r}")
+    if trust == "on" and optimizer != "adamw":
+        raise ValueError(f"adam_trust on is layer-wise adaptation of adamw: it cannot be combined "
+                         f"with optimizer {optimizer!r}")
+    return trust == "on"
+
+
+def lamb_bias_corrections(t: int, beta1: float, beta2: float):
+    """Host mirror of the device's k1 = 1 / (1 - b1^t), k2 = 1 / (1 - b2^t) (csrc/lamb.hip):
+    fp64 from the fp32 coefficients, 1 - b^t as -expm1(t * log(b)), each rounded to fp32 once."""
+    import math
+
+    def k(b):
+        b = float(np.float32(b))
+        return float(np.float32(1.0 / (1.0 if b == 0.0 else -math.expm1(t * math.log(b)))))
+
+    t = max(1, int(t))
+    return k(beta1), k(beta2)
+
+
+def lamb_trust_summary(state):
+    """min / median / max trust ratio over a lamb_state() dict (lars_trust_summary's shape)."""
+    t = sorted(v[2] for v in state.values())
+    if not t:
+        return {}
+    return {"lamb_trust_min": t[0], "lamb_trust_median": t[len(t) // 2], "lamb_trust_max": t[-1]}
+
+
 def adam_decay_table(shapes, wd: float, decay_skip: str = "none"):
     """wd_seg of adam_update_pack (csrc/adam.hip): the fp32 weight decay of each parameter
     segment, in slot order.  `shapes`: the trainables' shapes.  'none' decays every

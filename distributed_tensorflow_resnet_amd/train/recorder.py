@@ -590,20 +590,49 @@ class StepRecorder:
                     plan.grad_sqnorm(grad, e.params.n_train, e.clip_part.data_ptr())
                     plan.clip_scale(e.clip_part.data_ptr(), e.clip_chunks,
                                     float(np.float32(e.clip_grad_norm)), co)
-                i1 = plan.adam_update_pack(master, grad, mom, e.adam_v.data_ptr(),
-                                           e.params.n_train, *e.sched.launch_args(),
-                                           e.gstep.data_ptr(), e.adam_start.data_ptr(),
-                                           e.adam_beta1, e.adam_beta2, e.adam_epsilon, 1.0, co,
-                                           e.adam_decay, e.segs.data_ptr(), e.nseg,
-                                           e.adam_wd.data_ptr(), e.wbf.data_ptr(), sp + 8,
-                                           e.adam_out.data_ptr(), *e.sched.extra_launch_args())
+                lamb = ()
+                if e.lamb:
+                    # adam_trust on (csrc/lamb.hip): the moments and the chunk sums of w^2 and
+                    # u^2, the per-tensor trust ratios, then the update at lr * trust -- grad is
+                    # complete here, as for lars, and only the first launch reads it
+                    lo = e.lars_out.data_ptr()
+                    coef = (e.adam_beta1, e.adam_beta2, e.adam_epsilon)
+                    j0 = plan.lamb_moments_norms(
+                        master, grad, mom, e.adam_v.data_ptr(), e.gstep.data_ptr(),
+                        e.adam_start.data_ptr(), *coef, 1.0, co, e.adam_decay,
+                        e.segs.data_ptr(), e.lars_segs.data_ptr(), e.lars_blk.data_ptr(),
+                        e.lars_blk.numel(), e.adam_wd.data_ptr(), e.lars_part.data_ptr())
+                    j1 = plan.lamb_trust(e.lars_part.data_ptr(), e.lars_segs.data_ptr(), e.nseg,
+                                         lo, lo + 4 * e.nseg, lo + 8 * e.nseg)
+                    i1 = plan.lamb_update_pack(
+                        master, mom, e.adam_v.data_ptr(), e.params.n_train,
+                        *e.sched.launch_args(), e.gstep.data_ptr(), e.adam_start.data_ptr(),
+                        *coef, e.adam_decay, e.segs.data_ptr(), e.nseg, e.adam_wd.data_ptr(), lo,
+                        e.wbf.data_ptr(), sp + 8, e.adam_out.data_ptr(),
+                        *e.sched.extra_launch_args())
+                    lamb = (j0, j1)
+                else:
+                    i1 = plan.adam_update_pack(master, grad, mom, e.adam_v.data_ptr(),
+                                               e.params.n_train, *e.sched.launch_args(),
+                                               e.gstep.data_ptr(), e.adam_start.data_ptr(),
+                                               e.adam_beta1, e.adam_beta2, e.adam_epsilon, 1.0, co,
+                                               e.adam_decay, e.segs.data_ptr(), e.nseg,
+                                               e.adam_wd.data_ptr(), e.wbf.data_ptr(), sp + 8,
+                                               e.adam_out.data_ptr(), *e.sched.extra_launch_args())
                 if out.op_buffers:   # the overlap plan declares what its ops touch
                     gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
                     if clip:
                         out.op_buffers[i0] = gb | {"clip"}
                         out.op_buffers[i0 + 1] = {"clip"}
-                    out.op_buffers[i1] = (gb | {f"param:{b}" for b in range(len(e.buckets))}
-                                          | {"adam", "lr", "gstep"} | ({"clip"} if clip else set()))
+                    if lamb:
+                        out.op_buffers[lamb[0]] = (gb | pb | {"adam", "lamb", "gstep"}
+                                                   | ({"clip"} if clip else set()))
+                        out.op_buffers[lamb[1]] = {"lamb"}
+                        out.op_buffers[i1] = pb | {"adam", "lamb", "lr", "gstep"}
+                    else:
+                        out.op_buffers[i1] = (gb | pb | {"adam", "lr", "gstep"}
+                                              | ({"clip"} if clip else set()))
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

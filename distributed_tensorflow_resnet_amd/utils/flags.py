@@ -13,7 +13,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --ema_decay        device-side EMA of the weights, checkpointed; --eval_ema scores it
   --clip_grad_norm   clip the gradient by its global norm on the device (inf: only log it)
   --optimizer adamw  Adam with decoupled (or l2) weight decay in one device launch:
-                     --adam_beta1/_beta2/_epsilon, --adam_decay, --adam_decay_skip
+                     --adam_beta1/_beta2/_epsilon, --adam_decay, --adam_decay_skip;
+                     --adam_trust on makes it LAMB (per-tensor trust ratios), --adam_trust_skip
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -179,6 +180,14 @@ class FlagParser(argparse.ArgumentParser):
                            ns.adam_decay_skip)
             except ValueError as e:
                 self.error(str(e))
+        if hasattr(ns, "adam_trust"):
+            from ..train.layout import check_adam_trust
+
+            try:   # on: layer-wise adaptation of adamw, of no other optimizer
+                check_adam_trust(ns.adam_trust, ns.adam_trust_skip,
+                                 getattr(ns, "optimizer", "adamw"))
+            except ValueError as e:
+                self.error("--adam_trust: " + str(e))
         if getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "synthetic", False):
             self.error("--mixup_alpha cannot be combined with --synthetic: the synthetic "
                        "input has no input launch to mix in")
@@ -287,6 +296,14 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="adamw: tensors without weight decay: 'none' = every trainable is "
                         "decayed (this project's rule), 'vectors' = every rank-1 tensor (BN "
                         "gamma / beta, the dense bias) is not.")
+    p.add_argument("--adam_trust", default="off", choices=("off", "on"),
+                   help="adamw: 'on' = LAMB (You et al. 2020), the Adam direction u at a "
+                        "per-tensor rate lr * trust, trust = |w| / |u| (layer-wise adaptation, "
+                        "for large global batches); an error with any other --optimizer.")
+    p.add_argument("--adam_trust_skip", default="vectors", choices=("vectors", "none"),
+                   help="--adam_trust on: tensors that are not adapted (trust = 1): 'vectors' = "
+                        "every rank-1 tensor (BN gamma / beta, the dense bias), 'none' = adapt "
+                        "them too.  Unused with --adam_trust off.")
     p.add_argument("--lars_eeta", type=float, default=0.001,
                    help="LARS trust coefficient.")
     p.add_argument("--lars_epsilon", type=float, default=0.0,

@@ -43,6 +43,10 @@ def engine_state(eng) -> Dict[str, torch.Tensor]:
           "stats": eng.params.stats.detach().clone(), "global_step": eng.gstep.detach().clone()}
     if getattr(eng, "ema", None) is not None:   # the EMA shadows, when the engine keeps them
         st["ema"] = eng.ema.detach().clone()
+    if getattr(eng, "adam_v", None) is not None:   # adamw's second moment
+        st["adam_v"] = eng.adam_v.detach().clone()
+    if getattr(eng, "lamb", False):   # adam_trust on: (trust, |w|, |u|) of the last step
+        st["lamb"] = eng.lars_out.detach().clone()
     return st
 
 

@@ -1175,6 +1175,27 @@ static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
                                  0, 0, 0, 0, 0);
 }
 
+// Random Erasing on the input buffer the launch before wrote (erase.hip): x is bf16 NHWC with
+// Cpad 8 or (s2d) [N][H/2][W/2][16]; table / thresh (of 2^24) / noise (0: zero fill) / log (0:
+// none) are kernels.h's Erase.  Checked here, when the op is made.
+static Launch mk_erase_boxes(ptr_t x, int N, int H, int W, int Cpad, int s2d,
+                             unsigned long long seed, ptr_t gstep, ptr_t table, int table_len,
+                             long long thresh, ptr_t noise, int noise_len, ptr_t log) {
+  if (thresh < 0 || thresh > (1 << 24))
+    throw std::invalid_argument("erase_boxes: thresh must be in [0, 2^24]");
+  Erase er;
+  er.table = P<const int>(table);
+  er.table_len = table_len;
+  er.thresh = (unsigned)thresh;
+  er.noise = P<const float>(noise);
+  er.noise_len = noise ? noise_len : 0;
+  er.log = P<int>(log);
+  erase_boxes_check(P<const void>(x), N, H, W, Cpad, s2d, er);
+  return [=](hipStream_t s) {
+    erase_boxes(P<bf16>(x), N, H, W, Cpad, s2d, seed, P<const long long>(gstep), er, s);
+  };
+}
+
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
   return [=](hipStream_t s) { stem_s2d_pack(P<const float>(w7), P<bf16>(w4), K, s); };
 }
@@ -1766,6 +1787,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_mix);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_cut);
+  def_op(m, plan, "erase_boxes", mk_erase_boxes);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

@@ -513,6 +513,23 @@ void maxpool_fwd(const bf16* x, bf16* y, uint8_t* argmax, int N, int H, int W, i
 void maxpool_bwd(const uint8_t* argmax, const bf16* dy, bf16* dx, int N, int H, int W, int C,
                  int Ho, int Wo, int k, int stride, int pad, hipStream_t s);
 
+// ---- random erasing (erase.hip) ----
+// One box per image, drawn per image: data/cifar.py erase_draw(seed, step, n, table_len, H, W,
+// table, thresh) is the specification.  x is the step's input buffer behind the input launch:
+// bf16 NHWC with Cpad 8, or (s2d) the space-to-depth stem operand [N][H/2][W/2][16].
+struct Erase {
+  const int* table = nullptr;     // [table_len] eh << 16 | ew (erase_table); 0: not erased
+  int table_len = 0;
+  unsigned thresh = 0;            // of 2^24: 0 = never, 2^24 = every image with an entry
+  const float* noise = nullptr;   // [noise_len] fp32 (erase_noise_table); null: zero fill
+  int noise_len = 0;
+  int* log = nullptr;             // optional [N][5] {on, y0, x0, eh, ew} (0s: not erased)
+};
+// the argument checks of erase_boxes (std::invalid_argument), for plan recording
+void erase_boxes_check(const void* x, int N, int H, int W, int Cpad, int s2d, const Erase& er);
+void erase_boxes(bf16* x, int N, int H, int W, int Cpad, int s2d, unsigned long long seed,
+                 const long long* gstep, const Erase& er, hipStream_t s);
+
 // ---- flat-parameter descriptors ----
 struct ParamSeg {          // one trainable tensor inside the flat buffers
   long long offset;        // element offset into master/grad/mom (master layout = TF HWIO)

@@ -355,6 +355,103 @@ def cutmix_draw(seed: int, step: int, batch: int, table_len: int, H: int, W: int
     return d
 
 
+# ---------------------------------------------------------------- random erasing
+# Random Erasing (Zhong et al. 2020; with a zero fill, Cutout: DeVries & Taylor 2017) in a
+# launch of its own behind the input launch (csrc/erase.hip): with probability p, batch position
+# n gets one rectangle of its image overwritten by the fill.  Unlike the two mixes the draw is
+# per IMAGE: keyed like the crops with (seed, step, n), under a salted and hashed seed, so it is
+# no image's crop hash and no step's mix hash.  The box sizes come from a host-made table
+# (torchvision's RandomErasing.get_params loop in fp64), so neither a sampler nor a sqrt nor a
+# log runs on the device.  The functions below are the specification the kernel must equal.
+ERASE_TABLE_LEN = 4096
+ERASE_SALT = 0x455241534521           # "ERASE!"
+_ERASE_NOISE_SALT = 0x4E4F495345      # "NOISE"
+ERASE_THRESH_ONE = 1 << 24
+
+
+def erase_table(seed: int, H: int, W: int, area_min: float = 0.02, area_max: float = 1.0 / 3.0,
+                aspect_min: float = 0.3, length: int = ERASE_TABLE_LEN) -> np.ndarray:
+    """`length` box sizes as int32 ``eh << 16 | ew``.  Each entry is torchvision's
+    RandomErasing.get_params loop in fp64 from Generator(PCG64(seed ^ salt)): up to 10 attempts
+    of area = H * W * U(area_min, area_max), log r ~ U(log aspect_min, -log aspect_min),
+    eh = int(round(sqrt(area * r))), ew = int(round(sqrt(area / r))), accepted when
+    1 <= eh < H and 1 <= ew < W.  Ten failures give 0: that image is not erased."""
+    if not (1 < H < 1 << 15 and 1 < W < 1 << 15):
+        raise ValueError(f"erasing needs 1 < H, W < 2**15, got {H}x{W}")
+    if not 0.0 < area_min <= area_max <= 1.0:
+        raise ValueError(f"need 0 < erase_area_min <= erase_area_max <= 1, got {area_min!r}, "
+                         f"{area_max!r}")
+    if not 0.0 < aspect_min <= 1.0:
+        raise ValueError(f"erase_aspect_min must be in (0, 1], got {aspect_min!r}")
+    rng = np.random.Generator(np.random.PCG64((seed & _M64) ^ ERASE_SALT))
+    lo = float(np.log(aspect_min))
+    out = np.zeros(length, dtype=np.int32)
+    for i in range(length):
+        for _ in range(10):
+            area = H * W * rng.uniform(area_min, area_max)
+            r = float(np.exp(rng.uniform(lo, abs(lo))))
+            eh = int(round(float(np.sqrt(area * r))))
+            ew = int(round(float(np.sqrt(area / r))))
+            if 1 <= eh < H and 1 <= ew < W:
+                out[i] = (eh << 16) | ew
+                break
+    return out
+
+
+def erase_thresh(p: float) -> int:
+    """The 24-bit threshold an image's draw is compared with: int(round(p * 2**24))."""
+    if not 0.0 <= p <= 1.0:   # NaN included
+        raise ValueError(f"erase_prob must be in [0, 1], got {p!r}")
+    return int(round(p * ERASE_THRESH_ONE))
+
+
+def erase_noise_table(seed: int, length: int = ERASE_TABLE_LEN) -> np.ndarray:
+    """`length` fp32 standard-normal draws (Generator(PCG64(seed ^ salt)).standard_normal): the
+    values a noise-filled box is made of.  Element (y, x, c) of image n's box is
+    table[splitmix(h2 ^ ((y * W + x) * 4 + c)) % length] (erase_noise_index), rounded to bf16
+    once on the device."""
+    rng = np.random.Generator(np.random.PCG64((seed & _M64) ^ _ERASE_NOISE_SALT))
+    return rng.standard_normal(length).astype(np.float32)
+
+
+def erase_hash(seed: int, step: int, n: int) -> int:
+    """The 64-bit hash of image n's draw: the crop hash's key form under a salted, hashed seed."""
+    return splitmix(splitmix((seed & _M64) ^ ERASE_SALT) ^
+                    splitmix((step * 0x100000001B3 + n) & _M64))
+
+
+def erase_draw(seed: int, step: int, n: int, table_len: int, H: int, W: int, entry_of,
+               thresh: int) -> dict:
+    """Image n's draw at step `step`: ``on`` ((h >> 40) < thresh, and its table entry is not
+    0), ``index`` into the table, the box's corner ``y0, x0`` and size ``eh, ew`` (all 0 when
+    off).  ``h2`` (the placement hash, also the key of the noise fill) is returned too.
+    Integers only; exact for steps >= 2**32.  erase_table only makes eh < H and ew < W; the
+    draw takes every entry that fits (1 <= eh <= H, 1 <= ew <= W: a hand-made table may hold
+    a full row or column) and raises for one that does not, which the kernel treats as off."""
+    if step < 0 or n < 0 or table_len < 1:
+        raise ValueError("need step >= 0, n >= 0, table_len >= 1")
+    if not 0 <= thresh <= ERASE_THRESH_ONE:
+        raise ValueError(f"thresh must be in [0, 2**24], got {thresh!r}")
+    h = erase_hash(seed, step, n)
+    index = (h & 0xFFFFFFFF) % table_len
+    h2 = splitmix(h ^ ERASE_SALT)
+    d = {"on": False, "index": index, "y0": 0, "x0": 0, "eh": 0, "ew": 0, "h2": h2}
+    entry = int(entry_of[index])
+    if not (h >> 40) < thresh or entry == 0:
+        return d
+    eh, ew = (entry >> 16) & 0xFFFF, entry & 0xFFFF
+    if not (1 <= eh <= H and 1 <= ew <= W):
+        raise ValueError(f"table entry {index}: box {eh}x{ew} does not fit {H}x{W}")
+    d.update(on=True, y0=(h2 & 0xFFFFFFFF) % (H - eh + 1), x0=(h2 >> 32) % (W - ew + 1),
+             eh=eh, ew=ew)
+    return d
+
+
+def erase_noise_index(h2: int, y: int, x: int, c: int, W: int, length: int) -> int:
+    """Index into the noise table of channel c of pixel (y, x) of a box placed by h2."""
+    return splitmix(h2 ^ ((y * W + x) * 4 + c)) % length
+
+
 def synthetic_batches(batch_size: int, num_classes: int = 10, seed: int = 0):
     """Endless random uint8 CIFAR-shaped records (for --synthetic)."""
     g = torch.Generator().manual_seed(seed)

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from ..data.cifar import (MIXUP_TABLE_LEN, augment_cpu, cutmix_draw, cutmix_table, cutmix_thresh,
-                          mixup_draw, mixup_table)
+                          erase_draw, erase_noise_index, erase_noise_table, erase_table,
+                          erase_thresh, mixup_draw, mixup_table)
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
@@ -26,7 +27,7 @@ from ..parallel.dist import local_device_index
 from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_state
 from .layout import (check_adam_trust, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
-                     check_mixup_alpha)
+                     check_mixup_alpha, check_erase)
 
 
 class GPUBackend:
@@ -125,6 +126,9 @@ class GPUBackend:
     def mix_state(self):
         return self.engine.mix_state()
 
+    def erase_state(self):
+        return self.engine.erase_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -144,7 +148,9 @@ class CPUBackend:
                  adam_beta1: float = 0.9, adam_beta2: float = 0.999,
                  adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
                  adam_decay_skip: str = "none", adam_trust="off",
-                 adam_trust_skip: str = "vectors"):
+                 adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
+                 erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -162,7 +168,21 @@ class CPUBackend:
                 self.mix_table = np.ones(MIXUP_TABLE_LEN, dtype=np.float32)
         self._mix_state = None
         self._cut_area = None
-        self.last_input = None     # the batch the last step fed the model (mixup / CutMix on)
+        self.last_input = None     # the batch the last step fed the model (mixup / CutMix /
+        #                            erasing on)
+        # Random Erasing, csrc/erase.hip's boxes on the fp32 batch after its mix, from the same
+        # tables and draw (0 = off); the noise values are the fp32 table's
+        (self.erase_prob, self.erase_area_min, self.erase_area_max, self.erase_aspect_min,
+         self.erase_fill) = check_erase(erase_prob, erase_area_min, erase_area_max,
+                                        erase_aspect_min, erase_fill, spec.dataset)
+        self.erase_tab = self.erase_noise = self._erase_state = None
+        if self.erase_prob > 0:
+            self.erase_tab = erase_table(data_seed, spec.image_h, spec.image_w,
+                                         self.erase_area_min, self.erase_area_max,
+                                         self.erase_aspect_min)
+            self.erase_thresh = erase_thresh(self.erase_prob)
+            if self.erase_fill == "noise":
+                self.erase_noise = erase_noise_table(data_seed)
         # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self._clip_state = None
@@ -272,6 +292,9 @@ class CPUBackend:
             self.last_input = x
             if not float(lam) >= 0.5:   # precision is counted against the dominant label
                 y = mix["labels_b"]
+        if self.erase_tab is not None:
+            x = self._erase(x)
+            self.last_input = x
         logits = m(x, True)
         xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing, **mix)
         # mean over the GLOBAL batch: local mean * (local/global), then sum-allreduce
@@ -437,6 +460,32 @@ class CPUBackend:
         """As Engine.mix_state (None: mixup and CutMix off, or no step yet)."""
         return self._mix_state
 
+    def _erase(self, x):
+        """x [N, H, W, C] with each image's box of this step (erase_draw) set to the fill."""
+        N, H, W, C = x.shape
+        x = x.clone()
+        state = np.zeros((N, 5), dtype=np.int64)
+        for n in range(N):
+            d = erase_draw(self.data_seed, self.step_count, n, len(self.erase_tab), H, W,
+                           self.erase_tab, self.erase_thresh)
+            if not d["on"]:
+                continue
+            y0, x0, eh, ew = d["y0"], d["x0"], d["eh"], d["ew"]
+            state[n] = (1, y0, x0, eh, ew)
+            if self.erase_noise is None:
+                x[n, y0:y0 + eh, x0:x0 + ew] = 0.0
+                continue
+            idx = [[[erase_noise_index(d["h2"], y, xx, c, W, len(self.erase_noise))
+                     for c in range(C)] for xx in range(x0, x0 + ew)]
+                   for y in range(y0, y0 + eh)]
+            x[n, y0:y0 + eh, x0:x0 + ew] = torch.from_numpy(self.erase_noise[np.array(idx)])
+        self._erase_state = state
+        return x
+
+    def erase_state(self):
+        """As Engine.erase_state (None: erasing off, or no step yet)."""
+        return self._erase_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -481,6 +530,11 @@ class CPUBackend:
             m["mix_mode"] = int(self._cut_area is not None)
             if self._cut_area is not None:
                 m["cutmix_area"] = self._cut_area
+        if self._erase_state is not None:
+            box = self._erase_state
+            m["erase_count"] = int(box[:, 0].sum())
+            m["erase_area"] = float((box[:, 3] * box[:, 4]).sum() /
+                                    (self.N * self.spec.image_h * self.spec.image_w))
         return m
 
     def synchronize(self):
@@ -540,7 +594,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  mix_switch_prob: float = 0.5, adam_beta1: float = 0.9,
                  adam_beta2: float = 0.999, adam_epsilon: float = 1e-8,
                  adam_decay: str = "decoupled", adam_decay_skip: str = "none",
-                 adam_trust="off", adam_trust_skip: str = "vectors"):
+                 adam_trust="off", adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
+                 erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -548,6 +604,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
     adam = dict(adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
                 adam_decay=adam_decay, adam_decay_skip=adam_decay_skip, adam_trust=adam_trust,
                 adam_trust_skip=adam_trust_skip)
+    erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
+                 erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
+                 erase_fill=erase_fill)
     if device == "gpu":
         from .engine import Engine
 
@@ -563,7 +622,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                      label_smoothing=label_smoothing, ema_decay=ema_decay,
                      ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
                      mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha,
-                     mix_switch_prob=mix_switch_prob, **adam)
+                     mix_switch_prob=mix_switch_prob, **adam, **erase)
         return GPUBackend(eng, use_graph=use_graph)
     if resident is not None:
         raise ValueError("a device-resident split needs the GPU backend")
@@ -574,4 +633,4 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                       label_smoothing=label_smoothing, ema_decay=ema_decay,
                       ema_warmup=ema_warmup, clip_grad_norm=clip_grad_norm,
                       mixup_alpha=mixup_alpha, data_seed=data_seed, cutmix_alpha=cutmix_alpha,
-                      mix_switch_prob=mix_switch_prob, **adam)
+                      mix_switch_prob=mix_switch_prob, **adam, **erase)

@@ -227,6 +227,11 @@ def main(argv=None, kind: str = "cifar") -> int:
                            clip_grad_norm=flags.clip_grad_norm, mixup_alpha=flags.mixup_alpha,
                            cutmix_alpha=flags.cutmix_alpha,
                            mix_switch_prob=flags.mix_switch_prob,
+                           erase_prob=flags.erase_prob,
+                           erase_area_min=flags.erase_area_min,
+                           erase_area_max=flags.erase_area_max,
+                           erase_aspect_min=flags.erase_aspect_min,
+                           erase_fill=flags.erase_fill,
                            adam_beta1=flags.adam_beta1, adam_beta2=flags.adam_beta2,
                            adam_epsilon=flags.adam_epsilon, adam_decay=flags.adam_decay,
                            adam_decay_skip=flags.adam_decay_skip,

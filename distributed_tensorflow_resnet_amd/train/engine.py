@@ -40,7 +40,8 @@ import numpy as np
 import torch
 
 from .. import native
-from ..data.cifar import (MIXUP_TABLE_LEN, cutmix_table, cutmix_thresh, mixup_table,
+from ..data.cifar import (MIXUP_TABLE_LEN, cutmix_table, cutmix_thresh, erase_noise_table,
+                          erase_table, erase_thresh, mixup_table,
                           resident_steps_per_epoch, upload_resident)
 from ..models.params import ParamStore
 from ..models.spec import BNSpec, ConvSpec, ModelSpec
@@ -50,7 +51,7 @@ from ..utils.streamcheck import check_plan
 from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa: F401
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
-                     check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob,
+                     check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob, check_erase,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary)
@@ -132,7 +133,9 @@ class Engine:
                  adam_beta1: float = 0.9, adam_beta2: float = 0.999,
                  adam_epsilon: float = 1e-8, adam_decay: str = "decoupled",
                  adam_decay_skip: str = "none", adam_trust="off",
-                 adam_trust_skip: str = "vectors"):
+                 adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
+                 erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -189,6 +192,13 @@ class Engine:
         self.cutmix_alpha = check_cutmix_alpha(cutmix_alpha)
         self.mix_switch_prob = check_mix_switch_prob(mix_switch_prob)
         self.cut_thresh = cutmix_thresh(self.mixup_alpha, self.cutmix_alpha, self.mix_switch_prob)
+        # Random Erasing in a launch of its own behind the input launch (csrc/erase.hip;
+        # data/cifar.py erase_draw): each image gets, with probability erase_prob, one box
+        # overwritten by the fill -- after the mix, when one is on; labels and lam are untouched.
+        # 0 = off: nothing allocated, no op recorded.  The eval plans never erase.
+        (self.erase_prob, self.erase_area_min, self.erase_area_max, self.erase_aspect_min,
+         self.erase_fill) = check_erase(erase_prob, erase_area_min, erase_area_max,
+                                        erase_aspect_min, erase_fill, spec.dataset)
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -244,6 +254,15 @@ class Engine:
         if self.cutmix_alpha > 0 and input_mode not in MIXUP_INPUT_MODES:
             raise ValueError(f"cutmix_alpha > 0 needs an input launch to paste in (input_mode one "
                              f"of {MIXUP_INPUT_MODES}), got input_mode={input_mode!r}")
+        if self.erase_prob > 0:
+            # the input buffer must be rewritten by a launch every step, or boxes would pile up
+            if input_mode not in MIXUP_INPUT_MODES:
+                raise ValueError(f"erase_prob > 0 needs an input launch to erase behind "
+                                 f"(input_mode one of {MIXUP_INPUT_MODES}), got "
+                                 f"input_mode={input_mode!r}")
+            if input_mode.startswith("cifar") and (spec.image_h, spec.image_w) != (32, 32):
+                raise ValueError("erase_prob > 0: not with the generic-shape CIFAR augment "
+                                 f"kernel ({spec.image_h}x{spec.image_w} images)")
         # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
         # the device and the step's input launch picks its own records through the keyed
         # permutation of global_step (data/cifar.py resident_index; csrc/data.hip).  Uploaded
@@ -524,6 +543,18 @@ class Engine:
             self.cut_table = torch.from_numpy(
                 cutmix_table(self.cutmix_alpha, self.data_seed, H, W)).to(dev)
             self.cut_log = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.erase_tab = self.erase_noise = self.erase_log = None
+        self.erase_thresh = 0
+        if self.erase_prob > 0:
+            # the box sizes and (noise fill) the noise values, uploaded once, and the launch's
+            # per-image {on, y0, x0, eh, ew}: fixed pointers
+            self.erase_tab = torch.from_numpy(erase_table(
+                self.data_seed, H, W, self.erase_area_min, self.erase_area_max,
+                self.erase_aspect_min)).to(dev)
+            self.erase_thresh = erase_thresh(self.erase_prob)
+            if self.erase_fill == "noise":
+                self.erase_noise = torch.from_numpy(erase_noise_table(self.data_seed)).to(dev)
+            self.erase_log = torch.zeros((N, 5), dtype=torch.int32, device=dev)
         st = spec.stem
         self.stem_out = torch.empty((N, st.ho, st.wo, st.cout), dtype=BF16, device=dev)
         if spec.maxpool:
@@ -769,6 +800,15 @@ class Engine:
         cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
         return {"mode": "cutmix" if cut[0] else "mixup", "lam": lam, "shift": shift,
                 "box": tuple(cut[1:5]) if cut[0] else None}
+
+    def erase_state(self):
+        """The last step's erased boxes (synchronises): int array [N, 5] of {on, y0, x0, eh, ew}
+        per batch position, data/cifar.py erase_draw's (0s: not erased).  None: erasing off, or
+        no step yet."""
+        if self.erase_log is None or self._steps_run == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        return self.erase_log.cpu().numpy()
 
     def mix_head_ptrs(self) -> tuple:
         """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""
@@ -1056,6 +1096,11 @@ class Engine:
             m["mix_mode"] = int(cut[0])
             if cut[0]:
                 m["cutmix_area"] = int(cut[5])
+        if self.erase_log is not None:
+            box = self.erase_log.cpu().numpy().astype(np.int64)
+            m["erase_count"] = int(box[:, 0].sum())
+            m["erase_area"] = float((box[:, 3] * box[:, 4]).sum() /
+                                    (self.N * self.spec.image_h * self.spec.image_w))
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -100,6 +100,8 @@ class LoggingTensorHook(Hook):
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"
                        if m["mix_mode"] else f", mixup lam = {m['mixup_lam']:.6g}")
+            if "erase_count" in m:   # --erase_prob
+                mix += f", erased = {m['erase_count']} (area {m['erase_area']:.4g})"
             log(f"INFO:tensorflow:step = {m['global_step']}, loss = {m['cost']:.6f}, "
                 f"{self.key} = {m['precision']:.4f}, lr = {m['lr']:.6g}{lars}{clip}{mix}")
 

@@ -274,6 +274,37 @@ def check_mix_switch_prob(p) -> float:
     return p
 
 
+ERASE_FILLS = ("zero", "noise")
+
+
+def check_erase(prob, area_min=0.02, area_max=1.0 / 3.0, aspect_min=0.3, fill="zero",
+                dataset: str = "") -> tuple:
+    """--erase_prob and its sub-flags as both backends take them -> (prob, area_min, area_max,
+    aspect_min, fill): prob in [0, 1] (0 = off), 0 < area_min <= area_max <= 1, aspect_min in
+    (0, 1], fill zero | noise.  Noise is refused for ImageNet: those inputs are mean-subtracted
+    but not scaled, so unit noise is a constant there, and zero is already the mean pixel."""
+    try:
+        prob, area_min, area_max, aspect_min = (float(v) for v in
+                                                (prob, area_min, area_max, aspect_min))
+    except (TypeError, ValueError):
+        raise ValueError("erase_prob, erase_area_min, erase_area_max and erase_aspect_min must "
+                         "be numbers") from None
+    if not 0.0 <= prob <= 1.0:   # NaN included
+        raise ValueError(f"erase_prob must be in [0, 1], got {prob!r}")
+    if not 0.0 < area_min <= area_max <= 1.0:
+        raise ValueError(f"need 0 < erase_area_min <= erase_area_max <= 1, got {area_min!r}, "
+                         f"{area_max!r}")
+    if not 0.0 < aspect_min <= 1.0:
+        raise ValueError(f"erase_aspect_min must be in (0, 1], got {aspect_min!r}")
+    if fill not in ERASE_FILLS:
+        raise ValueError(f"erase_fill must be one of {ERASE_FILLS}, got {fill!r}")
+    if fill == "noise" and str(dataset).startswith("imagenet"):
+        raise ValueError("erase_fill noise is not for ImageNet: its inputs are mean-subtracted "
+                         "but not scaled, so unit noise is a constant there (zero is the mean "
+                         "pixel)")
+    return prob, area_min, area_max, aspect_min, fill
+
+
 def check_clip_grad_norm(c, optimizer: str) -> float:
     """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
     the norm is measured, the scale is exactly 1); not together with lars, whose trust

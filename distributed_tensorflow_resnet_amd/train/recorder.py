@@ -714,6 +714,16 @@ class StepRecorder:
                                   *mix(e.labels.data_ptr()))
         elif zero[0]:
             plan.memset(*zero)
+        self._erase_op = None
+        if e.erase_tab is not None:
+            # Random Erasing: a launch of its own on the main stream, directly behind the input
+            # launch and before the forward, so every input kernel above stays as it is
+            noise = e.erase_noise
+            self._erase_op = plan.erase_boxes(
+                e.x_in.data_ptr(), e.N, H, W, e.cpad_in, int(e.stem_s2d), e.data_seed,
+                e.gstep.data_ptr(), e.erase_tab.data_ptr(), e.erase_tab.numel(), e.erase_thresh,
+                noise.data_ptr() if noise is not None else 0,
+                noise.numel() if noise is not None else 0, e.erase_log.data_ptr())
 
     def record_layers(self) -> RecordedStep:
         """The launch-per-layer step."""
@@ -937,6 +947,8 @@ class StepRecorder:
         self._reduce_main = True   # the slab reduces run on the main stream
         if e.prn.overlap:
             early = self._emit_persist_overlap(args)
+            if self._erase_op is not None and out.op_buffers:
+                out.op_buffers[self._erase_op] = {"input"}   # the overlap plan declares its ops
             out.seg["bwd"] = (b1, plan.size())
             if e.opt_fused:   # the rest: the last bucket's segments
                 self._emit_optimizer(fused_slabs={}, gin=self._packed_gin(),

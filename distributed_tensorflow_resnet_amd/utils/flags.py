@@ -123,14 +123,21 @@ def _cutmix_alpha(v) -> float:
     return f
 
 
-def _switch_prob(v) -> float:
-    try:
-        f = float(v)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
-    if not 0.0 <= f <= 1.0:   # NaN included
-        raise argparse.ArgumentTypeError(f"a switch probability must be in [0, 1], got {v!r}")
-    return f
+def _unit_float(what: str):
+    """argparse type: a float in [0, 1] (NaN refused), named `what` in the error."""
+    def parse(v) -> float:
+        try:
+            f = float(v)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+        if not 0.0 <= f <= 1.0:   # NaN included
+            raise argparse.ArgumentTypeError(f"{what} must be in [0, 1], got {v!r}")
+        return f
+    return parse
+
+
+_switch_prob = _unit_float("a switch probability")
+_erase_prob = _unit_float("an erase probability")
 
 
 def _lr_rate(v) -> float:
@@ -200,6 +207,17 @@ class FlagParser(argparse.ArgumentParser):
             elif not (getattr(ns, "mixup_alpha", 0.0) > 0 and getattr(ns, "cutmix_alpha", 0.0) > 0):
                 self.error("--mix_switch_prob chooses between mixup and CutMix per step: it needs "
                            "--mixup_alpha > 0 and --cutmix_alpha > 0")
+        if hasattr(ns, "erase_prob"):
+            from ..train.layout import check_erase
+
+            try:   # the sub-flags are checked, and otherwise unused, at --erase_prob 0
+                check_erase(ns.erase_prob, ns.erase_area_min, ns.erase_area_max,
+                            ns.erase_aspect_min, ns.erase_fill, getattr(ns, "dataset", ""))
+            except ValueError as e:
+                self.error("--erase_prob: " + str(e))
+            if ns.erase_prob > 0 and getattr(ns, "synthetic", False):
+                self.error("--erase_prob cannot be combined with --synthetic: the synthetic "
+                           "input has no input launch to erase behind")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -216,6 +234,8 @@ class FlagParser(argparse.ArgumentParser):
 
 def build_parser(kind: str = "cifar", description: str | None = None) -> FlagParser:
     """kind: cifar | imagenet (train entrypoints), cifar_eval | imagenet_eval, single."""
+    from ..train.layout import ERASE_FILLS
+
     im = 1 if kind.startswith("imagenet") else 0
     p = FlagParser(description=description, allow_abbrev=False)
     d = {k: v[im] for k, v in _DEFAULTS.items()}
@@ -348,6 +368,24 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
     p.add_argument("--mix_switch_prob", type=_switch_prob, default=None,
                    help="Probability in [0, 1] that a step is a CutMix step when --mixup_alpha "
                         "and --cutmix_alpha are both > 0 (default 0.5).  An error otherwise.")
+    p.add_argument("--erase_prob", type=_erase_prob, default=0.0,
+                   help="Random Erasing (Zhong et al. 2020; with the zero fill, Cutout) on the "
+                        "device: each training image gets, with this probability, one random "
+                        "rectangle overwritten by the fill, in a launch of its own behind the "
+                        "input launch (after mixup / CutMix).  The draw is per image, a function "
+                        "of the seed, global_step and the batch position.  0 = off.  Evaluation "
+                        "never erases.  Same input requirements as --mixup_alpha.")
+    p.add_argument("--erase_area_min", type=float, default=0.02,
+                   help="--erase_prob: smallest erased share of the image (0 < min <= max <= 1).")
+    p.add_argument("--erase_area_max", type=float, default=1.0 / 3.0,
+                   help="--erase_prob: largest erased share of the image.")
+    p.add_argument("--erase_aspect_min", type=float, default=0.3,
+                   help="--erase_prob: the box's aspect ratio is log-uniform in [a, 1 / a]; a in "
+                        "(0, 1].")
+    p.add_argument("--erase_fill", default="zero", choices=ERASE_FILLS,
+                   help="--erase_prob: 'zero' = the mean pixel of the standardised input, "
+                        "'noise' = unit normal values from a host-made table (CIFAR only: an "
+                        "error with ImageNet, whose inputs are not scaled).")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

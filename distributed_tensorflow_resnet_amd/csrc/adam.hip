@@ -8,18 +8,17 @@
 //   alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)
 //   w'    = w - alpha * m' / (sqrt(v') + eps) (- lr * wd_s * w, the old w, in decoupled mode)
 // as ONE streaming launch over the flat fp32 master, gradient and the two moment buffers
-// (the first moment lives in the momentum buffer), in sgd_update_pack's shape: 256 threads,
-// at most 4096 workgroups, four consecutive elements per thread and trip (16-byte loads of
-// w, g, m, v; 16-byte stores of w, m, v; an 8-byte store of the bf16 HWIO copy), the
-// parameter segment tracked incrementally from the LDS copy of the table.  ohwi_pack
-// follows, with its global_step += 1, as after sgd_update_pack.
+// (the first moment lives in the momentum buffer): optim_device.h's FlatWalk, in
+// sgd_update_pack's shape, with AdamStep as its step (16-byte loads of g, m, v and stores of
+// m, v beside the walk's w and bf16 copy).  ohwi_pack follows, with its global_step += 1, as
+// after sgd_update_pack.
 // The decay of a segment is wd_seg[segment] (train/layout.py adam_decay_table), as LARS
 // reads trust[]; the decay mode is uniform over the launch.
-// Bias correction: one lane per workgroup evaluates lr (lr_at) and alpha ahead of the
-// loads, and both ride the barrier that publishes the segment table.  t is a 64-bit
-// integer; 1 - b^t is -expm1(t * log(b)) in fp64 (no cancellation at small t; b = 0 gives
-// exactly 1), the square root and the quotient are fp64, and the result is rounded to fp32
-// once: within one fp32 ulp of the correctly rounded value.  Nothing is read by the host.
+// Bias correction (optim_device.h bias_correction): one lane per workgroup evaluates lr
+// (lr_at) and alpha ahead of the loads, and both ride the barrier that publishes the segment
+// table.  t is a 64-bit integer; the square root and the quotient are fp64, and the result is
+// rounded to fp32 once: within one fp32 ulp of the correctly rounded value.  Nothing is read
+// by the host.
 // Per element everything is fp32, each product, sum, square root and quotient rounded at
 // most once (sqrtf and / are correctly rounded; tests/adam_oracle.py counts them).  1 - b1
 // and 1 - b2 come rounded once from fp64 on the host.  With g = m = v = 0 and no decay the
@@ -31,10 +30,6 @@
 #include "optim_device.h"
 
 namespace dtr {
-
-struct AdamCoef {
-  float b1, omb1, b2, omb2, eps;
-};
 
 #ifndef DTR_ADAM_NT
 #define DTR_ADAM_NT 1             // -DDTR_ADAM_NT=0: the A/B build of profiles/adam.md
@@ -54,17 +49,44 @@ __device__ __forceinline__ void adam_elem(float& w, float g, float& m, float& v,
   w = wn;
 }
 
+// FlatWalk's step: what adam keeps beside w.
 template <bool NT>
-__device__ __forceinline__ f32x4 adam_ld4(const float* p) {
-  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  else return *reinterpret_cast<const f32x4*>(p);
-}
+struct AdamStep {
+  const float* __restrict__ g;
+  float* __restrict__ m;
+  float* __restrict__ v;
+  const float* __restrict__ wd_seg;
+  AdamCoef c;
+  float grad_scale, lr, alpha;
+  bool dec;
+  static constexpr bool update = true;
 
-template <bool NT>
-__device__ __forceinline__ void adam_st4(float* p, f32x4 x) {
-  if constexpr (NT) __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(p));
-  else *reinterpret_cast<f32x4*>(p) = x;
-}
+  __device__ __forceinline__ void operator()(int sgi, long e0, f32x4& wv) const {
+    const f32x4 gv = ld4<false>(g + e0);
+    f32x4 mv = ld4<NT>(m + e0);
+    f32x4 vv = ld4<NT>(v + e0);
+    const float wd = wd_seg[sgi];
+    const float lrwd = lr * wd;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float wj = wv[j], mj = mv[j], vj = vv[j];
+      adam_elem(wj, gv[j], mj, vj, grad_scale, wd, lrwd, alpha, c, dec);
+      wv[j] = wj;
+      mv[j] = mj;
+      vv[j] = vj;
+    }
+    st4<NT>(m + e0, mv);
+    st4<NT>(v + e0, vv);
+  }
+
+  __device__ __forceinline__ void operator()(int sgi, long e, float& wj) const {
+    const float wd = wd_seg[sgi];
+    float mj = m[e], vj = v[e];
+    adam_elem(wj, g[e], mj, vj, grad_scale, wd, lr * wd, alpha, c, dec);
+    m[e] = mj;
+    v[e] = vj;
+  }
+};
 
 template <bool CLIP, bool NT>
 __global__ void __launch_bounds__(256)
@@ -80,11 +102,8 @@ adam_pack_kernel(float* __restrict__ w, const float* __restrict__ g, float* __re
   if (threadIdx.x == 0) {
     const long long step = gstep ? *gstep : 0ll;
     const float lr = lr_at(sched, (long)step);
-    long long t = step - (start ? *start : 0ll) + 1;
-    if (t < 1) t = 1;
-    const double c1 = -expm1((double)t * log((double)c.b1));
-    const double c2 = -expm1((double)t * log((double)c.b2));
-    const float alpha = (float)((double)lr * sqrt(c2) / c1);
+    const BiasCorrection b = bias_correction(step, start, c);
+    const float alpha = b.alpha(lr);
     rate_s[0] = lr;
     rate_s[1] = alpha;
     if (blockIdx.x == 0) {
@@ -92,70 +111,13 @@ adam_pack_kernel(float* __restrict__ w, const float* __restrict__ g, float* __re
       if (adam_out) {
         adam_out[0] = lr;
         adam_out[1] = alpha;
-        adam_out[2] = (float)t;
+        adam_out[2] = (float)b.t;
       }
     }
   }
-  const ParamSeg* S = segs;
-  if (nseg <= SEG_LDS_MAX) {
-    for (int i = threadIdx.x; i < nseg; i += blockDim.x) sseg[i] = segs[i];
-    S = sseg;
-  }
-  __syncthreads();   // the table and the two rates
-  const float lr = rate_s[0], alpha = rate_s[1];
-  const bool dec = decoupled != 0;   // uniform over the launch
-  const long nv = (n + 3) / 4;
-  const long stride = (long)gridDim.x * blockDim.x;
-  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= nv) return;
-  int sgi = find_seg(S, nseg, i * 4);
-  for (; i < nv; i += stride) {
-    const long e0 = i * 4;
-    while (sgi + 1 < nseg && S[sgi + 1].offset <= e0) ++sgi;
-    const ParamSeg& sg = S[sgi];
-    const bool whole = e0 + 4 <= n && e0 + 4 <= sg.offset + sg.numel;
-    if (whole) {
-      f32x4 wv = *reinterpret_cast<const f32x4*>(w + e0);
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + e0);
-      f32x4 mv = adam_ld4<NT>(m + e0);
-      f32x4 vv = adam_ld4<NT>(v + e0);
-      const float wd = wd_seg[sgi];
-      const float lrwd = lr * wd;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float wj = wv[j], mj = mv[j], vj = vv[j];
-        adam_elem(wj, gv[j], mj, vj, grad_scale, wd, lrwd, alpha, c, dec);
-        wv[j] = wj;
-        mv[j] = mj;
-        vv[j] = vj;
-      }
-      adam_st4<NT>(m + e0, mv);
-      adam_st4<NT>(v + e0, vv);
-      *reinterpret_cast<f32x4*>(w + e0) = wv;
-      if (bf && sg.bf_hwio >= 0) {
-        if (sg.kpad == sg.K && ((e0 - sg.offset) & 3) == 0) {
-          bf16x4 h = {(bf16)wv[0], (bf16)wv[1], (bf16)wv[2], (bf16)wv[3]};
-          *reinterpret_cast<bf16x4*>(bf + sg.bf_hwio + (e0 - sg.offset)) = h;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) write_hwio(sg, e0 + j, wv[j], bf);
-        }
-      }
-    } else {   // a vector straddling a segment end (e.g. a 10-class bias) or the tail
-      for (int j = 0; j < 4 && e0 + j < n; ++j) {
-        const long e = e0 + j;
-        const int sj_i = find_seg(S, nseg, e);
-        const ParamSeg& sj = S[sj_i];
-        const float wd = wd_seg[sj_i];
-        float wj = w[e], mj = m[e], vj = v[e];
-        adam_elem(wj, g[e], mj, vj, grad_scale, wd, lr * wd, alpha, c, dec);
-        m[e] = mj;
-        v[e] = vj;
-        w[e] = wj;
-        if (bf) write_hwio(sj, e, wj, bf);
-      }
-    }
-  }
+  const FlatWalk walk(sseg, segs, nseg, true);   // the table and the two rates
+  walk.run(w, n, bf, AdamStep<NT>{g, m, v, wd_seg, c, grad_scale, rate_s[0], rate_s[1],
+                                  decoupled != 0});   // (the mode: uniform over the launch)
 }
 
 void adam_update_pack(float* master, const float* grad, float* m, float* v, long n,
@@ -165,18 +127,15 @@ void adam_update_pack(float* master, const float* grad, float* m, float* v, long
                       const float* wd_seg, bf16* bf, float* lr_out, float* adam_out,
                       hipStream_t st) {
   if (n <= 0) return;
-  long blocks = ((n + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  const AdamCoef c{beta1, (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2),
-                   epsilon};
+  const AdamCoef c = adam_coef(beta1, beta2, epsilon);
   if (clip)
-    hipLaunchKernelGGL((adam_pack_kernel<true, ADAM_NT>), dim3((unsigned)blocks), dim3(256), 0, st,
+    hipLaunchKernelGGL((adam_pack_kernel<true, ADAM_NT>), dim3(flat_blocks(n)), dim3(256), 0, st,
                        master, grad, m, v, n, s, gstep, start_step, c, 1.f, clip, decoupled, segs,
                        nseg, wd_seg, bf, lr_out, adam_out);
   else
-    hipLaunchKernelGGL((adam_pack_kernel<false, ADAM_NT>), dim3((unsigned)blocks), dim3(256), 0,
-                       st, master, grad, m, v, n, s, gstep, start_step, c, grad_scale, clip,
-                       decoupled, segs, nseg, wd_seg, bf, lr_out, adam_out);
+    hipLaunchKernelGGL((adam_pack_kernel<false, ADAM_NT>), dim3(flat_blocks(n)), dim3(256), 0, st,
+                       master, grad, m, v, n, s, gstep, start_step, c, grad_scale, clip, decoupled,
+                       segs, nseg, wd_seg, bf, lr_out, adam_out);
   DTR_CHECK_LAUNCH();
 }
 

@@ -13,8 +13,10 @@
 //   clip_scale    one wave: the partials added in chunk order, norm and scale into the
 //                 two-float slot {norm, scale};
 //   sgd_clip_pack sgd_pack's update and HWIO re-pack with the gradient scaled by slot[1]
-//                 in place of the host grad_scale (optim_device.h); ohwi_pack follows as
-//                 after sgd_pack.
+//                 in place of the host grad_scale; ohwi_pack follows as after sgd_pack.
+// optim_device.h has the fp64 reduction of a workgroup (block_sum_f64) and sgd_pack_body, the
+// SGD step over the flat walk; clip_scale keeps its own loop over the partials, which
+// prefetches (one sum per chunk, thousands of chunks in one wave).
 // c = inf measures only: every finite norm is <= inf, so the scale is exactly 1.
 // Accumulation widths: a thread adds at most 17 squares in fp32 (4 float4s and one tail
 // scalar; lars_norms' bound of 18 covers it); from there on everything is fp64 -- the wave
@@ -28,15 +30,9 @@
 
 namespace dtr {
 
-__device__ __forceinline__ double clip_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
+// (no head and a fixed alignment: its own three lines in place of chunk_span)
 __global__ void __launch_bounds__(256)
 grad_sqnorm_kernel(const float* __restrict__ g, long long n, double* __restrict__ part) {
-  __shared__ double red[4];
   const int tid = threadIdx.x;
   const long long start = (long long)blockIdx.x * CLIP_CHUNK;   // a multiple of 4: aligned
   const long long rest = n - start;                             // > 0 (grid = ceil(n / chunk))
@@ -60,10 +56,7 @@ grad_sqnorm_kernel(const float* __restrict__ g, long long n, double* __restrict_
     for (int i = 0; i < 4; ++i) s += a[j][i] * a[j][i];
   }
   s += t * t;
-  const double d = clip_wave_sum_f64((double)s);
-  if ((tid & 63) == 0) red[tid >> 6] = d;
-  __syncthreads();
-  if (tid == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_sum_f64<1>({s}, part);
 }
 
 int clip_chunks(long long n) { return n <= 0 ? 0 : (int)((n + CLIP_CHUNK - 1) / CLIP_CHUNK); }
@@ -124,10 +117,7 @@ void sgd_clip_update_pack(float* master, const float* grad, float* mom, long n,
                           const LrSchedule& s, const long long* gstep, float momentum, float wd,
                           const float* clip, int use_momentum, const ParamSeg* segs, int nseg,
                           bf16* bf, float* lr_out, hipStream_t st) {
-  long blocks = ((n + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sgd_clip_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, master, grad,
+  hipLaunchKernelGGL(sgd_clip_pack_kernel, dim3(flat_blocks(n)), dim3(256), 0, st, master, grad,
                      mom, n, s, gstep, momentum, wd, clip, use_momentum, segs, nseg, bf, lr_out);
   DTR_CHECK_LAUNCH();
 }

@@ -10,8 +10,11 @@
 //                a fixed summation order, so the norms are bit-reproducible;
 //   lars_trust   one wave per tensor: its chunks' partials added in chunk order, the two
 //                norms and the trust ratio;
-//   lars_sgd_pack  sgd_pack's update and HWIO re-pack at the rate lr * trust[segment]
-//                (optim_device.h); ohwi_pack follows as after sgd_pack.
+//   lars_sgd_pack  sgd_pack's update and HWIO re-pack at the rate lr * trust[segment];
+//                ohwi_pack follows as after sgd_pack.
+// The control flow is optim_device.h's: chunk_span and block_sum_f64 (lars_norms),
+// seg_part_sums (lars_trust), sgd_pack_body's SgdStep<LARS> over the FlatWalk (lars_sgd_pack).
+// Its own are the squares, the closing formula of the trust ratio and the launchers.
 // Accumulation widths: a thread adds at most 18 squares in fp32 (4 float4s of the aligned
 // body, one head and one tail scalar); from there on everything is fp64 -- the wave
 // shuffles, the four waves, the chunks, the square roots and the ratio, which is rounded
@@ -23,41 +26,23 @@
 
 namespace dtr {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(256)
 lars_norms_kernel(const float* __restrict__ w, const float* __restrict__ g,
                   const ParamSeg* __restrict__ segs, const LarsSeg* __restrict__ lsegs,
                   const int* __restrict__ blk_seg, double* __restrict__ part) {
-  __shared__ double red[4][2];
   const int tid = threadIdx.x;
   const int si = blk_seg[blockIdx.x];
-  const long long off = segs[si].offset, numel = segs[si].numel;
-  const long long c = (long long)blockIdx.x - lsegs[si].chunk0;
-  // this chunk: [start, end) inside the segment -- never an element of a neighbour
-  const long long start = off + c * LARS_CHUNK;
-  const long long rest = numel - c * LARS_CHUNK;
-  const long long end = start + (rest < LARS_CHUNK ? rest : (long long)LARS_CHUNK);
-  // scalars up to the first 16-byte boundary, float4s, scalars after the last whole one
-  long long body0 = (start + 3) & ~3ll;
-  if (body0 > end) body0 = end;
-  const int head = (int)(body0 - start);          // < 4
-  const int nvec = (int)((end - body0) >> 2);     // <= LARS_CHUNK / 4 = 4 * 256
-  const long long tail0 = body0 + 4ll * nvec;
-  const int tail = (int)(end - tail0);            // < 4
+  const ChunkSpan ch = chunk_span(segs[si].offset, segs[si].numel,
+                                  (long long)blockIdx.x - lsegs[si].chunk0, LARS_CHUNK);
   float sw = 0.f, sg = 0.f;
-  f32x4 a[4], b[4];                               // 8 loads in flight
+  f32x4 a[4], b[4];                               // 8 loads in flight (nvec <= 4 * 256)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int k = tid + j * 256;
     a[j] = b[j] = f32x4{0.f, 0.f, 0.f, 0.f};      // (adding the zeros is exact)
-    if (k < nvec) {
-      a[j] = *reinterpret_cast<const f32x4*>(w + body0 + 4ll * k);
-      b[j] = *reinterpret_cast<const f32x4*>(g + body0 + 4ll * k);
+    if (k < ch.nvec) {
+      a[j] = *reinterpret_cast<const f32x4*>(w + ch.body0 + 4ll * k);
+      b[j] = *reinterpret_cast<const f32x4*>(g + ch.body0 + 4ll * k);
     }
   }
 #pragma unroll
@@ -68,26 +53,17 @@ lars_norms_kernel(const float* __restrict__ w, const float* __restrict__ g,
       sg += b[j][i] * b[j][i];
     }
   }
-  if (tid < head) {
-    const float x = w[start + tid], y = g[start + tid];
+  if (tid < ch.head) {
+    const float x = w[ch.start + tid], y = g[ch.start + tid];
     sw += x * x;
     sg += y * y;
   }
-  if (tid < tail) {
-    const float x = w[tail0 + tid], y = g[tail0 + tid];
+  if (tid < ch.tail) {
+    const float x = w[ch.tail0 + tid], y = g[ch.tail0 + tid];
     sw += x * x;
     sg += y * y;
   }
-  const double dw = wave_sum_f64((double)sw), dg = wave_sum_f64((double)sg);
-  if ((tid & 63) == 0) {
-    red[tid >> 6][0] = dw;
-    red[tid >> 6][1] = dg;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    part[2 * (long long)blockIdx.x] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-    part[2 * (long long)blockIdx.x + 1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-  }
+  block_sum_f64<2>({sw, sg}, part);
 }
 
 void lars_norms(const float* master, const float* grad, const ParamSeg* segs,
@@ -103,29 +79,11 @@ __global__ void __launch_bounds__(64)
 lars_trust_kernel(const double* __restrict__ part, const LarsSeg* __restrict__ lsegs, float eeta,
                   float wd, float epsilon, float grad_scale, float* __restrict__ trust,
                   float* __restrict__ wn, float* __restrict__ gn) {
-  __shared__ double sh[64][2];
-  const int lane = threadIdx.x;
   const int si = blockIdx.x;
   const LarsSeg ls = lsegs[si];
-  double sw = 0.0, sg = 0.0;
-  // 64 partials at a time through LDS (coalesced loads), added by one lane in chunk order
-  for (int c0 = 0; c0 < ls.nchunks; c0 += 64) {
-    const int c = c0 + lane;
-    if (c < ls.nchunks) {
-      sh[lane][0] = part[2 * (ls.chunk0 + c)];
-      sh[lane][1] = part[2 * (ls.chunk0 + c) + 1];
-    }
-    __syncthreads();
-    if (lane == 0) {
-      const int m = min(64, ls.nchunks - c0);
-      for (int j = 0; j < m; ++j) {
-        sw += sh[j][0];
-        sg += sh[j][1];
-      }
-    }
-    __syncthreads();
-  }
-  if (lane == 0) {
+  double sw, sg;
+  seg_part_sums(part, ls, sw, sg);
+  if (threadIdx.x == 0) {
     const double w_n = sqrt(sw), g_n = fabs((double)grad_scale) * sqrt(sg);
     float t = 1.f;
     if (!ls.skip && w_n > 0.0 && g_n > 0.0)
@@ -161,10 +119,7 @@ void lars_update_pack(float* master, const float* grad, float* mom, long n, cons
                       const long long* gstep, float momentum, float wd, float grad_scale,
                       const ParamSeg* segs, int nseg, const float* trust, bf16* bf,
                       float* lr_out, hipStream_t st) {
-  long blocks = ((n + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(lars_sgd_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, master, grad,
+  hipLaunchKernelGGL(lars_sgd_pack_kernel, dim3(flat_blocks(n)), dim3(256), 0, st, master, grad,
                      mom, n, s, gstep, momentum, wd, grad_scale, segs, nseg, trust, bf, lr_out);
   DTR_CHECK_LAUNCH();
 }

@@ -16,7 +16,8 @@
 
 namespace dtr {
 
-// (the update itself is optim_device.h's sgd_pack_body, shared with lars.hip)
+// (the update is optim_device.h's sgd_pack_body: SgdStep over the FlatWalk, shared with
+// lars.hip and clip.hip)
 __global__ void __launch_bounds__(256)
 sgd_pack_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ mom,
                 long n, LrSchedule sched, const long long* __restrict__ gstep, float momentum,
@@ -31,12 +32,8 @@ void sgd_update_pack(float* master, const float* grad, float* mom, long n, const
                      const long long* gstep, float momentum, float wd, float grad_scale,
                      int use_momentum, const ParamSeg* segs, int nseg, bf16* bf, float* lr_out,
                      int update, hipStream_t st) {
-  long blocks = ((n + 3) / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sgd_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, master, grad, mom,
-                     n, s, gstep, momentum, wd, grad_scale, use_momentum, segs, nseg, bf, lr_out,
-                     update);
+  hipLaunchKernelGGL(sgd_pack_kernel, dim3(flat_blocks(n)), dim3(256), 0, st, master, grad, mom, n,
+                     s, gstep, momentum, wd, grad_scale, use_momentum, segs, nseg, bf, lr_out, update);
   DTR_CHECK_LAUNCH();
 }
 

@@ -36,6 +36,20 @@ def _resources(src):
     return rows
 
 
+OPTIM_SOURCES = tuple(os.path.join(CSRC, f + ".hip") for f in ("optim", "lars", "clip", "adam", "lamb"))
+
+
+def optimizer_resources():
+    """[(kernel function name, {remark: value})] over the optimizer files: the name demangled
+    as far as the identifier, so a template's instantiations share one."""
+    rows = []
+    for src in OPTIM_SOURCES:
+        for name, r in _resources(src).items():
+            m = re.match(r"_ZN3dtr\d+([a-z0-9_]+?_kernel)", name)
+            rows.append((m.group(1) if m else name, r))
+    return rows
+
+
 def prn_resources():
     """{kernel name: {remark: value}} over the persistent kernels' three files."""
     rows = {}

@@ -248,3 +248,28 @@ def test_optimizer_kernels_have_no_spills(src):
     for name, r in kernels.items():
         assert int(r["VGPRs Spill"]) == 0, (name, r)
         assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
+
+
+# kernel: (instantiations, waves per SIMD before the walks were shared in optim_device.h)
+WALK_KERNELS = {"sgd_pack_kernel": (1, 4), "lars_sgd_pack_kernel": (1, 4),
+                "sgd_clip_pack_kernel": (1, 4), "adam_pack_kernel": (2, 4),
+                "lamb_pack_kernel": (1, 4), "lars_norms_kernel": (1, 7),
+                "lamb_moments_norms_kernel": (2, 3), "lars_trust_kernel": (1, 8),
+                "lamb_trust_kernel": (1, 8), "grad_sqnorm_kernel": (1, 8),
+                "clip_scale_kernel": (1, 8)}
+
+
+@pytest.mark.skipif(not kr.have_compiler(), reason="no ROCm compiler")
+def test_shared_walks_keep_the_optimizer_kernels_occupancy():
+    """The flat walk, the chunk reduction and the partial sums are force-inlined templates of
+    optim_device.h: no kernel that uses them may spill, use scratch or hold fewer waves than
+    its own copy did (profiles/optim_walk.md; VGPR and SGPR counts are printed, not pinned)."""
+    rows = [(n, r) for n, r in kr.optimizer_resources() if n in WALK_KERNELS]
+    assert {n: sum(m == n for m, _ in rows) for n in WALK_KERNELS} == \
+        {n: k for n, (k, _) in WALK_KERNELS.items()}
+    for name, r in rows:
+        print(f"{name}: VGPRs {r['VGPRs']} SGPRs {r['TotalSGPRs']} "
+              f"waves/SIMD {r['Occupancy [waves/SIMD]']}")
+        assert int(r["VGPRs Spill"]) == 0, (name, r)
+        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
+        assert int(r["Occupancy [waves/SIMD]"]) >= WALK_KERNELS[name][1], (name, r)

@@ -908,6 +908,40 @@ static Launch mk_adam_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, lo
                                    adam_out, kPiecewise);
 }
 
+// lion_update_pack: adam_update_pack's alignment and coefficient checks; clip as there
+static Launch mk_lion_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, long n, float init,
+                                        long long warm_steps, float warm_from, float warm_to,
+                                        std::vector<long long> bounds, std::vector<float> vals,
+                                        ptr_t gstep, float beta1, float beta2, float grad_scale,
+                                        ptr_t clip, ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
+                                        ptr_t lr_out, LrDecayArgs decay) {
+  if ((master | grad | m) & 15)
+    throw std::invalid_argument("lion_update_pack: master, grad and m must be 16-byte aligned");
+  if (!master || !grad || !m || !segs || !wd_seg || !gstep)
+    throw std::invalid_argument("lion_update_pack: null buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("lion_update_pack: n >= 0 and nseg > 0");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    throw std::invalid_argument("lion_update_pack: beta1 and beta2 in [0, 1)");
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    lion_update_pack(P<float>(master), P<const float>(grad), P<float>(m), n, sc,
+                     P<const long long>(gstep), beta1, beta2, grad_scale, P<const float>(clip),
+                     P<const ParamSeg>(segs), nseg, P<const float>(wd_seg), P<bf16>(bf),
+                     P<float>(lr_out), s);
+  };
+}
+
+static Launch mk_lion_update_pack(ptr_t master, ptr_t grad, ptr_t m, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float beta1, float beta2, float grad_scale,
+                                  ptr_t clip, ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
+                                  ptr_t lr_out) {
+  return mk_lion_update_pack_decay(master, grad, m, n, init, warm_steps, warm_from, warm_to,
+                                   bounds, vals, gstep, beta1, beta2, grad_scale, clip, segs,
+                                   nseg, wd_seg, bf, lr_out, kPiecewise);
+}
+
 // The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
 static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
                       const std::string& decay_mode) {
@@ -1768,6 +1802,8 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack_decay);
   def_op(m, plan, "adam_update_pack", mk_adam_update_pack);
   def_op(m, plan, "adam_update_pack", mk_adam_update_pack_decay);
+  def_op(m, plan, "lion_update_pack", mk_lion_update_pack);
+  def_op(m, plan, "lion_update_pack", mk_lion_update_pack_decay);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
   def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);

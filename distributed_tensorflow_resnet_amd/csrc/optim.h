@@ -124,6 +124,14 @@ void lamb_update_pack(float* master, const float* m, const float* v, long n,
                       float beta1, float beta2, float epsilon, int decoupled,
                       const ParamSeg* segs, int nseg, const float* wd_seg, const float* trust,
                       bf16* bf, float* lr_out, float* adam_out, hipStream_t st);
+// Lion (lion.hip) in one launch of adam_update_pack's shape: c = beta1 m + (1 - beta1) g',
+// w' = (w - lr sign(c)) - (lr wd_seg) w, m' = beta2 m + (1 - beta2) g' with g' the gradient
+// scaled by grad_scale or, clip non-null, by the device value clip[1].  m (the momentum
+// buffer) is the only state.  master, grad and m must be 16-byte aligned; 0 <= beta < 1.
+void lion_update_pack(float* master, const float* grad, float* m, long n, const LrSchedule& s,
+                      const long long* gstep, float beta1, float beta2, float grad_scale,
+                      const float* clip, const ParamSeg* segs, int nseg, const float* wd_seg,
+                      bf16* bf, float* lr_out, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

@@ -24,8 +24,8 @@ from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
-from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_state
-from .layout import (check_adam_trust, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
+from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_lion, tf_to_state
+from .layout import (check_adam_trust, check_lion, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase)
 
@@ -86,15 +86,19 @@ class GPUBackend:
         if eng.adam:
             adam = {"v": eng.adam_v, "start_step": int(eng.adam_start.item()),
                     "beta1": eng.adam_beta1, "beta2": eng.adam_beta2}
-        return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam)
+        return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam,
+                           lion=eng.lion)
 
     def load_state(self, tensors):
         eng = self.engine
         # adamw: the momentum buffer is the first moment, loaded from the Adam slots
-        gs = tf_to_state(tensors, eng.params, None if eng.adam else eng.mom, strict=True,
-                         ema=eng.ema)
+        # (lion: it is m, loaded from the Lion slots)
+        gs = tf_to_state(tensors, eng.params, None if eng.adam or eng.lion else eng.mom,
+                         strict=True, ema=eng.ema)
         if eng.adam:
             eng.set_adam_start(tf_to_adam(tensors, eng.params, eng.mom, eng.adam_v))
+        if eng.lion:
+            tf_to_lion(tensors, eng.params, eng.mom)
         eng.sync_from_params(ema_loaded=True)
         self._host_step = gs
 
@@ -150,7 +154,9 @@ class CPUBackend:
                  adam_decay_skip: str = "none", adam_trust="off",
                  adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
-                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero",
+                 lion_beta1: float = 0.9, lion_beta2: float = 0.99,
+                 lion_decay_skip: str = "none"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -214,7 +220,7 @@ class CPUBackend:
         self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars or adamw, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw or lion, got {optimizer!r}")
         # adamw, csrc/adam.hip's expressions in fp32 torch: the first moment in `mom`, the
         # second in `adam_v`; t counts from adam_start
         self.adam = optimizer == "adamw"
@@ -231,6 +237,14 @@ class CPUBackend:
             wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
                                       adam_decay_skip)
             self.adam_wd = torch.repeat_interleave(
+                torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
+        # lion, csrc/lion.hip's expressions in fp32 torch: m in `mom`, nothing else kept
+        self.lion = optimizer == "lion"
+        self.lion_beta1, self.lion_beta2 = check_lion(lion_beta1, lion_beta2, lion_decay_skip)
+        if self.lion:
+            wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
+                                      lion_decay_skip)
+            self.lion_wd = torch.repeat_interleave(
                 torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
         if lars_skip not in ("vectors", "none"):
             raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
@@ -309,8 +323,8 @@ class CPUBackend:
                 self.dist.all_reduce_sum(g)
         lr = self.sched.at(self.step_count)
         with torch.no_grad():
-            if self.adam:
-                gp = None   # (its decay is per tensor and per mode: _adam_update)
+            if self.adam or self.lion:
+                gp = None   # (its decay is per tensor and per mode: _adam_update, _lion_update)
             elif self.clip_grad_norm > 0:
                 # after the all-reduce: every rank forms the same norm from the same bits
                 gp = self._clip_scale(g) * g + self.wd * master
@@ -320,6 +334,8 @@ class CPUBackend:
                 self._lamb_update(master, g, lr)
             elif self.adam:
                 self._adam_update(master, g, lr)
+            elif self.lion:
+                self._lion_update(master, g, lr)
             elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
@@ -369,6 +385,21 @@ class CPUBackend:
     def adam_state(self):
         """(t, alpha) of the last step (None: not adamw, or no step yet)."""
         return self._adam_state
+
+    def _lion_update(self, master, g, lr):
+        """csrc/lion.hip's update in fp32 torch: every product, sum and difference on its own."""
+        f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
+        b1, b2 = f(self.lion_beta1), f(self.lion_beta2)
+        omb1, omb2 = f(1.0 - float(b1)), f(1.0 - float(b2))
+        lr32 = f(lr)
+        w, m = master, self.mom
+        gp = g * self._clip_scale(g) if self.clip_grad_norm > 0 else g.clone()
+        c = b1 * m + omb1 * gp
+        one = torch.ones_like(c)
+        u = torch.where(c > 0, one, torch.where(c < 0, -one, c))   # +-0 and NaN stay
+        dec = (lr32 * self.lion_wd) * w   # decoupled: of the old w
+        m.copy_(b2 * m + omb2 * gp)
+        w.copy_((w - lr32 * u) - dec)
 
     def _lamb_update(self, master, g, lr):
         """csrc/lamb.hip's three stages in fp32 torch (the norms in fp64, as the kernels'
@@ -525,6 +556,8 @@ class CPUBackend:
             m["grad_norm"], m["clip_scale"] = self._clip_state
         if self._adam_state is not None:
             m["adam_alpha"] = self._adam_state[1]
+        if self.lion:
+            m["optimizer"] = "lion"
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -548,14 +581,18 @@ class CPUBackend:
         if self.adam:
             adam = {"v": self.adam_v, "start_step": self.adam_start, "beta1": self.adam_beta1,
                     "beta2": self.adam_beta2}
-        return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam)
+        return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam,
+                           lion=self.lion)
 
     def load_state(self, tensors):
         with torch.no_grad():
-            self.step_count = tf_to_state(tensors, self.store, None if self.adam else self.mom,
+            self.step_count = tf_to_state(tensors, self.store,
+                                          None if self.adam or self.lion else self.mom,
                                           ema=self.ema)
             if self.adam:
                 self.adam_start = tf_to_adam(tensors, self.store, self.mom, self.adam_v)
+            if self.lion:
+                tf_to_lion(tensors, self.store, self.mom)
 
     def broadcast_parameters(self, src: int = 0):
         if self.dist is not None and self.world > 1:
@@ -596,14 +633,17 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  adam_decay: str = "decoupled", adam_decay_skip: str = "none",
                  adam_trust="off", adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
-                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero",
+                 lion_beta1: float = 0.9, lion_beta2: float = 0.99,
+                 lion_decay_skip: str = "none"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
         device = "gpu" if torch.cuda.is_available() else "cpu"
     adam = dict(adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
                 adam_decay=adam_decay, adam_decay_skip=adam_decay_skip, adam_trust=adam_trust,
-                adam_trust_skip=adam_trust_skip)
+                adam_trust_skip=adam_trust_skip, lion_beta1=lion_beta1, lion_beta2=lion_beta2,
+                lion_decay_skip=lion_decay_skip)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

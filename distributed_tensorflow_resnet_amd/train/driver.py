@@ -235,7 +235,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            adam_beta1=flags.adam_beta1, adam_beta2=flags.adam_beta2,
                            adam_epsilon=flags.adam_epsilon, adam_decay=flags.adam_decay,
                            adam_decay_skip=flags.adam_decay_skip,
-                           adam_trust=flags.adam_trust, adam_trust_skip=flags.adam_trust_skip)
+                           adam_trust=flags.adam_trust, adam_trust_skip=flags.adam_trust_skip,
+                           lion_beta1=flags.lion_beta1, lion_beta2=flags.lion_beta2,
+                           lion_decay_skip=flags.lion_decay_skip)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

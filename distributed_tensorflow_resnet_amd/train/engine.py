@@ -54,7 +54,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob, check_erase,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
-                     OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary)
+                     OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
+                     OPT_FUSED_LION_REASON, check_lion)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -135,7 +136,9 @@ class Engine:
                  adam_decay_skip: str = "none", adam_trust="off",
                  adam_trust_skip: str = "vectors", erase_prob: float = 0.0,
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
-                 erase_aspect_min: float = 0.3, erase_fill: str = "zero"):
+                 erase_aspect_min: float = 0.3, erase_fill: str = "zero",
+                 lion_beta1: float = 0.9, lion_beta2: float = 0.99,
+                 lion_decay_skip: str = "none"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -150,7 +153,7 @@ class Engine:
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars or adamw, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw or lion, got {optimizer!r}")
         if lars_skip not in LARS_SKIPS:
             raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
         # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
@@ -172,6 +175,12 @@ class Engine:
         # move between trust on and off.  Off: nothing allocated, every plan as adamw's
         self.lamb = check_adam_trust(adam_trust, adam_trust_skip, optimizer)
         self.adam_trust_skip = adam_trust_skip
+        # lion: the sign of an interpolated momentum with decoupled weight decay, one launch on
+        # the generic optimizer path (csrc/lion.hip).  Its only state, an average of the
+        # gradient, lives in the momentum buffer; nothing else is allocated but the decay table
+        self.lion = optimizer == "lion"
+        self.lion_beta1, self.lion_beta2 = check_lion(lion_beta1, lion_beta2, lion_decay_skip)
+        self.lion_decay_skip = lion_decay_skip
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -354,6 +363,9 @@ class Engine:
         if self.adam and self.opt_fused:   # (before clipping: with both, adamw is the reason)
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_LAMB_REASON if self.lamb else OPT_FUSED_ADAM_REASON
+        if self.lion and self.opt_fused:   # (before clipping, as adamw)
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_LION_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -463,6 +475,10 @@ class Engine:
             # the per-segment decay the kernel reads, as the LARS kernel reads trust[]
             self.adam_wd = torch.from_numpy(adam_decay_table(
                 [s.shape for s in ps.train_slots], self.wd, self.adam_decay_skip)).to(dev)
+        self.lion_wd = None
+        if self.lion:   # the same table under lion_decay_skip
+            self.lion_wd = torch.from_numpy(adam_decay_table(
+                [s.shape for s in ps.train_slots], self.wd, self.lion_decay_skip)).to(dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:
             # chunk partials and the {norm, scale} slot: fixed pointers
@@ -1090,6 +1106,8 @@ class Engine:
             m["grad_norm"], m["clip_scale"] = self.clip_out.cpu().tolist()
         if self.adam:
             m["adam_alpha"] = float(self.adam_out[1].item())
+        if self.lion:
+            m["optimizer"] = "lion"
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8

@@ -96,6 +96,8 @@ class LoggingTensorHook(Hook):
                     if "grad_norm" in m else "")   # --clip_grad_norm
             if "adam_alpha" in m:   # --optimizer adamw
                 clip += f", adam alpha = {m['adam_alpha']:.6g}"
+            if m.get("optimizer") == "lion":   # --optimizer lion
+                clip += ", optimizer: lion"
             mix = ""
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"

@@ -134,7 +134,7 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
-OPTIMIZERS = ("mom", "sgd", "lars", "adamw")
+OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion")
 ADAM_DECAYS = ("decoupled", "l2")
 ADAM_DECAY_SKIPS = ("none", "vectors")
 OPT_FUSED_ADAM_REASON = ("optimizer adamw: the one-launch optimizer is SGD-momentum; adamw takes "
@@ -186,6 +186,28 @@ def check_adam_trust(trust="off", trust_skip: str = "vectors", optimizer: str = 
         raise ValueError(f"adam_trust on is layer-wise adaptation of adamw: it cannot be combined "
                          f"with optimizer {optimizer!r}")
     return trust == "on"
+
+
+OPT_FUSED_LION_REASON = ("optimizer lion: the one-launch optimizer is SGD-momentum; lion takes "
+                         "the generic optimizer launches")
+
+
+def check_lion(beta1, beta2, decay_skip: str = "none"):
+    """The lion flags as both backends take them: (beta1, beta2) as floats, both in [0, 1)
+    (in fp32 too, as the kernel's float arguments); decay_skip as adam_decay_skip."""
+    try:
+        b1, b2 = float(beta1), float(beta2)
+    except (TypeError, ValueError):
+        raise ValueError(f"lion_beta1 and lion_beta2 must be numbers, got "
+                         f"{beta1!r}, {beta2!r}") from None
+    for name, b in (("lion_beta1", b1), ("lion_beta2", b2)):
+        if not 0.0 <= b < 1.0:   # NaN included
+            raise ValueError(f"{name} must be in [0, 1), got {b!r}")
+    if float(np.float32(b1)) >= 1.0 or float(np.float32(b2)) >= 1.0:
+        raise ValueError(f"lion_beta1 and lion_beta2 must be below 1 in fp32, got {b1!r}, {b2!r}")
+    if decay_skip not in ADAM_DECAY_SKIPS:
+        raise ValueError(f"lion_decay_skip must be one of {ADAM_DECAY_SKIPS}, got {decay_skip!r}")
+    return b1, b2
 
 
 def lamb_bias_corrections(t: int, beta1: float, beta2: float):

@@ -633,6 +633,29 @@ class StepRecorder:
                     else:
                         out.op_buffers[i1] = (gb | pb | {"adam", "lr", "gstep"}
                                               | ({"clip"} if clip else set()))
+            elif e.lion:
+                # one launch (csrc/lion.hip), as adamw's: with clipping the norm launches go in
+                # front and the update reads the scale from the device slot
+                clip, co = e.clip_grad_norm > 0, 0
+                i0 = plan.size()
+                if clip:
+                    co = e.clip_out.data_ptr()
+                    plan.grad_sqnorm(grad, e.params.n_train, e.clip_part.data_ptr())
+                    plan.clip_scale(e.clip_part.data_ptr(), e.clip_chunks,
+                                    float(np.float32(e.clip_grad_norm)), co)
+                i1 = plan.lion_update_pack(master, grad, mom, e.params.n_train,
+                                           *e.sched.launch_args(), e.gstep.data_ptr(),
+                                           e.lion_beta1, e.lion_beta2, 1.0, co,
+                                           e.segs.data_ptr(), e.nseg, e.lion_wd.data_ptr(),
+                                           e.wbf.data_ptr(), sp + 8, *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
+                    if clip:
+                        out.op_buffers[i0] = gb | {"clip"}
+                        out.op_buffers[i0 + 1] = {"clip"}
+                    out.op_buffers[i1] = (gb | pb | {"lr", "gstep"}
+                                          | ({"clip"} if clip else set()))
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

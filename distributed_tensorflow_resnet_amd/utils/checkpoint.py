@@ -7,7 +7,8 @@ under its TF name (HWIO conv kernels, BN gamma/beta, dense kernel/bias), its
 ``global_step``; a run with ``--ema_decay`` adds ``<name>/ExponentialMovingAverage`` per
 trainable (tf.train.ExponentialMovingAverage's shadow variables); a run with ``--optimizer
 adamw`` saves ``<name>/Adam`` and ``<name>/Adam_1`` in place of ``<name>/Momentum``, plus
-``beta1_power``, ``beta2_power`` and ``adam_start_step``.  ``max_to_keep``
+``beta1_power``, ``beta2_power`` and ``adam_start_step``; a run with ``--optimizer lion``
+saves ``<name>/Lion`` in place of ``<name>/Momentum`` (no extra scalars).  ``max_to_keep``
 = 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
@@ -29,6 +30,9 @@ ADAM_M_SUFFIX, ADAM_V_SUFFIX = "/Adam", "/Adam_1"   # tf.train.AdamOptimizer's s
 ADAM_START = "adam_start_step"                     # ours: the step the moments count from
 
 
+LION_SUFFIX = "/Lion"   # lion's one slot: an average of the gradient, not mom's accumulator
+
+
 def adam_beta_powers(t_done: int, beta1: float, beta2: float):
     """TF 1.12's beta1_power / beta2_power variables after t_done Adam steps: b^(t_done + 1)
     (they start at b and are multiplied by b after every step), from the fp32 betas in fp64,
@@ -38,21 +42,23 @@ def adam_beta_powers(t_done: int, beta1: float, beta2: float):
 
 
 def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
-                ema: torch.Tensor | None = None, adam: dict | None = None) -> dict[str, np.ndarray]:
+                ema: torch.Tensor | None = None, adam: dict | None = None,
+                lion: bool = False) -> dict[str, np.ndarray]:
     """ParamStore (+flat momentum, +flat EMA shadows, in the same layout) -> {TF name: array}.
     ``ema`` adds ``<name>/ExponentialMovingAverage`` per trainable; without it the entries
     are exactly the reference's.  ``adam`` (an adamw run: {"v": flat second moment,
     "start_step", "beta1", "beta2"}): `momentum` is the first moment and goes out as
     ``<name>/Adam``, v as ``<name>/Adam_1`` (TF's slot names), no ``/Momentum``; plus the fp32
     scalars beta1_power / beta2_power (TF 1.12's variables after global_step - start_step
-    Adam steps) and the int64 ``adam_start_step``, which restore goes by."""
+    Adam steps) and the int64 ``adam_start_step``, which restore goes by.  ``lion`` (a lion
+    run): `momentum` is its m and goes out as ``<name>/Lion``, no ``/Momentum``."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
     mom = momentum.detach().float().cpu().numpy() if momentum is not None else None
     sh = ema.detach().float().cpu().numpy() if ema is not None else None
     v = adam["v"].detach().float().cpu().numpy() if adam is not None else None
-    m_suffix = ADAM_M_SUFFIX if adam is not None else "/Momentum"
+    m_suffix = ADAM_M_SUFFIX if adam is not None else LION_SUFFIX if lion else "/Momentum"
     for s in store.train_slots:
         out[s.name] = master[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if mom is not None:
@@ -96,6 +102,24 @@ def tf_to_adam(tensors: dict, store, m: torch.Tensor, v: torch.Tensor) -> int:
                 raise ValueError(f"{s.name + suffix}: {a.size} elements, expected {s.numel}")
             buf.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
     return int(np.asarray(tensors.get(ADAM_START, 0)))
+
+
+def tf_to_lion(tensors: dict, store, m: torch.Tensor) -> None:
+    """Load the m of a lion run from {TF name: array}.  With every ``<name>/Lion`` present it
+    is loaded; otherwise (e.g. a `mom` checkpoint, whose ``/Momentum`` is an accumulator and
+    is ignored) m is zero and one log line says so."""
+    absent = [s.name for s in store.train_slots if s.name + LION_SUFFIX not in tensors]
+    if absent:
+        print(f"INFO:tensorflow:checkpoint has no Lion slots for {len(absent)} of "
+              f"{len(store.train_slots)} variables (e.g. {absent[0] + LION_SUFFIX}): the momentum "
+              "starts from zero", flush=True)
+        m.data.zero_()
+        return
+    for s in store.train_slots:
+        a = np.asarray(tensors[s.name + LION_SUFFIX], dtype=np.float32).reshape(-1)
+        if a.size != s.numel:
+            raise ValueError(f"{s.name + LION_SUFFIX}: {a.size} elements, expected {s.numel}")
+        m.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
 
 
 def ema_weights(tensors: dict, store) -> dict:

@@ -15,6 +15,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --optimizer adamw  Adam with decoupled (or l2) weight decay in one device launch:
                      --adam_beta1/_beta2/_epsilon, --adam_decay, --adam_decay_skip;
                      --adam_trust on makes it LAMB (per-tensor trust ratios), --adam_trust_skip
+  --optimizer lion   Lion (sign of an interpolated momentum, one state buffer) in one device
+                     launch: --lion_beta1/_beta2, --lion_decay_skip
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -80,6 +82,16 @@ def _adam_beta(v) -> float:
         raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
     if not 0.0 <= f < 1.0:   # NaN included
         raise argparse.ArgumentTypeError(f"an Adam beta must be in [0, 1), got {v!r}")
+    return f
+
+
+def _lion_beta(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < 1.0:   # NaN included
+        raise argparse.ArgumentTypeError(f"a Lion beta must be in [0, 1), got {v!r}")
     return f
 
 
@@ -185,6 +197,13 @@ class FlagParser(argparse.ArgumentParser):
             try:   # (the fp32 values the kernel gets: a beta that rounds to 1, an epsilon to 0)
                 check_adam(ns.adam_beta1, ns.adam_beta2, ns.adam_epsilon, ns.adam_decay,
                            ns.adam_decay_skip)
+            except ValueError as e:
+                self.error(str(e))
+        if hasattr(ns, "lion_beta1"):
+            from ..train.layout import check_lion
+
+            try:   # (the fp32 values the kernel gets: a beta that rounds to 1)
+                check_lion(ns.lion_beta1, ns.lion_beta2, ns.lion_decay_skip)
             except ValueError as e:
                 self.error(str(e))
         if hasattr(ns, "adam_trust"):
@@ -294,13 +313,16 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw"),
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion"),
                    help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
                         "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
                         "epsilon) (layer-wise adaptive rate scaling, for large global batches).  "
                         "adamw: Adam (tf.train.AdamOptimizer's form) with decoupled weight "
                         "decay; the presets' learning rates are SGD rates, so set --lr_peak "
-                        "(e.g. 1e-3) or --lr_value_scale with it.")
+                        "(e.g. 1e-3) or --lr_value_scale with it.  lion: the sign of an "
+                        "interpolated momentum (Chen et al. 2023) with decoupled weight decay "
+                        "and one state buffer; every element moves by lr, so set a rate well "
+                        "below adamw's (the paper: 3-10x) and a correspondingly larger decay.")
     p.add_argument("--adam_beta1", type=_adam_beta, default=0.9,
                    help="adamw: decay of the first moment, in [0, 1).")
     p.add_argument("--adam_beta2", type=_adam_beta, default=0.999,
@@ -324,6 +346,13 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="--adam_trust on: tensors that are not adapted (trust = 1): 'vectors' = "
                         "every rank-1 tensor (BN gamma / beta, the dense bias), 'none' = adapt "
                         "them too.  Unused with --adam_trust off.")
+    p.add_argument("--lion_beta1", type=_lion_beta, default=0.9,
+                   help="lion: weight of the momentum in the interpolation whose sign is the "
+                        "update, in [0, 1).")
+    p.add_argument("--lion_beta2", type=_lion_beta, default=0.99,
+                   help="lion: decay of the momentum, in [0, 1).")
+    p.add_argument("--lion_decay_skip", default="none", choices=("none", "vectors"),
+                   help="lion: tensors without weight decay, as --adam_decay_skip.")
     p.add_argument("--lars_eeta", type=float, default=0.001,
                    help="LARS trust coefficient.")
     p.add_argument("--lars_epsilon", type=float, default=0.0,

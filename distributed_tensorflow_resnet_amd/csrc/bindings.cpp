@@ -942,6 +942,56 @@ static Launch mk_lion_update_pack(ptr_t master, ptr_t grad, ptr_t m, long n, flo
                                    nseg, wd_seg, bf, lr_out, kPiecewise);
 }
 
+// rmsprop_update_pack: lion_update_pack's alignment and coefficient checks, adam_update_pack's
+// epsilon and decay-mode ("l2" | "decoupled") checks; mg is needed only when centered
+static Launch mk_rmsprop_update_pack_decay(ptr_t master, ptr_t grad, ptr_t ms, ptr_t mg,
+                                           ptr_t mom, long n, float init, long long warm_steps,
+                                           float warm_from, float warm_to,
+                                           std::vector<long long> bounds, std::vector<float> vals,
+                                           ptr_t gstep, float rho, float momentum, float epsilon,
+                                           float grad_scale, ptr_t clip, int centered,
+                                           std::string decay_mode, ptr_t segs, int nseg,
+                                           ptr_t wd_seg, ptr_t bf, ptr_t lr_out,
+                                           LrDecayArgs decay) {
+  if ((master | grad | ms | mom | (centered ? mg : 0)) & 15)
+    throw std::invalid_argument(
+        "rmsprop_update_pack: master, grad, ms, mom (and mg) must be 16-byte aligned");
+  if (!master || !grad || !ms || !mom || !segs || !wd_seg || !gstep)
+    throw std::invalid_argument("rmsprop_update_pack: null buffer");
+  if (centered && !mg)
+    throw std::invalid_argument("rmsprop_update_pack: centered needs the mg buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("rmsprop_update_pack: n >= 0 and nseg > 0");
+  if (!(rho >= 0.f && rho < 1.f) || !(momentum >= 0.f && momentum < 1.f))
+    throw std::invalid_argument("rmsprop_update_pack: rho and momentum in [0, 1)");
+  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
+    throw std::invalid_argument("rmsprop_update_pack: epsilon must be positive and finite");
+  if (decay_mode != "decoupled" && decay_mode != "l2")
+    throw std::invalid_argument("rmsprop_update_pack: decay mode '" + decay_mode +
+                                "' (l2, decoupled)");
+  const int decoupled = decay_mode == "decoupled";
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    rmsprop_update_pack(P<float>(master), P<const float>(grad), P<float>(ms), P<float>(mg),
+                        P<float>(mom), n, sc, P<const long long>(gstep), rho, momentum, epsilon,
+                        grad_scale, P<const float>(clip), centered != 0, decoupled,
+                        P<const ParamSeg>(segs), nseg, P<const float>(wd_seg), P<bf16>(bf),
+                        P<float>(lr_out), s);
+  };
+}
+
+static Launch mk_rmsprop_update_pack(ptr_t master, ptr_t grad, ptr_t ms, ptr_t mg, ptr_t mom,
+                                     long n, float init, long long warm_steps, float warm_from,
+                                     float warm_to, std::vector<long long> bounds,
+                                     std::vector<float> vals, ptr_t gstep, float rho,
+                                     float momentum, float epsilon, float grad_scale, ptr_t clip,
+                                     int centered, std::string decay_mode, ptr_t segs, int nseg,
+                                     ptr_t wd_seg, ptr_t bf, ptr_t lr_out) {
+  return mk_rmsprop_update_pack_decay(master, grad, ms, mg, mom, n, init, warm_steps, warm_from,
+                                      warm_to, bounds, vals, gstep, rho, momentum, epsilon,
+                                      grad_scale, clip, centered, decay_mode, segs, nseg, wd_seg,
+                                      bf, lr_out, kPiecewise);
+}
+
 // The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
 static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
                       const std::string& decay_mode) {
@@ -1804,6 +1854,8 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "adam_update_pack", mk_adam_update_pack_decay);
   def_op(m, plan, "lion_update_pack", mk_lion_update_pack);
   def_op(m, plan, "lion_update_pack", mk_lion_update_pack_decay);
+  def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack);
+  def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack_decay);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
   def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);

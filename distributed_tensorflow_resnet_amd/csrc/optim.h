@@ -132,6 +132,18 @@ void lion_update_pack(float* master, const float* grad, float* m, long n, const 
                       const long long* gstep, float beta1, float beta2, float grad_scale,
                       const float* clip, const ParamSeg* segs, int nseg, const float* wd_seg,
                       bf16* bf, float* lr_out, hipStream_t st);
+// RMSProp in TF 1.12's form (rmsprop.hip) in one launch of adam_update_pack's shape:
+// ms' = rho ms + (1 - rho) g'^2, centered: mg' = rho mg + (1 - rho) g',
+// mom' = momentum mom + (lr g') / sqrt(ms' [- mg'^2] + epsilon), w' = w - mom', with g' the
+// gradient scaled by grad_scale or, clip non-null, by the device value clip[1]; the decay
+// wd_seg goes into g' (decoupled = 0: l2) or off the old w at lr wd_seg (decoupled).  mom is
+// the momentum buffer; mg is read and written only when centered (it may be null otherwise).
+// master, grad, ms, mom (and mg) must be 16-byte aligned; 0 <= rho, momentum < 1; epsilon > 0.
+void rmsprop_update_pack(float* master, const float* grad, float* ms, float* mg, float* mom,
+                         long n, const LrSchedule& s, const long long* gstep, float rho,
+                         float momentum, float epsilon, float grad_scale, const float* clip,
+                         int centered, int decoupled, const ParamSeg* segs, int nseg,
+                         const float* wd_seg, bf16* bf, float* lr_out, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

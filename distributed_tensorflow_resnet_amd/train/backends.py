@@ -24,8 +24,9 @@ from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
-from ..utils.checkpoint import state_to_tf, tf_to_adam, tf_to_lion, tf_to_state
-from .layout import (check_adam_trust, check_lion, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
+from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_to_lion,
+                                tf_to_rmsprop, tf_to_state)
+from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase)
 
@@ -86,15 +87,20 @@ class GPUBackend:
         if eng.adam:
             adam = {"v": eng.adam_v, "start_step": int(eng.adam_start.item()),
                     "beta1": eng.adam_beta1, "beta2": eng.adam_beta2}
+        rms = {"ms": eng.rms_ms, "mg": eng.rms_mg} if eng.rmsprop else None
         return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam,
-                           lion=eng.lion)
+                           lion=eng.lion, rmsprop=rms)
 
     def load_state(self, tensors):
         eng = self.engine
         # adamw: the momentum buffer is the first moment, loaded from the Adam slots
-        # (lion: it is m, loaded from the Lion slots)
-        gs = tf_to_state(tensors, eng.params, None if eng.adam or eng.lion else eng.mom,
-                         strict=True, ema=eng.ema)
+        # (lion: it is m, loaded from the Lion slots; rmsprop: from the RMSProp slots)
+        own = eng.adam or eng.lion or eng.rmsprop
+        if eng.rmsprop:   # first: a checkpoint of the other form is refused before anything moves
+            check_rmsprop_form(tensors, eng.params, eng.rmsprop_centered)
+        gs = tf_to_state(tensors, eng.params, None if own else eng.mom, strict=True, ema=eng.ema)
+        if eng.rmsprop:   # (after the weights, as the adam and lion slots)
+            tf_to_rmsprop(tensors, eng.params, eng.rms_ms, eng.rms_mg, eng.mom)
         if eng.adam:
             eng.set_adam_start(tf_to_adam(tensors, eng.params, eng.mom, eng.adam_v))
         if eng.lion:
@@ -104,6 +110,9 @@ class GPUBackend:
 
     def adam_state(self):
         return self.engine.adam_state()
+
+    def rmsprop_state(self):
+        return self.engine.rmsprop_state()
 
     @property
     def ema_decay(self) -> float:
@@ -156,7 +165,10 @@ class CPUBackend:
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
                  erase_aspect_min: float = 0.3, erase_fill: str = "zero",
                  lion_beta1: float = 0.9, lion_beta2: float = 0.99,
-                 lion_decay_skip: str = "none"):
+                 lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
+                 rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
+                 rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
+                 rmsprop_decay_skip: str = "none"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -220,7 +232,7 @@ class CPUBackend:
         self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw or lion, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion or rmsprop, got {optimizer!r}")
         # adamw, csrc/adam.hip's expressions in fp32 torch: the first moment in `mom`, the
         # second in `adam_v`; t counts from adam_start
         self.adam = optimizer == "adamw"
@@ -245,6 +257,22 @@ class CPUBackend:
             wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
                                       lion_decay_skip)
             self.lion_wd = torch.repeat_interleave(
+                torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
+        # rmsprop, csrc/rmsprop.hip's expressions in fp32 torch: its momentum in `mom`, the
+        # mean square (from ones) in `rms_ms`, centered the mean gradient in `rms_mg`
+        self.rmsprop = optimizer == "rmsprop"
+        (self.rmsprop_rho, self.rmsprop_momentum, self.rmsprop_epsilon,
+         self.rmsprop_centered) = check_rmsprop(rmsprop_rho, rmsprop_momentum, rmsprop_epsilon,
+                                                rmsprop_centered, rmsprop_wd, rmsprop_decay_skip)
+        self.rmsprop_wd = rmsprop_wd   # the mode; the per-element decay is rmsprop_wd_seg
+        self.rms_ms = self.rms_mg = None
+        if self.rmsprop:
+            self.rms_ms = torch.ones(self.store.n_train)
+            if self.rmsprop_centered:
+                self.rms_mg = torch.zeros(self.store.n_train)
+            wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
+                                      rmsprop_decay_skip)
+            self.rmsprop_wd_seg = torch.repeat_interleave(
                 torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
         if lars_skip not in ("vectors", "none"):
             raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
@@ -323,8 +351,9 @@ class CPUBackend:
                 self.dist.all_reduce_sum(g)
         lr = self.sched.at(self.step_count)
         with torch.no_grad():
-            if self.adam or self.lion:
-                gp = None   # (its decay is per tensor and per mode: _adam_update, _lion_update)
+            if self.adam or self.lion or self.rmsprop:
+                gp = None   # (its decay is per tensor and per mode: _adam_update, _lion_update,
+                #             _rmsprop_update)
             elif self.clip_grad_norm > 0:
                 # after the all-reduce: every rank forms the same norm from the same bits
                 gp = self._clip_scale(g) * g + self.wd * master
@@ -336,6 +365,8 @@ class CPUBackend:
                 self._adam_update(master, g, lr)
             elif self.lion:
                 self._lion_update(master, g, lr)
+            elif self.rmsprop:
+                self._rmsprop_update(master, g, lr)
             elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
@@ -400,6 +431,44 @@ class CPUBackend:
         dec = (lr32 * self.lion_wd) * w   # decoupled: of the old w
         m.copy_(b2 * m + omb2 * gp)
         w.copy_((w - lr32 * u) - dec)
+
+    def _rmsprop_update(self, master, g, lr):
+        """csrc/rmsprop.hip's update in fp32 torch: every product, sum, difference, square root
+        and quotient on its own."""
+        f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
+        rho, mo, eps = f(self.rmsprop_rho), f(self.rmsprop_momentum), f(self.rmsprop_epsilon)
+        omr = f(1.0 - float(rho))
+        lr32 = f(lr)
+        w, ms, mom = master, self.rms_ms, self.mom
+        gp = g * self._clip_scale(g) if self.clip_grad_norm > 0 else g.clone()
+        decoupled = self.rmsprop_wd == "decoupled"
+        if not decoupled:
+            gp = gp + self.rmsprop_wd_seg * w
+        ms.copy_(rho * ms + omr * (gp * gp))
+        d = ms
+        if self.rmsprop_centered:
+            mg = self.rms_mg
+            mg.copy_(rho * mg + omr * gp)
+            d = ms - mg * mg
+        d = d + eps
+        # (the root through fp64 and rounded once more: correctly rounded in fp32, as the
+        # kernel's, whichever vector sqrt the torch build uses)
+        mom.copy_(mo * mom + (lr32 * gp) / d.double().sqrt().float())
+        wn = w - mom
+        if decoupled:
+            wn = wn - (lr32 * self.rmsprop_wd_seg) * w   # of the old w
+        w.copy_(wn)
+
+    def rmsprop_state(self):
+        """As Engine.rmsprop_state(): the coefficients and flat views of ms (and mg)."""
+        if not self.rmsprop:
+            return None
+        st = {"rho": self.rmsprop_rho, "momentum": self.rmsprop_momentum,
+              "epsilon": self.rmsprop_epsilon, "centered": self.rmsprop_centered,
+              "ms": self.rms_ms.view(-1)}
+        if self.rmsprop_centered:
+            st["mg"] = self.rms_mg.view(-1)
+        return st
 
     def _lamb_update(self, master, g, lr):
         """csrc/lamb.hip's three stages in fp32 torch (the norms in fp64, as the kernels'
@@ -558,6 +627,8 @@ class CPUBackend:
             m["adam_alpha"] = self._adam_state[1]
         if self.lion:
             m["optimizer"] = "lion"
+        if self.rmsprop:
+            m["optimizer"] = "rmsprop"
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -581,18 +652,23 @@ class CPUBackend:
         if self.adam:
             adam = {"v": self.adam_v, "start_step": self.adam_start, "beta1": self.adam_beta1,
                     "beta2": self.adam_beta2}
+        rms = {"ms": self.rms_ms, "mg": self.rms_mg} if self.rmsprop else None
         return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam,
-                           lion=self.lion)
+                           lion=self.lion, rmsprop=rms)
 
     def load_state(self, tensors):
         with torch.no_grad():
-            self.step_count = tf_to_state(tensors, self.store,
-                                          None if self.adam or self.lion else self.mom,
+            if self.rmsprop:   # first: a checkpoint of the other form is refused untouched
+                check_rmsprop_form(tensors, self.store, self.rmsprop_centered)
+            own = self.adam or self.lion or self.rmsprop
+            self.step_count = tf_to_state(tensors, self.store, None if own else self.mom,
                                           ema=self.ema)
             if self.adam:
                 self.adam_start = tf_to_adam(tensors, self.store, self.mom, self.adam_v)
             if self.lion:
                 tf_to_lion(tensors, self.store, self.mom)
+            if self.rmsprop:   # (after the weights, as the adam and lion slots)
+                tf_to_rmsprop(tensors, self.store, self.rms_ms, self.rms_mg, self.mom)
 
     def broadcast_parameters(self, src: int = 0):
         if self.dist is not None and self.world > 1:
@@ -635,7 +711,10 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
                  erase_aspect_min: float = 0.3, erase_fill: str = "zero",
                  lion_beta1: float = 0.9, lion_beta2: float = 0.99,
-                 lion_decay_skip: str = "none"):
+                 lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
+                 rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
+                 rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
+                 rmsprop_decay_skip: str = "none"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -643,7 +722,10 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
     adam = dict(adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
                 adam_decay=adam_decay, adam_decay_skip=adam_decay_skip, adam_trust=adam_trust,
                 adam_trust_skip=adam_trust_skip, lion_beta1=lion_beta1, lion_beta2=lion_beta2,
-                lion_decay_skip=lion_decay_skip)
+                lion_decay_skip=lion_decay_skip, rmsprop_rho=rmsprop_rho,
+                rmsprop_momentum=rmsprop_momentum, rmsprop_epsilon=rmsprop_epsilon,
+                rmsprop_centered=rmsprop_centered, rmsprop_wd=rmsprop_wd,
+                rmsprop_decay_skip=rmsprop_decay_skip)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

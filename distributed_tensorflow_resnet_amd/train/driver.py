@@ -237,7 +237,13 @@ def main(argv=None, kind: str = "cifar") -> int:
                            adam_decay_skip=flags.adam_decay_skip,
                            adam_trust=flags.adam_trust, adam_trust_skip=flags.adam_trust_skip,
                            lion_beta1=flags.lion_beta1, lion_beta2=flags.lion_beta2,
-                           lion_decay_skip=flags.lion_decay_skip)
+                           lion_decay_skip=flags.lion_decay_skip,
+                           rmsprop_rho=flags.rmsprop_rho,
+                           rmsprop_momentum=flags.rmsprop_momentum,
+                           rmsprop_epsilon=flags.rmsprop_epsilon,
+                           rmsprop_centered=flags.rmsprop_centered,
+                           rmsprop_wd=flags.rmsprop_wd,
+                           rmsprop_decay_skip=flags.rmsprop_decay_skip)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

@@ -55,7 +55,7 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
-                     OPT_FUSED_LION_REASON, check_lion)
+                     OPT_FUSED_LION_REASON, check_lion, OPT_FUSED_RMSPROP_REASON, check_rmsprop)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -138,7 +138,10 @@ class Engine:
                  erase_area_min: float = 0.02, erase_area_max: float = 1.0 / 3.0,
                  erase_aspect_min: float = 0.3, erase_fill: str = "zero",
                  lion_beta1: float = 0.9, lion_beta2: float = 0.99,
-                 lion_decay_skip: str = "none"):
+                 lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
+                 rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
+                 rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
+                 rmsprop_decay_skip: str = "none"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -153,7 +156,7 @@ class Engine:
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw or lion, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion or rmsprop, got {optimizer!r}")
         if lars_skip not in LARS_SKIPS:
             raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
         # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
@@ -181,6 +184,15 @@ class Engine:
         self.lion = optimizer == "lion"
         self.lion_beta1, self.lion_beta2 = check_lion(lion_beta1, lion_beta2, lion_decay_skip)
         self.lion_decay_skip = lion_decay_skip
+        # rmsprop: TF 1.12's RMSPropOptimizer (momentum, epsilon inside the root, optionally
+        # centered), one launch on the generic optimizer path (csrc/rmsprop.hip).  Its `mom`
+        # lives in the momentum buffer; ms (from ones) and, centered only, mg exist only for it
+        self.rmsprop = optimizer == "rmsprop"
+        (self.rmsprop_rho, self.rmsprop_momentum, self.rmsprop_epsilon,
+         self.rmsprop_centered) = check_rmsprop(rmsprop_rho, rmsprop_momentum, rmsprop_epsilon,
+                                                rmsprop_centered, rmsprop_wd, rmsprop_decay_skip)
+        # (rmsprop_wd is the mode, as adam_decay; the per-segment table is rmsprop_wd_seg)
+        self.rmsprop_wd, self.rmsprop_decay_skip = rmsprop_wd, rmsprop_decay_skip
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -311,6 +323,11 @@ class Engine:
             # it; the host writes it here and on restore
             self.adam_start = torch.zeros(1, dtype=torch.int64, device=dev)
             self.adam_out = torch.zeros(3, device=dev)   # {lr, alpha, t} of the last step
+        self.rms_ms = self.rms_mg = None
+        if self.rmsprop:
+            self.rms_ms = torch.ones(self.params.n_train, device=dev)   # TF's `rms` slot: ones
+            if self.rmsprop_centered:
+                self.rms_mg = torch.zeros(self.params.n_train, device=dev)
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
         # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
         self.scalars = torch.zeros(8, device=dev)
@@ -366,6 +383,9 @@ class Engine:
         if self.lion and self.opt_fused:   # (before clipping, as adamw)
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_LION_REASON
+        if self.rmsprop and self.opt_fused:   # (before clipping, as adamw)
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_RMSPROP_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -479,6 +499,10 @@ class Engine:
         if self.lion:   # the same table under lion_decay_skip
             self.lion_wd = torch.from_numpy(adam_decay_table(
                 [s.shape for s in ps.train_slots], self.wd, self.lion_decay_skip)).to(dev)
+        self.rmsprop_wd_seg = None
+        if self.rmsprop:   # the same table under rmsprop_decay_skip
+            self.rmsprop_wd_seg = torch.from_numpy(adam_decay_table(
+                [s.shape for s in ps.train_slots], self.wd, self.rmsprop_decay_skip)).to(dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:
             # chunk partials and the {norm, scale} slot: fixed pointers
@@ -791,6 +815,19 @@ class Engine:
         torch.cuda.synchronize(self.device)
         _, alpha, t = self.adam_out.cpu().tolist()
         return int(t), alpha
+
+    def rmsprop_state(self):
+        """{"rho", "momentum", "epsilon", "centered"} of the rmsprop optimizer plus "ms" (and,
+        centered, "mg"): flat views of the state buffers, in the master's layout (`mom` is the
+        momentum buffer).  None unless the optimizer is rmsprop."""
+        if not self.rmsprop:
+            return None
+        st = {"rho": self.rmsprop_rho, "momentum": self.rmsprop_momentum,
+              "epsilon": self.rmsprop_epsilon, "centered": self.rmsprop_centered,
+              "ms": self.rms_ms.view(-1)}
+        if self.rmsprop_centered:
+            st["mg"] = self.rms_mg.view(-1)
+        return st
 
     def set_adam_start(self, step: int):
         """The step the moments count from (a restore's: the checkpoint's adam_start_step, or
@@ -1108,6 +1145,8 @@ class Engine:
             m["adam_alpha"] = float(self.adam_out[1].item())
         if self.lion:
             m["optimizer"] = "lion"
+        if self.rmsprop:
+            m["optimizer"] = "rmsprop"
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
@@ -1134,6 +1173,8 @@ class Engine:
         ts = (self.params.master, self.params.stats, self.mom, self.gstep)
         if self.adam:
             ts += (self.adam_v, self.adam_start)
+        if self.rmsprop:
+            ts += (self.rms_ms,) + ((self.rms_mg,) if self.rmsprop_centered else ())
         return ts + (self.ema,) if self.ema is not None else ts
 
     def broadcast_parameters(self, src: int = 0):

@@ -98,6 +98,8 @@ class LoggingTensorHook(Hook):
                 clip += f", adam alpha = {m['adam_alpha']:.6g}"
             if m.get("optimizer") == "lion":   # --optimizer lion
                 clip += ", optimizer: lion"
+            if m.get("optimizer") == "rmsprop":   # --optimizer rmsprop
+                clip += ", optimizer: rmsprop"
             mix = ""
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"

@@ -134,7 +134,7 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
-OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion")
+OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion", "rmsprop")
 ADAM_DECAYS = ("decoupled", "l2")
 ADAM_DECAY_SKIPS = ("none", "vectors")
 OPT_FUSED_ADAM_REASON = ("optimizer adamw: the one-launch optimizer is SGD-momentum; adamw takes "
@@ -208,6 +208,39 @@ def check_lion(beta1, beta2, decay_skip: str = "none"):
     if decay_skip not in ADAM_DECAY_SKIPS:
         raise ValueError(f"lion_decay_skip must be one of {ADAM_DECAY_SKIPS}, got {decay_skip!r}")
     return b1, b2
+
+
+OPT_FUSED_RMSPROP_REASON = ("optimizer rmsprop: the one-launch optimizer is SGD-momentum; rmsprop "
+                            "takes the generic optimizer launches")
+RMSPROP_WDS = ("l2", "decoupled")
+
+
+def check_rmsprop(rho, momentum, epsilon, centered=False, wd: str = "l2",
+                  decay_skip: str = "none"):
+    """The rmsprop flags as both backends take them: (rho, momentum, epsilon, centered) as
+    floats and a bool.  rho and momentum are in [0, 1) (in fp32 too, as the kernel's float
+    arguments); epsilon > 0 and finite in fp32 (it sits inside the square root: with 0 an
+    element whose gradient and ms are zero would be 0 / 0); wd is the decay mode, decay_skip
+    as adam_decay_skip.  (adam_trust on with rmsprop is check_adam_trust's to refuse.)"""
+    try:
+        r, mo, eps = float(rho), float(momentum), float(epsilon)
+    except (TypeError, ValueError):
+        raise ValueError(f"rmsprop_rho, rmsprop_momentum and rmsprop_epsilon must be numbers, "
+                         f"got {rho!r}, {momentum!r}, {epsilon!r}") from None
+    for name, b in (("rmsprop_rho", r), ("rmsprop_momentum", mo)):
+        if not 0.0 <= b < 1.0:   # NaN included
+            raise ValueError(f"{name} must be in [0, 1), got {b!r}")
+    if float(np.float32(r)) >= 1.0 or float(np.float32(mo)) >= 1.0:
+        raise ValueError(f"rmsprop_rho and rmsprop_momentum must be below 1 in fp32, got "
+                         f"{r!r}, {mo!r}")
+    if not 0.0 < float(np.float32(eps)) < float("inf"):
+        raise ValueError(f"rmsprop_epsilon must be positive (and finite in fp32), got {eps!r}")
+    if wd not in RMSPROP_WDS:
+        raise ValueError(f"rmsprop_wd must be one of {RMSPROP_WDS}, got {wd!r}")
+    if decay_skip not in ADAM_DECAY_SKIPS:
+        raise ValueError(f"rmsprop_decay_skip must be one of {ADAM_DECAY_SKIPS}, got "
+                         f"{decay_skip!r}")
+    return r, mo, eps, bool(centered)
 
 
 def lamb_bias_corrections(t: int, beta1: float, beta2: float):

@@ -656,6 +656,31 @@ class StepRecorder:
                         out.op_buffers[i0 + 1] = {"clip"}
                     out.op_buffers[i1] = (gb | pb | {"lr", "gstep"}
                                           | ({"clip"} if clip else set()))
+            elif e.rmsprop:
+                # one launch (csrc/rmsprop.hip), as adamw's: with clipping the norm launches go
+                # in front and the update reads the scale from the device slot
+                clip, co = e.clip_grad_norm > 0, 0
+                i0 = plan.size()
+                if clip:
+                    co = e.clip_out.data_ptr()
+                    plan.grad_sqnorm(grad, e.params.n_train, e.clip_part.data_ptr())
+                    plan.clip_scale(e.clip_part.data_ptr(), e.clip_chunks,
+                                    float(np.float32(e.clip_grad_norm)), co)
+                i1 = plan.rmsprop_update_pack(
+                    master, grad, e.rms_ms.data_ptr(),
+                    e.rms_mg.data_ptr() if e.rmsprop_centered else 0, mom, e.params.n_train,
+                    *e.sched.launch_args(), e.gstep.data_ptr(), e.rmsprop_rho,
+                    e.rmsprop_momentum, e.rmsprop_epsilon, 1.0, co, int(e.rmsprop_centered),
+                    e.rmsprop_wd, e.segs.data_ptr(), e.nseg, e.rmsprop_wd_seg.data_ptr(),
+                    e.wbf.data_ptr(), sp + 8, *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
+                    if clip:
+                        out.op_buffers[i0] = gb | {"clip"}
+                        out.op_buffers[i0 + 1] = {"clip"}
+                    out.op_buffers[i1] = (gb | pb | {"rmsprop", "lr", "gstep"}
+                                          | ({"clip"} if clip else set()))
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

@@ -8,7 +8,11 @@ under its TF name (HWIO conv kernels, BN gamma/beta, dense kernel/bias), its
 trainable (tf.train.ExponentialMovingAverage's shadow variables); a run with ``--optimizer
 adamw`` saves ``<name>/Adam`` and ``<name>/Adam_1`` in place of ``<name>/Momentum``, plus
 ``beta1_power``, ``beta2_power`` and ``adam_start_step``; a run with ``--optimizer lion``
-saves ``<name>/Lion`` in place of ``<name>/Momentum`` (no extra scalars).  ``max_to_keep``
+saves ``<name>/Lion`` in place of ``<name>/Momentum`` (no extra scalars); a run with
+``--optimizer rmsprop`` saves tf.train.RMSPropOptimizer's slots in their creation order
+(``rms``, then ``mg`` if centered, then ``momentum``): ``<name>/RMSProp`` and
+``<name>/RMSProp_1``, centered ``<name>/RMSProp``, ``<name>/RMSProp_1`` and
+``<name>/RMSProp_2``, in place of ``<name>/Momentum`` (no extra scalars).  ``max_to_keep``
 = 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
@@ -33,6 +37,19 @@ ADAM_START = "adam_start_step"                     # ours: the step the moments 
 LION_SUFFIX = "/Lion"   # lion's one slot: an average of the gradient, not mom's accumulator
 
 
+# tf.train.RMSPropOptimizer's slot names, in the order TF 1.12 creates the slots: rms, mg
+# (centered only), momentum -- so "/RMSProp_1" is the momentum of a plain run and mg of a
+# centered one
+RMSPROP_SUFFIXES = ("/RMSProp", "/RMSProp_1", "/RMSProp_2")
+
+
+def rmsprop_suffixes(centered: bool) -> dict:
+    """{"ms", "mom"[, "mg"]: slot suffix} of a plain or centered rmsprop run."""
+    if centered:
+        return {"ms": RMSPROP_SUFFIXES[0], "mg": RMSPROP_SUFFIXES[1], "mom": RMSPROP_SUFFIXES[2]}
+    return {"ms": RMSPROP_SUFFIXES[0], "mom": RMSPROP_SUFFIXES[1]}
+
+
 def adam_beta_powers(t_done: int, beta1: float, beta2: float):
     """TF 1.12's beta1_power / beta2_power variables after t_done Adam steps: b^(t_done + 1)
     (they start at b and are multiplied by b after every step), from the fp32 betas in fp64,
@@ -43,7 +60,7 @@ def adam_beta_powers(t_done: int, beta1: float, beta2: float):
 
 def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
                 ema: torch.Tensor | None = None, adam: dict | None = None,
-                lion: bool = False) -> dict[str, np.ndarray]:
+                lion: bool = False, rmsprop: dict | None = None) -> dict[str, np.ndarray]:
     """ParamStore (+flat momentum, +flat EMA shadows, in the same layout) -> {TF name: array}.
     ``ema`` adds ``<name>/ExponentialMovingAverage`` per trainable; without it the entries
     are exactly the reference's.  ``adam`` (an adamw run: {"v": flat second moment,
@@ -51,7 +68,9 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
     ``<name>/Adam``, v as ``<name>/Adam_1`` (TF's slot names), no ``/Momentum``; plus the fp32
     scalars beta1_power / beta2_power (TF 1.12's variables after global_step - start_step
     Adam steps) and the int64 ``adam_start_step``, which restore goes by.  ``lion`` (a lion
-    run): `momentum` is its m and goes out as ``<name>/Lion``, no ``/Momentum``."""
+    run): `momentum` is its m and goes out as ``<name>/Lion``, no ``/Momentum``.  ``rmsprop``
+    (an rmsprop run: {"ms": flat mean square, "mg": flat mean gradient or None}): `momentum`,
+    ms and mg go out under rmsprop_suffixes(mg is not None), no ``/Momentum``."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
@@ -59,10 +78,17 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
     sh = ema.detach().float().cpu().numpy() if ema is not None else None
     v = adam["v"].detach().float().cpu().numpy() if adam is not None else None
     m_suffix = ADAM_M_SUFFIX if adam is not None else LION_SUFFIX if lion else "/Momentum"
+    rms = {}
+    if rmsprop is not None:
+        suf = rmsprop_suffixes(rmsprop.get("mg") is not None)
+        m_suffix = suf["mom"]
+        rms = {suf[k]: rmsprop[k].detach().float().cpu().numpy() for k in suf if k != "mom"}
     for s in store.train_slots:
         out[s.name] = master[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if mom is not None:
             out[s.name + m_suffix] = mom[s.offset:s.offset + s.numel].reshape(s.shape).copy()
+        for suffix, buf in rms.items():
+            out[s.name + suffix] = buf[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if v is not None:
             out[s.name + ADAM_V_SUFFIX] = v[s.offset:s.offset + s.numel].reshape(s.shape).copy()
         if sh is not None:
@@ -120,6 +146,65 @@ def tf_to_lion(tensors: dict, store, m: torch.Tensor) -> None:
         if a.size != s.numel:
             raise ValueError(f"{s.name + LION_SUFFIX}: {a.size} elements, expected {s.numel}")
         m.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
+
+
+def check_rmsprop_form(tensors: dict, store, centered: bool) -> bool:
+    """Whether {TF name: array} holds the slots of an rmsprop run of this form (False: it has
+    no ``<name>/RMSProp`` slots for some variable, so the state starts afresh).  Touches
+    nothing, so a restore calls it before anything is loaded.  ValueError: the slots are of the
+    other form (plain against centered: ``<name>/RMSProp_1`` is the momentum in one and mg in
+    the other), or a slot of this form is missing or of the wrong size."""
+    names = [s.name for s in store.train_slots]
+    if any(n + RMSPROP_SUFFIXES[0] not in tensors for n in names):
+        return False
+    ckpt_centered = any(n + RMSPROP_SUFFIXES[2] in tensors for n in names)
+    if ckpt_centered != centered:
+        kind = ("centered", "plain")
+        raise ValueError(
+            f"checkpoint holds the slots of a {kind[not ckpt_centered]} rmsprop run and this run "
+            f"is {kind[not centered]}: {names[0] + RMSPROP_SUFFIXES[1]} is "
+            f"{'mg' if ckpt_centered else 'the momentum'} there and "
+            f"{'mg' if centered else 'the momentum'} here; restore it with "
+            f"--rmsprop_centered={'true' if ckpt_centered else 'false'}")
+    for suffix in rmsprop_suffixes(centered).values():
+        for s in store.train_slots:
+            k = s.name + suffix
+            if k not in tensors:
+                raise ValueError(f"checkpoint lacks the rmsprop slot {k}")
+            size = int(np.asarray(tensors[k]).size)
+            if size != s.numel:
+                raise ValueError(f"{k}: {size} elements, expected {s.numel}")
+    return True
+
+
+def tf_to_rmsprop(tensors: dict, store, ms: torch.Tensor, mg: torch.Tensor | None,
+                  mom: torch.Tensor) -> None:
+    """Load the state of an rmsprop run (mg not None: centered) from {TF name: array}.  With
+    every slot of its form present they are loaded.  Without the ``<name>/RMSProp`` slots (e.g.
+    a `mom` checkpoint, whose ``/Momentum`` is ignored) ms starts from ones, as TF's `rms` slot
+    does, mg and mom from zeros, and one log line says so.  A checkpoint of the other form
+    (plain into centered or the reverse) is refused: its ``<name>/RMSProp_1`` is the momentum
+    in one and mg in the other (check_rmsprop_form, which a restore also calls on its own
+    before it loads anything)."""
+    centered = mg is not None
+    suf = rmsprop_suffixes(centered)
+    names = [s.name for s in store.train_slots]
+    absent = [n for n in names if n + RMSPROP_SUFFIXES[0] not in tensors]
+    if not check_rmsprop_form(tensors, store, centered):
+        print(f"INFO:tensorflow:checkpoint has no RMSProp slots for {len(absent)} of "
+              f"{len(names)} variables (e.g. {absent[0] + RMSPROP_SUFFIXES[0]}): ms starts from "
+              "ones, mg and the momentum from zero", flush=True)
+        ms.data.fill_(1.0)
+        mom.data.zero_()
+        if centered:
+            mg.data.zero_()
+        return
+    for key, buf in (("ms", ms), ("mg", mg), ("mom", mom)):
+        if key not in suf:
+            continue
+        for s in store.train_slots:
+            a = np.asarray(tensors[s.name + suf[key]], dtype=np.float32).reshape(-1)
+            buf.data[s.offset:s.offset + s.numel].copy_(torch.from_numpy(a))
 
 
 def ema_weights(tensors: dict, store) -> dict:

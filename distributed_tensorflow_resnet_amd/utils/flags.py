@@ -17,6 +17,9 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
                      --adam_trust on makes it LAMB (per-tensor trust ratios), --adam_trust_skip
   --optimizer lion   Lion (sign of an interpolated momentum, one state buffer) in one device
                      launch: --lion_beta1/_beta2, --lion_decay_skip
+  --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
+                     one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
+                     --rmsprop_wd, --rmsprop_decay_skip
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -92,6 +95,26 @@ def _lion_beta(v) -> float:
         raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
     if not 0.0 <= f < 1.0:   # NaN included
         raise argparse.ArgumentTypeError(f"a Lion beta must be in [0, 1), got {v!r}")
+    return f
+
+
+def _rmsprop_coef(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 <= f < 1.0:   # NaN included
+        raise argparse.ArgumentTypeError(f"rmsprop's rho and momentum must be in [0, 1), got {v!r}")
+    return f
+
+
+def _rmsprop_epsilon(v) -> float:
+    try:
+        f = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {v!r}") from None
+    if not 0.0 < f < float("inf"):   # zero, negative, inf or NaN
+        raise argparse.ArgumentTypeError(f"rmsprop's epsilon must be positive and finite, got {v!r}")
     return f
 
 
@@ -206,6 +229,14 @@ class FlagParser(argparse.ArgumentParser):
                 check_lion(ns.lion_beta1, ns.lion_beta2, ns.lion_decay_skip)
             except ValueError as e:
                 self.error(str(e))
+        if hasattr(ns, "rmsprop_rho"):
+            from ..train.layout import check_rmsprop
+
+            try:   # (the fp32 values the kernel gets: a rho that rounds to 1, an epsilon to 0)
+                check_rmsprop(ns.rmsprop_rho, ns.rmsprop_momentum, ns.rmsprop_epsilon,
+                              ns.rmsprop_centered, ns.rmsprop_wd, ns.rmsprop_decay_skip)
+            except ValueError as e:
+                self.error(str(e))
         if hasattr(ns, "adam_trust"):
             from ..train.layout import check_adam_trust
 
@@ -313,7 +344,7 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion"),
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion", "rmsprop"),
                    help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
                         "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
                         "epsilon) (layer-wise adaptive rate scaling, for large global batches).  "
@@ -322,7 +353,12 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "(e.g. 1e-3) or --lr_value_scale with it.  lion: the sign of an "
                         "interpolated momentum (Chen et al. 2023) with decoupled weight decay "
                         "and one state buffer; every element moves by lr, so set a rate well "
-                        "below adamw's (the paper: 3-10x) and a correspondingly larger decay.")
+                        "below adamw's (the paper: 3-10x) and a correspondingly larger decay.  "
+                        "rmsprop: tf.train.RMSPropOptimizer's form (timm's rmsproptf): momentum, "
+                        "epsilon inside the square root, ms from ones, no bias correction; the "
+                        "presets' learning rates (0.1 / 0.4) are SGD rates, so set --lr_peak "
+                        "(e.g. 1e-3) with it; the recipe-scale epsilon (TF-slim uses 1.0) is "
+                        "--rmsprop_epsilon's to set.")
     p.add_argument("--adam_beta1", type=_adam_beta, default=0.9,
                    help="adamw: decay of the first moment, in [0, 1).")
     p.add_argument("--adam_beta2", type=_adam_beta, default=0.999,
@@ -353,6 +389,23 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="lion: decay of the momentum, in [0, 1).")
     p.add_argument("--lion_decay_skip", default="none", choices=("none", "vectors"),
                    help="lion: tensors without weight decay, as --adam_decay_skip.")
+    p.add_argument("--rmsprop_rho", type=_rmsprop_coef, default=0.9,
+                   help="rmsprop: decay of the mean square (TF's `decay`), in [0, 1).")
+    p.add_argument("--rmsprop_momentum", type=_rmsprop_coef, default=0.9,
+                   help="rmsprop: momentum, in [0, 1).  0.9 is TF-slim's value; TF's own default "
+                        "of 0 is a valid setting.")
+    p.add_argument("--rmsprop_epsilon", type=_rmsprop_epsilon, default=1e-10,
+                   help="rmsprop: epsilon, inside the square root; must be > 0.  1e-10 is TF's "
+                        "default; TF-slim's recipes use 1.0.")
+    p.add_bool("rmsprop_centered", False,
+               "rmsprop: the centered form (the denominator is the estimated variance: a third "
+               "state buffer mg).")
+    p.add_argument("--rmsprop_wd", default="l2", choices=("l2", "decoupled"),
+                   help="rmsprop: l2 = the decay term is part of the gradient (plain TF RMSProp "
+                        "on the reference's cost); decoupled = taken off the old weight at the "
+                        "scheduled lr, as adamw's.")
+    p.add_argument("--rmsprop_decay_skip", default="none", choices=("none", "vectors"),
+                   help="rmsprop: tensors without weight decay, as --adam_decay_skip.")
     p.add_argument("--lars_eeta", type=float, default=0.001,
                    help="LARS trust coefficient.")
     p.add_argument("--lars_epsilon", type=float, default=0.0,

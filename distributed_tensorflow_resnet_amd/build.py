@@ -33,9 +33,12 @@ COMMON_FLAGS = [
 ]
 
 
-# per-file extra flags (none at present; e.g. ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] keeps
-# a one-wave-per-SIMD kernel's MFMA accumulators in arch VGPRs, profiles/imagenet_wide.md)
-FILE_FLAGS: dict = {}
+# per-file extra flags (e.g. ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] keeps a
+# one-wave-per-SIMD kernel's MFMA accumulators in arch VGPRs, profiles/imagenet_wide.md).
+# muon.hip: no packed fp32 arithmetic (v_pk_*_f32) in its element-wise passes
+FILE_FLAGS: dict = {
+    "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _sources():

@@ -992,6 +992,62 @@ static Launch mk_rmsprop_update_pack(ptr_t master, ptr_t grad, ptr_t ms, ptr_t m
                                       bf, lr_out, kPiecewise);
 }
 
+// The Muon launches (muon.hip).  rows / cols: the host's copy of the device table's R and K,
+// one pair per record, checked against muon_covers here.
+static Launch mk_muon_orthogonalize(ptr_t grad, ptr_t mom, ptr_t dir, ptr_t tab,
+                                    std::vector<int> rows, std::vector<int> cols, float momentum,
+                                    int nesterov, int steps, float grad_scale) {
+  if (!grad || !mom || !dir || !tab) throw std::invalid_argument("muon_orthogonalize: null buffer");
+  if (rows.empty() || rows.size() != cols.size())
+    throw std::invalid_argument("muon_orthogonalize: one (R, K) per record, at least one");
+  for (size_t i = 0; i < rows.size(); ++i)
+    if (!muon_covers(rows[i], cols[i]))
+      throw std::invalid_argument("muon_orthogonalize: tensor " + std::to_string(i) + " is " +
+                                  std::to_string(rows[i]) + " x " + std::to_string(cols[i]) +
+                                  ": the short side must be in [1, 64] and the long side <= 576");
+  if (!(momentum >= 0.f && momentum < 1.f))
+    throw std::invalid_argument("muon_orthogonalize: momentum in [0, 1)");
+  if (steps < 1 || steps > 8) throw std::invalid_argument("muon_orthogonalize: steps in [1, 8]");
+  const int nt = (int)rows.size();
+  return [=](hipStream_t s) {
+    muon_orthogonalize(P<const float>(grad), P<float>(mom), P<float>(dir),
+                       P<const MuonTensor>(tab), nt, momentum, nesterov, steps, grad_scale, s);
+  };
+}
+
+static Launch mk_muon_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                        float init, long long warm_steps, float warm_from,
+                                        float warm_to, std::vector<long long> bounds,
+                                        std::vector<float> vals, ptr_t gstep, float momentum,
+                                        float wd, float aux_scale, float grad_scale, ptr_t segs,
+                                        int nseg, ptr_t muon_seg, ptr_t q_seg, ptr_t bf,
+                                        ptr_t lr_out, LrDecayArgs decay) {
+  if ((master | grad | mom | dir) & 15)
+    throw std::invalid_argument("muon_update_pack: master, grad, mom and dir must be 16-byte aligned");
+  if (!master || !grad || !mom || !dir || !segs || !muon_seg || !q_seg || !gstep)
+    throw std::invalid_argument("muon_update_pack: null buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("muon_update_pack: n >= 0 and nseg > 0");
+  if (!(aux_scale > 0.f)) throw std::invalid_argument("muon_update_pack: aux_scale > 0");
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    muon_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), P<const float>(dir), n,
+                     sc, P<const long long>(gstep), momentum, wd, aux_scale, grad_scale,
+                     P<const ParamSeg>(segs), nseg, P<const int>(muon_seg), P<const float>(q_seg),
+                     P<bf16>(bf), P<float>(lr_out), s);
+  };
+}
+
+static Launch mk_muon_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                  float init, long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float momentum, float wd, float aux_scale,
+                                  float grad_scale, ptr_t segs, int nseg, ptr_t muon_seg,
+                                  ptr_t q_seg, ptr_t bf, ptr_t lr_out) {
+  return mk_muon_update_pack_decay(master, grad, mom, dir, n, init, warm_steps, warm_from, warm_to,
+                                   bounds, vals, gstep, momentum, wd, aux_scale, grad_scale, segs,
+                                   nseg, muon_seg, q_seg, bf, lr_out, kPiecewise);
+}
+
 // The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
 static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
                       const std::string& decay_mode) {
@@ -1856,6 +1912,9 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "lion_update_pack", mk_lion_update_pack_decay);
   def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack);
   def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack_decay);
+  def_op(m, plan, "muon_orthogonalize", mk_muon_orthogonalize);
+  def_op(m, plan, "muon_update_pack", mk_muon_update_pack);
+  def_op(m, plan, "muon_update_pack", mk_muon_update_pack_decay);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
   def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);
@@ -1966,6 +2025,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("wg_desc_bytes", []() { return (int)sizeof(WgReduceDesc); });
   m.def("opt_work_bytes", []() { return (int)sizeof(OptWork); });
   m.def("lars_seg_bytes", []() { return (int)sizeof(LarsSeg); });
+  m.def("muon_tensor_bytes", []() { return (int)sizeof(MuonTensor); });
+  m.def("muon_covers", &muon_covers);
   m.attr("LARS_CHUNK") = (int)LARS_CHUNK;
   m.attr("CLIP_CHUNK") = (int)CLIP_CHUNK;
   m.def("clip_chunks", &clip_chunks, "workgroups (fp64 partials) of grad_sqnorm over n elements");

@@ -144,6 +144,32 @@ void rmsprop_update_pack(float* master, const float* grad, float* ms, float* mg,
                          float momentum, float epsilon, float grad_scale, const float* clip,
                          int centered, int decoupled, const ParamSeg* segs, int nseg,
                          const float* wd_seg, bf16* bf, float* lr_out, hipStream_t st);
+// Muon (muon.hip).  One record per orthogonalised tensor: a conv kernel whose HWIO master is
+// the row-major R x K matrix at `offset` of the flat buffers; transpose = (K <= R): the
+// iteration runs on the matrix's transpose, short side first.
+struct MuonTensor {
+  long long offset;
+  int seg;                 // its parameter segment
+  int R, K;
+  int transpose;
+};
+// Short side <= 64 and long side <= 576: what one workgroup holds in LDS.
+bool muon_covers(int R, int K);
+// One workgroup per record: m' = momentum m + g' in place (g' = grad_scale g; grad is only
+// read), u = g' + momentum m' (nesterov) or m', X0 = bf16(u / (||u||_F + 1e-7)), `steps`
+// quintic Newton-Schulz steps in bf16 with fp32 accumulation, and the result as fp32 into dir
+// at the tensor's offset.  Nothing outside the records' tensors is touched.
+void muon_orthogonalize(const float* grad, float* mom, float* dir, const MuonTensor* tab,
+                        int ntensors, float momentum, int nesterov, int steps, float grad_scale,
+                        hipStream_t st);
+// One launch of lion_update_pack's shape.  muon_seg[segment] != 0: w' = (w - (lr wd) w) -
+// (lr q_seg[segment]) dir; else sgd_update_pack's update with momentum at lr * aux_scale.
+// master, grad, mom and dir must be 16-byte aligned.
+void muon_update_pack(float* master, const float* grad, float* mom, const float* dir, long n,
+                      const LrSchedule& s, const long long* gstep, float momentum, float wd,
+                      float aux_scale, float grad_scale, const ParamSeg* segs, int nseg,
+                      const int* muon_seg, const float* q_seg, bf16* bf, float* lr_out,
+                      hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

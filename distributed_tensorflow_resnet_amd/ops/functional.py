@@ -335,3 +335,36 @@ def cifar_augment_resident(records_u8, labels_all, pos, batch, cpad=8, pad=4, se
     if log_index:
         res += (idx,)
     return res
+
+
+def muon_orthogonalize(grad, mom, shapes, offsets=None, *, momentum=0.95, nesterov=True, steps=5,
+                       grad_scale=1.0, out=None):
+    """csrc/muon.hip's first launch on flat fp32 buffers: for every (R, K) of ``shapes`` (the
+    row-major R x K matrix at the matching element of ``offsets``, default back to back) the
+    momentum ``mom`` is updated in place and the Newton-Schulz-orthogonalised direction is
+    written into ``out`` (default: zeros like grad) at the same offset.  One workgroup per
+    matrix; a short side above 64 or a long side above 576 raises.  Returns ``out``."""
+    import numpy as np
+
+    from ..train.layout import MUON_DTYPE
+
+    _check(grad, torch.float32, 1, "grad")
+    _check(mom, torch.float32, 1, "mom")
+    out = torch.zeros_like(grad) if out is None else out
+    _check(out, torch.float32, 1, "out")
+    if offsets is None:
+        offsets = [0]
+        for R, K in shapes[:-1]:
+            offsets.append(offsets[-1] + R * K)
+    if len(offsets) != len(shapes) or mom.numel() != grad.numel() or out.numel() != grad.numel():
+        raise ValueError("one offset per shape, and grad, mom and out of one length")
+    for o, (R, K) in zip(offsets, shapes):
+        if o < 0 or o + R * K > grad.numel():
+            raise ValueError(f"matrix {R} x {K} at {o} is outside the {grad.numel()} elements")
+    tab = np.array([(o, i, R, K, int(K <= R)) for i, (o, (R, K)) in enumerate(zip(offsets, shapes))],
+                   dtype=MUON_DTYPE)
+    dtab = torch.from_numpy(tab.view(np.uint8).copy()).to(grad.device)
+    native().muon_orthogonalize(grad.data_ptr(), mom.data_ptr(), out.data_ptr(), dtab.data_ptr(),
+                                [R for R, _ in shapes], [K for _, K in shapes], float(momentum),
+                                int(bool(nesterov)), int(steps), float(grad_scale), _stream())
+    return out

@@ -28,7 +28,7 @@ from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_
                                 tf_to_rmsprop, tf_to_state)
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
-                     check_mixup_alpha, check_erase)
+                     check_mixup_alpha, check_erase, check_muon, muon_tables)
 
 
 class GPUBackend:
@@ -168,7 +168,9 @@ class CPUBackend:
                  lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
                  rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
-                 rmsprop_decay_skip: str = "none"):
+                 rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
+                 muon_nesterov: bool = True, muon_ns_steps: int = 5,
+                 muon_aux_lr_scale: float = 1.0):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -232,7 +234,7 @@ class CPUBackend:
         self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion or rmsprop, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon or rmsprop, got {optimizer!r}")
         # adamw, csrc/adam.hip's expressions in fp32 torch: the first moment in `mom`, the
         # second in `adam_v`; t counts from adam_start
         self.adam = optimizer == "adamw"
@@ -274,6 +276,16 @@ class CPUBackend:
                                       rmsprop_decay_skip)
             self.rmsprop_wd_seg = torch.repeat_interleave(
                 torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
+        # muon, csrc/muon.hip's update in fp32 torch with its bf16 roundings: conv kernels move
+        # along the orthogonalised momentum, the rest takes mom's update; `mom` is the only state
+        self.muon = optimizer == "muon"
+        (self.muon_momentum, self.muon_nesterov, self.muon_ns_steps,
+         self.muon_aux_lr_scale) = check_muon(muon_momentum, muon_nesterov, muon_ns_steps,
+                                              muon_aux_lr_scale, self.clip_grad_norm, optimizer)
+        if self.muon:
+            self.muon_tab, seg, self.muon_q = muon_tables(self.store.train_slots)
+            self.muon_mask = torch.repeat_interleave(
+                torch.from_numpy(seg).bool(), torch.tensor([s.numel for s in self.store.train_slots]))
         if lars_skip not in ("vectors", "none"):
             raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
         self.lars = optimizer == "lars"
@@ -367,6 +379,8 @@ class CPUBackend:
                 self._lion_update(master, g, lr)
             elif self.rmsprop:
                 self._rmsprop_update(master, g, lr)
+            elif self.muon:
+                self._muon_update(master, g, gp, lr)
             elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
@@ -469,6 +483,34 @@ class CPUBackend:
         if self.rmsprop_centered:
             st["mg"] = self.rms_mg.view(-1)
         return st
+
+    def _muon_update(self, master, g, gp, lr):
+        """csrc/muon.hip's two launches in torch: per conv kernel m' = mu m + g, u = g + mu m'
+        (Nesterov) or m', five-coefficient Newton-Schulz on the short x long orientation with a
+        bf16 rounding of A, B and X (the products in fp32), w' = (w - lr wd w) - lr q O; every
+        other element takes mom's update (gp = g + wd w) at lr * muon_aux_lr_scale."""
+        bf = lambda x: x.to(torch.bfloat16).float()   # noqa: E731
+        a, b, c = 3.4445, -4.7750, 2.0315
+        mu, aux = self.muon_mask, ~self.muon_mask
+        m_aux = self.momentum * self.mom[aux] + gp[aux]
+        w_aux = master[aux] - (lr * self.muon_aux_lr_scale) * m_aux
+        for rec in self.muon_tab:
+            o, R, K = int(rec["offset"]), int(rec["R"]), int(rec["K"])
+            sl = slice(o, o + R * K)
+            m = self.muon_momentum * self.mom[sl] + g[sl]
+            self.mom[sl] = m
+            u = (g[sl] + self.muon_momentum * m if self.muon_nesterov else m).view(R, K)
+            x = bf(u / (u.norm() + 1e-7))
+            x = x.t() if rec["transpose"] else x
+            for _ in range(self.muon_ns_steps):
+                A = bf(x @ x.t())
+                B = bf(b * A + c * (A @ A))
+                x = bf(a * x + B @ x)
+            o_dir = (x.t() if rec["transpose"] else x).reshape(-1)
+            w = master[sl]
+            master[sl] = (w - (lr * self.wd) * w) - (lr * float(self.muon_q[int(rec["seg"])])) * o_dir
+        self.mom[aux] = m_aux
+        master[aux] = w_aux
 
     def _lamb_update(self, master, g, lr):
         """csrc/lamb.hip's three stages in fp32 torch (the norms in fp64, as the kernels'
@@ -629,6 +671,8 @@ class CPUBackend:
             m["optimizer"] = "lion"
         if self.rmsprop:
             m["optimizer"] = "rmsprop"
+        if self.muon:
+            m["optimizer"] = "muon"
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -714,7 +758,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
                  rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
-                 rmsprop_decay_skip: str = "none"):
+                 rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
+                 muon_nesterov: bool = True, muon_ns_steps: int = 5,
+                 muon_aux_lr_scale: float = 1.0):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -725,7 +771,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                 lion_decay_skip=lion_decay_skip, rmsprop_rho=rmsprop_rho,
                 rmsprop_momentum=rmsprop_momentum, rmsprop_epsilon=rmsprop_epsilon,
                 rmsprop_centered=rmsprop_centered, rmsprop_wd=rmsprop_wd,
-                rmsprop_decay_skip=rmsprop_decay_skip)
+                rmsprop_decay_skip=rmsprop_decay_skip, muon_momentum=muon_momentum,
+                muon_nesterov=muon_nesterov, muon_ns_steps=muon_ns_steps,
+                muon_aux_lr_scale=muon_aux_lr_scale)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

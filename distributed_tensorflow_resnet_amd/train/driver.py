@@ -243,7 +243,11 @@ def main(argv=None, kind: str = "cifar") -> int:
                            rmsprop_epsilon=flags.rmsprop_epsilon,
                            rmsprop_centered=flags.rmsprop_centered,
                            rmsprop_wd=flags.rmsprop_wd,
-                           rmsprop_decay_skip=flags.rmsprop_decay_skip)
+                           rmsprop_decay_skip=flags.rmsprop_decay_skip,
+                           muon_momentum=flags.muon_momentum,
+                           muon_nesterov=flags.muon_nesterov,
+                           muon_ns_steps=flags.muon_ns_steps,
+                           muon_aux_lr_scale=flags.muon_aux_lr_scale)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

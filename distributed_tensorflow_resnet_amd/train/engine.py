@@ -55,7 +55,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
-                     OPT_FUSED_LION_REASON, check_lion, OPT_FUSED_RMSPROP_REASON, check_rmsprop)
+                     OPT_FUSED_LION_REASON, check_lion, OPT_FUSED_RMSPROP_REASON, check_rmsprop,
+                     MUON_DTYPE, OPT_FUSED_MUON_REASON, check_muon, muon_tables)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -141,7 +142,9 @@ class Engine:
                  lion_decay_skip: str = "none", rmsprop_rho: float = 0.9,
                  rmsprop_momentum: float = 0.9, rmsprop_epsilon: float = 1e-10,
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
-                 rmsprop_decay_skip: str = "none"):
+                 rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
+                 muon_nesterov: bool = True, muon_ns_steps: int = 5,
+                 muon_aux_lr_scale: float = 1.0):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -156,7 +159,7 @@ class Engine:
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion or rmsprop, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon or rmsprop, got {optimizer!r}")
         if lars_skip not in LARS_SKIPS:
             raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
         # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
@@ -193,6 +196,14 @@ class Engine:
                                                 rmsprop_centered, rmsprop_wd, rmsprop_decay_skip)
         # (rmsprop_wd is the mode, as adam_decay; the per-segment table is rmsprop_wd_seg)
         self.rmsprop_wd, self.rmsprop_decay_skip = rmsprop_wd, rmsprop_decay_skip
+        # muon: every conv kernel moves along its orthogonalised momentum (csrc/muon.hip: one
+        # workgroup per tensor runs Newton-Schulz on chip, then one flat update launch); every
+        # other tensor takes mom's update at lr * muon_aux_lr_scale.  The momentum buffer is the
+        # only state; the direction buffer and three small tables exist only for it
+        self.muon = optimizer == "muon"
+        (self.muon_momentum, self.muon_nesterov, self.muon_ns_steps,
+         self.muon_aux_lr_scale) = check_muon(muon_momentum, muon_nesterov, muon_ns_steps,
+                                              muon_aux_lr_scale, self.clip_grad_norm, optimizer)
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -328,6 +339,7 @@ class Engine:
             self.rms_ms = torch.ones(self.params.n_train, device=dev)   # TF's `rms` slot: ones
             if self.rmsprop_centered:
                 self.rms_mg = torch.zeros(self.params.n_train, device=dev)
+        self.muon_dir = torch.zeros(self.params.n_train, device=dev) if self.muon else None
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
         # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
         self.scalars = torch.zeros(8, device=dev)
@@ -386,6 +398,9 @@ class Engine:
         if self.rmsprop and self.opt_fused:   # (before clipping, as adamw)
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_RMSPROP_REASON
+        if self.muon and self.opt_fused:
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_MUON_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -503,6 +518,15 @@ class Engine:
         if self.rmsprop:   # the same table under rmsprop_decay_skip
             self.rmsprop_wd_seg = torch.from_numpy(adam_decay_table(
                 [s.shape for s in ps.train_slots], self.wd, self.rmsprop_decay_skip)).to(dev)
+        self.muon_tab = self.muon_seg = self.muon_q = None
+        if self.muon:
+            # one record per conv kernel (refused by name outside muon_covers), and per segment
+            # whether it is one and its q = sqrt(max(1, K / R))
+            tab, seg, q = muon_tables(ps.train_slots)
+            assert MUON_DTYPE.itemsize == self.nat.muon_tensor_bytes()
+            self.muon_shapes = ([int(r) for r in tab["R"]], [int(k) for k in tab["K"]])
+            self.muon_tab = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+            self.muon_seg, self.muon_q = torch.from_numpy(seg).to(dev), torch.from_numpy(q).to(dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:
             # chunk partials and the {norm, scale} slot: fixed pointers
@@ -1147,6 +1171,8 @@ class Engine:
             m["optimizer"] = "lion"
         if self.rmsprop:
             m["optimizer"] = "rmsprop"
+        if self.muon:
+            m["optimizer"] = "muon"
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8

@@ -100,6 +100,8 @@ class LoggingTensorHook(Hook):
                 clip += ", optimizer: lion"
             if m.get("optimizer") == "rmsprop":   # --optimizer rmsprop
                 clip += ", optimizer: rmsprop"
+            if m.get("optimizer") == "muon":   # --optimizer muon
+                clip += ", optimizer: muon"
             mix = ""
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"

@@ -134,7 +134,7 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
-OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion", "rmsprop")
+OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion", "muon", "rmsprop")
 ADAM_DECAYS = ("decoupled", "l2")
 ADAM_DECAY_SKIPS = ("none", "vectors")
 OPT_FUSED_ADAM_REASON = ("optimizer adamw: the one-launch optimizer is SGD-momentum; adamw takes "
@@ -208,6 +208,64 @@ def check_lion(beta1, beta2, decay_skip: str = "none"):
     if decay_skip not in ADAM_DECAY_SKIPS:
         raise ValueError(f"lion_decay_skip must be one of {ADAM_DECAY_SKIPS}, got {decay_skip!r}")
     return b1, b2
+
+
+OPT_FUSED_MUON_REASON = ("optimizer muon: the update of a conv kernel is a matrix function of its "
+                         "whole gradient (Newton-Schulz); it takes two generic launches")
+MUON_DTYPE = np.dtype([   # csrc/optim.h MuonTensor
+    ("offset", "<i8"), ("seg", "<i4"), ("R", "<i4"), ("K", "<i4"), ("transpose", "<i4"),
+])
+MUON_SHORT, MUON_LONG = 64, 576   # csrc/muon.hip muon_covers: what one workgroup holds in LDS
+
+
+def muon_covers(R: int, K: int) -> bool:
+    """Host mirror of csrc/muon.hip muon_covers."""
+    return 1 <= min(R, K) <= MUON_SHORT and max(R, K) <= MUON_LONG
+
+
+def check_muon(momentum=0.95, nesterov=True, ns_steps=5, aux_lr_scale=1.0,
+               clip_grad_norm: float = 0.0, optimizer: str = "muon"):
+    """The muon flags as both backends take them: (momentum, nesterov, ns_steps,
+    aux_lr_scale).  momentum in [0, 1) (in fp32 too), 1 <= ns_steps <= 8, aux_lr_scale > 0
+    and finite.  With the muon optimizer, clip_grad_norm is refused: the direction of every
+    conv kernel is normalised anyway."""
+    try:
+        mu, steps, aux = float(momentum), int(ns_steps), float(aux_lr_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"muon_momentum, muon_ns_steps and muon_aux_lr_scale must be numbers, "
+                         f"got {momentum!r}, {ns_steps!r}, {aux_lr_scale!r}") from None
+    if not 0.0 <= mu < 1.0 or float(np.float32(mu)) >= 1.0:   # NaN included
+        raise ValueError(f"muon_momentum must be in [0, 1), got {mu!r}")
+    if steps != float(ns_steps) or not 1 <= steps <= 8:
+        raise ValueError(f"muon_ns_steps must be an integer in [1, 8], got {ns_steps!r}")
+    if not 0.0 < float(np.float32(aux)) < float("inf"):
+        raise ValueError(f"muon_aux_lr_scale must be positive (and finite in fp32), got {aux!r}")
+    if optimizer == "muon" and float(clip_grad_norm) > 0:
+        raise ValueError("clip_grad_norm cannot be combined with optimizer muon: the direction "
+                         "of every conv kernel is normalised anyway")
+    return mu, bool(nesterov), steps, aux
+
+
+def muon_tables(train_slots):
+    """The tables of the muon launches (csrc/muon.hip), from the trainable slots in segment
+    order: the MuonTensor records (numpy, MUON_DTYPE; one per conv kernel, its HWIO master the
+    row-major R x K matrix, R = kh kw C), muon_seg (int32 per segment, 1 = conv kernel) and
+    q_seg (fp32 per segment: sqrt(max(1, K / R)) of a conv kernel, 0 elsewhere).  A conv
+    kernel outside muon_covers is refused by name."""
+    recs, seg, q = [], np.zeros(len(train_slots), np.int32), np.zeros(len(train_slots), np.float32)
+    for i, s in enumerate(train_slots):
+        if s.kind != "conv":
+            continue
+        K = int(s.shape[-1])
+        R = int(s.numel) // K
+        if not muon_covers(R, K):
+            raise ValueError(f"optimizer muon: conv kernel {s.name} is the matrix {R} x {K}; one "
+                             f"workgroup orthogonalises a short side <= {MUON_SHORT} and a long "
+                             f"side <= {MUON_LONG} (the CIFAR networks)")
+        recs.append((int(s.offset), i, R, K, int(K <= R)))
+        seg[i] = 1
+        q[i] = np.sqrt(np.float32(max(1.0, K / R)))
+    return np.array(recs, dtype=MUON_DTYPE), seg, q
 
 
 OPT_FUSED_RMSPROP_REASON = ("optimizer rmsprop: the one-launch optimizer is SGD-momentum; rmsprop "

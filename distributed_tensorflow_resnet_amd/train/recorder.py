@@ -681,6 +681,25 @@ class StepRecorder:
                         out.op_buffers[i0 + 1] = {"clip"}
                     out.op_buffers[i1] = (gb | pb | {"rmsprop", "lr", "gstep"}
                                           | ({"clip"} if clip else set()))
+            elif e.muon:
+                # two launches (csrc/muon.hip): one workgroup per conv kernel writes m' and the
+                # orthogonalised direction, then the flat update reads it (other tensors: mom's
+                # update at lr * muon_aux_lr_scale).  grad is complete here, as for lars
+                i0 = plan.muon_orthogonalize(grad, mom, e.muon_dir.data_ptr(),
+                                             e.muon_tab.data_ptr(), *e.muon_shapes,
+                                             e.muon_momentum, int(e.muon_nesterov),
+                                             e.muon_ns_steps, 1.0)
+                i1 = plan.muon_update_pack(master, grad, mom, e.muon_dir.data_ptr(),
+                                           e.params.n_train, *e.sched.launch_args(),
+                                           e.gstep.data_ptr(), e.momentum, e.wd,
+                                           e.muon_aux_lr_scale, 1.0, e.segs.data_ptr(), e.nseg,
+                                           e.muon_seg.data_ptr(), e.muon_q.data_ptr(),
+                                           e.wbf.data_ptr(), sp + 8, *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
+                    out.op_buffers[i0] = gb | {"muon"}
+                    out.op_buffers[i1] = gb | pb | {"muon", "lr", "gstep"}
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

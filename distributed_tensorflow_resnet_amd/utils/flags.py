@@ -17,6 +17,9 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
                      --adam_trust on makes it LAMB (per-tensor trust ratios), --adam_trust_skip
   --optimizer lion   Lion (sign of an interpolated momentum, one state buffer) in one device
                      launch: --lion_beta1/_beta2, --lion_decay_skip
+  --optimizer muon   Muon: conv kernels move along their momentum orthogonalised by Newton-Schulz
+                     on the matrix cores (CIFAR networks): --muon_momentum, --muon_nesterov,
+                     --muon_ns_steps, --muon_aux_lr_scale
   --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
                      one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
                      --rmsprop_wd, --rmsprop_decay_skip
@@ -237,6 +240,15 @@ class FlagParser(argparse.ArgumentParser):
                               ns.rmsprop_centered, ns.rmsprop_wd, ns.rmsprop_decay_skip)
             except ValueError as e:
                 self.error(str(e))
+        if hasattr(ns, "muon_momentum"):
+            from ..train.layout import check_muon
+
+            try:
+                check_muon(ns.muon_momentum, ns.muon_nesterov, ns.muon_ns_steps,
+                           ns.muon_aux_lr_scale, getattr(ns, "clip_grad_norm", 0.0),
+                           getattr(ns, "optimizer", "mom"))
+            except ValueError as e:
+                self.error(str(e))
         if hasattr(ns, "adam_trust"):
             from ..train.layout import check_adam_trust
 
@@ -344,7 +356,7 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion", "rmsprop"),
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion", "muon", "rmsprop"),
                    help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
                         "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
                         "epsilon) (layer-wise adaptive rate scaling, for large global batches).  "
@@ -358,7 +370,22 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "epsilon inside the square root, ms from ones, no bias correction; the "
                         "presets' learning rates (0.1 / 0.4) are SGD rates, so set --lr_peak "
                         "(e.g. 1e-3) with it; the recipe-scale epsilon (TF-slim uses 1.0) is "
-                        "--rmsprop_epsilon's to set.")
+                        "--rmsprop_epsilon's to set.  muon (Jordan et al. 2024; CIFAR networks): "
+                        "every conv kernel, as the matrix [kh kw C] x [K], moves along its "
+                        "Nesterov momentum orthogonalised by a quintic Newton-Schulz iteration "
+                        "(bf16 on the matrix cores), at lr * sqrt(max(1, K / R)) with decoupled "
+                        "weight decay; BN and dense tensors take mom's update at lr * "
+                        "--muon_aux_lr_scale.  Not with --clip_grad_norm.")
+    p.add_argument("--muon_momentum", type=float, default=0.95,
+                   help="muon: momentum of the conv kernels, in [0, 1) (the other tensors keep "
+                        "mom's 0.9).")
+    p.add_bool("muon_nesterov", True,
+               "muon: orthogonalise g + mu * m' (Nesterov) instead of the accumulator m'.")
+    p.add_argument("--muon_ns_steps", type=int, default=5,
+                   help="muon: Newton-Schulz steps, 1..8.")
+    p.add_argument("--muon_aux_lr_scale", type=float, default=1.0,
+                   help="muon: the rate of the tensors that are not conv kernels is lr times "
+                        "this, > 0.")
     p.add_argument("--adam_beta1", type=_adam_beta, default=0.9,
                    help="adamw: decay of the first moment, in [0, 1).")
     p.add_argument("--adam_beta2", type=_adam_beta, default=0.999,

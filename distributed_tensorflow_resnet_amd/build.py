@@ -38,6 +38,7 @@ COMMON_FLAGS = [
 # muon.hip: no packed fp32 arithmetic (v_pk_*_f32) in its element-wise passes
 FILE_FLAGS: dict = {
     "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "muon_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

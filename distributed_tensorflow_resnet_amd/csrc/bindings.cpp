@@ -1048,6 +1048,72 @@ static Launch mk_muon_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir
                                    nseg, muon_seg, q_seg, bf, lr_out, kPiecewise);
 }
 
+// The tiled Muon launches (muon_tiled.hip).  The tables are device copies of what
+// train/layout.py muon_tiled_tables builds; the counts are the host's.
+static Launch mk_muon_tiled_moments(ptr_t grad, ptr_t mom, ptr_t tab, ptr_t blk_t, int nblocks,
+                                    ptr_t part, float momentum, int nesterov, float grad_scale) {
+  if (!grad || !mom || !tab || !blk_t || !part)
+    throw std::invalid_argument("muon_tiled_moments: null buffer");
+  if ((grad | mom) & 15)
+    throw std::invalid_argument("muon_tiled_moments: grad and mom must be 16-byte aligned");
+  if (nblocks <= 0) throw std::invalid_argument("muon_tiled_moments: at least one chunk");
+  if (!(momentum >= 0.f && momentum < 1.f))
+    throw std::invalid_argument("muon_tiled_moments: momentum in [0, 1)");
+  return [=](hipStream_t s) {
+    muon_tiled_moments(P<const float>(grad), P<float>(mom), P<const MuonTiledTensor>(tab),
+                       P<const int>(blk_t), nblocks, P<double>(part), momentum, nesterov,
+                       grad_scale, s);
+  };
+}
+
+static Launch mk_muon_tiled_stage(ptr_t grad, ptr_t mom, ptr_t tab, ptr_t work, int nwork,
+                                  ptr_t part, ptr_t scratch, float momentum, int nesterov,
+                                  float grad_scale) {
+  if (!grad || !mom || !tab || !work || !part || !scratch)
+    throw std::invalid_argument("muon_tiled_stage: null buffer");
+  if (scratch & 15) throw std::invalid_argument("muon_tiled_stage: scratch must be 16-byte aligned");
+  if (nwork <= 0) throw std::invalid_argument("muon_tiled_stage: at least one tile");
+  return [=](hipStream_t s) {
+    muon_tiled_stage(P<const float>(grad), P<const float>(mom), P<const MuonTiledTensor>(tab),
+                     P<const MuonWork>(work), nwork, P<const double>(part), P<bf16>(scratch),
+                     momentum, nesterov, grad_scale, s);
+  };
+}
+
+static Launch mk_muon_tiled_syrk(ptr_t scratch, ptr_t tab, ptr_t work, int nwork, int epi) {
+  if (!scratch || !tab || !work) throw std::invalid_argument("muon_tiled_syrk: null buffer");
+  if (scratch & 15) throw std::invalid_argument("muon_tiled_syrk: scratch must be 16-byte aligned");
+  if (nwork <= 0) throw std::invalid_argument("muon_tiled_syrk: at least one tile");
+  if (epi != 0 && epi != 1) throw std::invalid_argument("muon_tiled_syrk: epi 0 (A) or 1 (B)");
+  return [=](hipStream_t s) {
+    muon_tiled_syrk(P<bf16>(scratch), P<const MuonTiledTensor>(tab), P<const MuonWork>(work),
+                    nwork, epi, s);
+  };
+}
+
+static Launch mk_muon_tiled_apply(ptr_t scratch, ptr_t tab, ptr_t work, int nwork, int max_sp) {
+  if (!scratch || !tab || !work) throw std::invalid_argument("muon_tiled_apply: null buffer");
+  if (scratch & 15) throw std::invalid_argument("muon_tiled_apply: scratch must be 16-byte aligned");
+  if (nwork <= 0) throw std::invalid_argument("muon_tiled_apply: at least one column block");
+  if (max_sp < MUON_TILE || max_sp > MUON_TILED_SHORT || max_sp % MUON_TILE)
+    throw std::invalid_argument("muon_tiled_apply: max_sp must be a multiple of 64 in [64, 1024]");
+  return [=](hipStream_t s) {
+    muon_tiled_apply(P<bf16>(scratch), P<const MuonTiledTensor>(tab), P<const MuonWork>(work),
+                     nwork, max_sp, s);
+  };
+}
+
+static Launch mk_muon_tiled_unstage(ptr_t scratch, ptr_t dir, ptr_t tab, ptr_t work, int nwork) {
+  if (!scratch || !dir || !tab || !work)
+    throw std::invalid_argument("muon_tiled_unstage: null buffer");
+  if (scratch & 15) throw std::invalid_argument("muon_tiled_unstage: scratch must be 16-byte aligned");
+  if (nwork <= 0) throw std::invalid_argument("muon_tiled_unstage: at least one tile");
+  return [=](hipStream_t s) {
+    muon_tiled_unstage(P<const bf16>(scratch), P<float>(dir), P<const MuonTiledTensor>(tab),
+                       P<const MuonWork>(work), nwork, s);
+  };
+}
+
 // The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
 static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
                       const std::string& decay_mode) {
@@ -1913,6 +1979,11 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack);
   def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack_decay);
   def_op(m, plan, "muon_orthogonalize", mk_muon_orthogonalize);
+  def_op(m, plan, "muon_tiled_moments", mk_muon_tiled_moments);
+  def_op(m, plan, "muon_tiled_stage", mk_muon_tiled_stage);
+  def_op(m, plan, "muon_tiled_syrk", mk_muon_tiled_syrk);
+  def_op(m, plan, "muon_tiled_apply", mk_muon_tiled_apply);
+  def_op(m, plan, "muon_tiled_unstage", mk_muon_tiled_unstage);
   def_op(m, plan, "muon_update_pack", mk_muon_update_pack);
   def_op(m, plan, "muon_update_pack", mk_muon_update_pack_decay);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
@@ -2027,6 +2098,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("lars_seg_bytes", []() { return (int)sizeof(LarsSeg); });
   m.def("muon_tensor_bytes", []() { return (int)sizeof(MuonTensor); });
   m.def("muon_covers", &muon_covers);
+  m.def("muon_tiled_tensor_bytes", []() { return (int)sizeof(MuonTiledTensor); });
+  m.def("muon_work_bytes", []() { return (int)sizeof(MuonWork); });
+  m.def("muon_tiled_covers", &muon_tiled_covers);
+  m.def("muon_tiled_apply_lds", &muon_tiled_apply_lds);
   m.attr("LARS_CHUNK") = (int)LARS_CHUNK;
   m.attr("CLIP_CHUNK") = (int)CLIP_CHUNK;
   m.def("clip_chunks", &clip_chunks, "workgroups (fp64 partials) of grad_sqnorm over n elements");

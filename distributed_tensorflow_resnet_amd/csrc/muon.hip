@@ -42,8 +42,9 @@
 //   * grad is only read; O goes out as fp32 to dir at the tensor's offset.
 // Launch 2, muon_update_pack: a FlatWalk launch in lion_update_pack's shape.  muon_seg[segment]
 // != 0: the weight update above from dir, contraction off, one rounding per operation; the
-// other segments run SgdStep<false> itself at lr * aux_scale.  ohwi_pack follows.
-#include "optim_device.h"
+// other segments take SgdStep<false>'s update at lr * aux_scale with sgd_pack_kernel's own
+// roundings (MuonAuxStep), bit for bit what `mom` gives them.  ohwi_pack follows.
+#include "muon_device.h"
 
 namespace dtr {
 
@@ -55,21 +56,10 @@ constexpr int MUON_XT_B = MUON_LONG * MUON_SHORT * 2;
 constexpr int MUON_AB_B = MUON_SHORT * MUON_SHORT * 2;
 constexpr int MUON_LDS = MUON_X_B + MUON_XT_B + MUON_AB_B + MUON_WAVES * 8;
 static_assert(MUON_LDS <= 163840, "LDS");
-constexpr float NS_A = 3.4445f, NS_B = -4.7750f, NS_C = 2.0315f;
 
 bool muon_covers(int R, int K) {
   const int s = R < K ? R : K, l = R < K ? K : R;
   return s >= 1 && s <= MUON_SHORT && l <= MUON_LONG;
-}
-
-__device__ __forceinline__ void muon_moment(float g, float& m, float s, float mu, int nesterov,
-                                            float& u) {
-#pragma clang fp contract(off)
-  const float gp = s * g;
-  const float mm = mu * m;
-  m = mm + gp;
-  const float t = mu * m;
-  u = nesterov ? gp + t : m;
 }
 
 // Element (short i, long c) of XT.
@@ -251,12 +241,53 @@ __device__ __forceinline__ void muon_elem(float& w, float d, float lrwd, float l
   w = kept - step;
 }
 
-// FlatWalk's step: a muon segment moves along dir, any other takes SgdStep<false> at lr_aux.
+// SgdStep<false>'s update with momentum for the other segments, written out with the roundings
+// that sgd_pack_kernel has on its two paths (tests/golden/optim_bits.json pins them), so that
+// such a tensor moves exactly as under `mom`: left to the compiler, this kernel contracted
+// g' + wd w the other way round (fma(s, g, wd w)), one ulp off in about 2 % of the elements.
+//   four elements: gv = fma(wd, w, s g);  one element: gv = wd w + s g, both products rounded;
+//   then acc = fma(momentum, m, gv), w' = fma(-rate, acc, w).
+struct MuonAuxStep {
+  const float* __restrict__ g;
+  float* __restrict__ mom;
+  float rate, momentum, wd, grad_scale;
+
+  __device__ __forceinline__ void tail(float gv, float& m, float& w) const {
+    m = __builtin_fmaf(momentum, m, gv);
+    w = __builtin_fmaf(-rate, m, w);
+  }
+
+  __device__ __forceinline__ void operator()(long e0, f32x4& wv) const {
+#pragma clang fp contract(off)
+    const f32x4 gv = ld4<false>(g + e0);
+    f32x4 mv = ld4<false>(mom + e0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sg = gv[j] * grad_scale;
+      float mj = mv[j], wj = wv[j];
+      tail(__builtin_fmaf(wd, wj, sg), mj, wj);
+      mv[j] = mj;
+      wv[j] = wj;
+    }
+    st4<false>(mom + e0, mv);
+  }
+
+  __device__ __forceinline__ void operator()(long e, float& wj) const {
+#pragma clang fp contract(off)
+    const float dec = wd * wj;
+    const float sg = g[e] * grad_scale;
+    float mj = mom[e];
+    tail(dec + sg, mj, wj);
+    mom[e] = mj;
+  }
+};
+
+// FlatWalk's step: a muon segment moves along dir, any other takes MuonAuxStep at lr_aux.
 struct MuonStep {
   const float* __restrict__ dir;
   const int* __restrict__ muon_seg;
   const float* __restrict__ q_seg;
-  SgdStep<false> aux;
+  MuonAuxStep aux;
   float lr, wd;
   static constexpr bool update = true;
 
@@ -271,13 +302,13 @@ struct MuonStep {
         wv[j] = wj;
       }
     } else {
-      aux(sgi, e0, wv);
+      aux(e0, wv);
     }
   }
 
   __device__ __forceinline__ void operator()(int sgi, long e, float& wj) const {
     if (muon_seg[sgi]) muon_elem(wj, dir[e], lr * wd, lr * q_seg[sgi]);
-    else aux(sgi, e, wj);
+    else aux(e, wj);
   }
 };
 
@@ -299,7 +330,7 @@ muon_pack_kernel(float* __restrict__ w, const float* __restrict__ g, float* __re
   const float lr = lr_s;
   walk.run(w, n, bf,
            MuonStep{dir, muon_seg, q_seg,
-                    SgdStep<false>{g, mom, nullptr, lr * aux_scale, momentum, wd, grad_scale, 1, 1},
+                    MuonAuxStep{g, mom, lr * aux_scale, momentum, wd, grad_scale},
                     lr, wd});
 }
 

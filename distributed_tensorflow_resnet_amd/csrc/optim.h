@@ -170,6 +170,52 @@ void muon_update_pack(float* master, const float* grad, float* mom, const float*
                       float aux_scale, float grad_scale, const ParamSeg* segs, int nseg,
                       const int* muon_seg, const float* q_seg, bf16* bf, float* lr_out,
                       hipStream_t st);
+// Tiled Muon (muon_tiled.hip): the same iteration for matrices one workgroup cannot hold, as
+// grouped launches over host-built work tables, the operands in a bf16 device scratch.
+constexpr int MUON_TILE = 64;   // output tile of the GEMM launches, k-tile, and the padding unit
+constexpr int MUON_TILED_SHORT = 1024, MUON_TILED_LONG = 8192;   // muon_tiled_covers
+struct MuonTiledTensor {
+  long long offset;              // of the row-major R x K master in the flat buffers
+  long long x_off, a_off, b_off; // bf16 elements into the scratch (multiples of 8): X[SP][LP],
+                                 // A[SP][SP], B[SP][SP]
+  long long chunk0;              // its first LARS_CHUNK-element chunk in the moments launch
+  int nchunks;
+  int seg;                       // its parameter segment
+  int R, K;
+  int transpose;                 // (K <= R): X = M^T
+  int SP, LP;                    // short and long side, rounded up to MUON_TILE
+  int pad;
+};
+// One workgroup of a tiled launch.  stage / unstage: the MUON_TILE^2 tile (short i, long j) of
+// X.  syrk: the output tile (i, j), i <= j; len = the reduction length.  apply: the block of
+// j long-side columns from i * j on; len = SP.
+struct MuonWork {
+  int t;                         // index into the MuonTiledTensor table
+  int i, j, len;
+};
+// Short side <= 1024 and long side <= 8192.
+bool muon_tiled_covers(int R, int K);
+// Dynamic LDS of muon_tiled_apply for a table whose largest SP is max_sp.
+int muon_tiled_apply_lds(int max_sp);
+// One workgroup per chunk (blk_t[b] = its tensor): m' = momentum m + g' in place and
+// part[b] = the chunk's sum of u^2 (fp64 from the wave on).  grad and mom 16-byte aligned.
+void muon_tiled_moments(const float* grad, float* mom, const MuonTiledTensor* tab,
+                        const int* blk_t, int nblocks, double* part, float momentum,
+                        int nesterov, float grad_scale, hipStream_t st);
+// X0 = bf16(u / (||u||_F + 1e-7)) and the zero padding; the norm from the tensor's chunk
+// partials in chunk order, u formed again from grad and the stored m'.
+void muon_tiled_stage(const float* grad, const float* mom, const MuonTiledTensor* tab,
+                      const MuonWork* work, int nwork, const double* part, bf16* scratch,
+                      float momentum, int nesterov, float grad_scale, hipStream_t st);
+// epi 0: A = bf16(X X^T); epi 1: B = bf16(b A + c (A A)).  Upper-triangle tiles, stored twice.
+void muon_tiled_syrk(bf16* scratch, const MuonTiledTensor* tab, const MuonWork* work, int nwork,
+                     int epi, hipStream_t st);
+// X = bf16(a X + B X) in place, a workgroup per block of long-side columns.
+void muon_tiled_apply(bf16* scratch, const MuonTiledTensor* tab, const MuonWork* work, int nwork,
+                      int max_sp, hipStream_t st);
+// dir = X as fp32 in M's orientation, the tensor's own elements only.
+void muon_tiled_unstage(const bf16* scratch, float* dir, const MuonTiledTensor* tab,
+                        const MuonWork* work, int nwork, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

@@ -368,3 +368,84 @@ def muon_orthogonalize(grad, mom, shapes, offsets=None, *, momentum=0.95, nester
                                 [R for R, _ in shapes], [K for _, K in shapes], float(momentum),
                                 int(bool(nesterov)), int(steps), float(grad_scale), _stream())
     return out
+
+
+def muon_tiled_buffers(tt, device):
+    """Device copies of train/layout.py muon_tiled_tables' dict, the chunk partials and the
+    bf16 scratch (X, A and B of every tensor) of the tiled muon launches."""
+    import numpy as np
+
+    from ..train.layout import MUON_TILED_DTYPE, MUON_WORK_DTYPE
+
+    nat = native()
+    assert MUON_TILED_DTYPE.itemsize == nat.muon_tiled_tensor_bytes()
+    assert MUON_WORK_DTYPE.itemsize == nat.muon_work_bytes()
+    raw = lambda a: torch.from_numpy(a.view(np.uint8).copy()).to(device)   # noqa: E731
+    buf = {k: raw(tt[k]) for k in ("tab", "stage", "syrk_a", "syrk_b", "apply")}
+    buf["n"] = {k: len(tt[k]) for k in ("stage", "syrk_a", "syrk_b", "apply", "blk")}
+    buf["blk"] = torch.from_numpy(tt["blk"]).to(device)
+    buf["part"] = torch.zeros(len(tt["blk"]), dtype=torch.float64, device=device)
+    buf["scratch"] = torch.zeros(tt["scratch"], dtype=BF16, device=device)
+    buf["max_sp"] = tt["max_sp"]
+    return buf
+
+
+def muon_tiled_sequence(api, buf, grad, mom, out, momentum, nesterov, steps, grad_scale, tail=()):
+    """The 3 + 3 * steps tiled muon launches (csrc/muon_tiled.hip) through `api`: the native
+    module (tail = the stream) or a plan being recorded (tail empty).  grad, mom and out are
+    pointers.  Returns what the calls returned (a plan's op indices)."""
+    n, p = buf["n"], {k: v.data_ptr() for k, v in buf.items() if torch.is_tensor(v)}
+    mu, nes, gs = float(momentum), int(bool(nesterov)), float(grad_scale)
+    ops = [api.muon_tiled_moments(grad, mom, p["tab"], p["blk"], n["blk"], p["part"], mu, nes, gs,
+                                  *tail),
+           api.muon_tiled_stage(grad, mom, p["tab"], p["stage"], n["stage"], p["part"],
+                                p["scratch"], mu, nes, gs, *tail)]
+    for _ in range(int(steps)):
+        ops += [api.muon_tiled_syrk(p["scratch"], p["tab"], p["syrk_a"], n["syrk_a"], 0, *tail),
+                api.muon_tiled_syrk(p["scratch"], p["tab"], p["syrk_b"], n["syrk_b"], 1, *tail),
+                api.muon_tiled_apply(p["scratch"], p["tab"], p["apply"], n["apply"],
+                                     buf["max_sp"], *tail)]
+    ops.append(api.muon_tiled_unstage(p["scratch"], out, p["tab"], p["stage"], n["stage"], *tail))
+    return ops
+
+
+def muon_orthogonalize_tiled(grad, mom, shapes, offsets=None, *, momentum=0.95, nesterov=True,
+                             steps=5, grad_scale=1.0, out=None):
+    """muon_orthogonalize's contract for matrices of any covered size: a shape inside
+    muon_covers goes to muon_orthogonalize's one workgroup, any other with a short side <= 1024
+    and a long side <= 8192 to the tiled launches of csrc/muon_tiled.hip (grad and mom must
+    then be 16-byte aligned); anything else raises.  Returns ``out``."""
+    from ..train.layout import muon_covers, muon_tiled_covers, muon_tiled_tables
+
+    _check(grad, torch.float32, 1, "grad")
+    _check(mom, torch.float32, 1, "mom")
+    out = torch.zeros_like(grad) if out is None else out
+    _check(out, torch.float32, 1, "out")
+    if offsets is None:
+        offsets = [0]
+        for R, K in shapes[:-1]:
+            offsets.append(offsets[-1] + R * K)
+    if len(offsets) != len(shapes) or mom.numel() != grad.numel() or out.numel() != grad.numel():
+        raise ValueError("one offset per shape, and grad, mom and out of one length")
+    if not 1 <= int(steps) <= 8 or not 0.0 <= float(momentum) < 1.0:
+        raise ValueError("steps in [1, 8] and momentum in [0, 1)")
+    small, big = [], []
+    for i, (o, (R, K)) in enumerate(zip(offsets, shapes)):
+        if R < 1 or K < 1 or o < 0 or o + R * K > grad.numel():
+            raise ValueError(f"matrix {R} x {K} at {o} is outside the {grad.numel()} elements")
+        if muon_covers(R, K):
+            small.append((o, (R, K)))
+        elif muon_tiled_covers(R, K):
+            big.append((int(o), i, int(R), int(K)))
+        else:
+            raise ValueError(f"matrix {R} x {K}: the tiled launches take a short side <= 1024 "
+                             f"and a long side <= 8192")
+    if small:
+        muon_orthogonalize(grad, mom, [s for _, s in small], [o for o, _ in small],
+                           momentum=momentum, nesterov=nesterov, steps=steps,
+                           grad_scale=grad_scale, out=out)
+    if big:
+        buf = muon_tiled_buffers(muon_tiled_tables(big), grad.device)
+        muon_tiled_sequence(native(), buf, grad.data_ptr(), mom.data_ptr(), out.data_ptr(),
+                            momentum, nesterov, steps, grad_scale, tail=(_stream(),))
+    return out

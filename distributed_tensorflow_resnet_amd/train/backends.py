@@ -170,7 +170,7 @@ class CPUBackend:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -283,7 +283,10 @@ class CPUBackend:
          self.muon_aux_lr_scale) = check_muon(muon_momentum, muon_nesterov, muon_ns_steps,
                                               muon_aux_lr_scale, self.clip_grad_norm, optimizer)
         if self.muon:
-            self.muon_tab, seg, self.muon_q = muon_tables(self.store.train_slots)
+            # (muon_tiled: the conv kernels the one-workgroup kernel refuses join the same loop)
+            tab, seg, self.muon_q, *tiled = muon_tables(self.store.train_slots,
+                                                        tiled=bool(muon_tiled))
+            self.muon_tab = list(tab) + (list(tiled[0]["tab"]) if tiled else [])
             self.muon_mask = torch.repeat_interleave(
                 torch.from_numpy(seg).bool(), torch.tensor([s.numel for s in self.store.train_slots]))
         if lars_skip not in ("vectors", "none"):
@@ -760,7 +763,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -773,7 +776,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                 rmsprop_centered=rmsprop_centered, rmsprop_wd=rmsprop_wd,
                 rmsprop_decay_skip=rmsprop_decay_skip, muon_momentum=muon_momentum,
                 muon_nesterov=muon_nesterov, muon_ns_steps=muon_ns_steps,
-                muon_aux_lr_scale=muon_aux_lr_scale)
+                muon_aux_lr_scale=muon_aux_lr_scale, muon_tiled=muon_tiled)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

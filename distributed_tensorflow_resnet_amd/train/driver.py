@@ -247,7 +247,8 @@ def main(argv=None, kind: str = "cifar") -> int:
                            muon_momentum=flags.muon_momentum,
                            muon_nesterov=flags.muon_nesterov,
                            muon_ns_steps=flags.muon_ns_steps,
-                           muon_aux_lr_scale=flags.muon_aux_lr_scale)
+                           muon_aux_lr_scale=flags.muon_aux_lr_scale,
+                           muon_tiled=flags.muon_tiled)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

@@ -144,7 +144,7 @@ class Engine:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -204,6 +204,9 @@ class Engine:
         (self.muon_momentum, self.muon_nesterov, self.muon_ns_steps,
          self.muon_aux_lr_scale) = check_muon(muon_momentum, muon_nesterov, muon_ns_steps,
                                               muon_aux_lr_scale, self.clip_grad_norm, optimizer)
+        # muon_tiled: conv kernels outside muon_covers (the ImageNet networks) take the tiled
+        # launches of csrc/muon_tiled.hip instead of being refused; off: nothing allocated
+        self.muon_tiled = bool(muon_tiled) and self.muon
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -518,14 +521,19 @@ class Engine:
         if self.rmsprop:   # the same table under rmsprop_decay_skip
             self.rmsprop_wd_seg = torch.from_numpy(adam_decay_table(
                 [s.shape for s in ps.train_slots], self.wd, self.rmsprop_decay_skip)).to(dev)
-        self.muon_tab = self.muon_seg = self.muon_q = None
+        self.muon_tab = self.muon_seg = self.muon_q = self.muon_tiled_buf = None
         if self.muon:
             # one record per conv kernel (refused by name outside muon_covers), and per segment
             # whether it is one and its q = sqrt(max(1, K / R))
-            tab, seg, q = muon_tables(ps.train_slots)
+            tab, seg, q, *tiled = muon_tables(ps.train_slots, tiled=self.muon_tiled)
             assert MUON_DTYPE.itemsize == self.nat.muon_tensor_bytes()
             self.muon_shapes = ([int(r) for r in tab["R"]], [int(k) for k in tab["K"]])
             self.muon_tab = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+            # the tiled launches' tables, chunk partials and bf16 scratch: only with the flag
+            if tiled and len(tiled[0]["tab"]):
+                from ..ops.functional import muon_tiled_buffers
+
+                self.muon_tiled_buf = muon_tiled_buffers(tiled[0], dev)
             self.muon_seg, self.muon_q = torch.from_numpy(seg).to(dev), torch.from_numpy(q).to(dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:

@@ -246,26 +246,92 @@ def check_muon(momentum=0.95, nesterov=True, ns_steps=5, aux_lr_scale=1.0,
     return mu, bool(nesterov), steps, aux
 
 
-def muon_tables(train_slots):
+MUON_TILE = 64            # csrc/optim.h MUON_TILE
+MUON_TILED_SHORT, MUON_TILED_LONG = 1024, 8192   # csrc/muon_tiled.hip muon_tiled_covers
+MUON_TILED_DTYPE = np.dtype([   # csrc/optim.h MuonTiledTensor
+    ("offset", "<i8"), ("x_off", "<i8"), ("a_off", "<i8"), ("b_off", "<i8"), ("chunk0", "<i8"),
+    ("nchunks", "<i4"), ("seg", "<i4"), ("R", "<i4"), ("K", "<i4"), ("transpose", "<i4"),
+    ("SP", "<i4"), ("LP", "<i4"), ("pad", "<i4"),
+])
+MUON_WORK_DTYPE = np.dtype([("t", "<i4"), ("i", "<i4"), ("j", "<i4"), ("len", "<i4")])   # MuonWork
+
+
+def muon_tiled_covers(R: int, K: int) -> bool:
+    """Host mirror of csrc/muon_tiled.hip muon_tiled_covers."""
+    return 1 <= min(R, K) <= MUON_TILED_SHORT and max(R, K) <= MUON_TILED_LONG
+
+
+def muon_apply_bn(SP: int) -> int:
+    """Long-side columns of a muon_tiled_apply workgroup: its SP-row panel must fit LDS."""
+    return 64 if SP <= 512 else 32
+
+
+def muon_tiled_tables(recs):
+    """The tables of the tiled muon launches (csrc/muon_tiled.hip) for `recs`, a list of
+    (offset, segment, R, K).  Returns a dict: `tab` (MUON_TILED_DTYPE: per tensor its padded
+    sides, its X / A / B offsets into the bf16 scratch and its chunks), `blk` (int32: the tensor
+    of every moments workgroup), the work tables `stage` (every 64 x 64 tile of X; unstage
+    walks it too), `syrk_a` / `syrk_b` (the upper-triangle tiles of A and of B) and `apply` (the
+    column blocks), each MUON_WORK_DTYPE and sorted longest reduction first, `scratch`
+    (bf16 elements) and `max_sp`."""
+    T = MUON_TILE
+    tab = np.zeros(len(recs), dtype=MUON_TILED_DTYPE)
+    blk, work, elems = [], {"stage": [], "syrk_a": [], "syrk_b": [], "apply": []}, 0
+    for t, (off, seg, R, K) in enumerate(recs):
+        assert muon_tiled_covers(R, K), (R, K)
+        s, l = min(R, K), max(R, K)
+        SP, LP = _ceil(s, T) * T, _ceil(l, T) * T
+        n = _ceil(R * K, LARS_CHUNK)
+        tab[t] = (off, elems, elems + SP * LP, elems + SP * LP + SP * SP, len(blk), n, seg, R, K,
+                  int(K <= R), SP, LP, 0)
+        elems += SP * LP + 2 * SP * SP          # (all three multiples of 64 elements)
+        blk += [t] * n
+        work["stage"] += [(t, i, j, 0) for i in range(SP // T) for j in range(LP // T)]
+        tri = [(i, j) for i in range(SP // T) for j in range(i, SP // T)]
+        work["syrk_a"] += [(t, i, j, LP) for i, j in tri]
+        work["syrk_b"] += [(t, i, j, SP) for i, j in tri]
+        bn = muon_apply_bn(SP)
+        work["apply"] += [(t, i, bn, SP) for i in range(LP // bn)]
+    out = {"tab": tab, "blk": np.array(blk, dtype=np.int32), "scratch": elems,
+           "max_sp": int(tab["SP"].max()) if len(recs) else 0}
+    for name, w in work.items():
+        w.sort(key=lambda r: -r[3])             # stable: ties keep the tensor order
+        out[name] = np.array(w, dtype=MUON_WORK_DTYPE)
+    return out
+
+
+def muon_tables(train_slots, tiled=False):
     """The tables of the muon launches (csrc/muon.hip), from the trainable slots in segment
     order: the MuonTensor records (numpy, MUON_DTYPE; one per conv kernel, its HWIO master the
     row-major R x K matrix, R = kh kw C), muon_seg (int32 per segment, 1 = conv kernel) and
     q_seg (fp32 per segment: sqrt(max(1, K / R)) of a conv kernel, 0 elsewhere).  A conv
-    kernel outside muon_covers is refused by name."""
+    kernel outside muon_covers is refused by name -- or, with `tiled`, goes to the tiled
+    launches (csrc/muon_tiled.hip): then a fourth value, muon_tiled_tables' dict over those
+    kernels, is returned too, and only a kernel outside muon_tiled_covers is refused."""
     recs, seg, q = [], np.zeros(len(train_slots), np.int32), np.zeros(len(train_slots), np.float32)
+    big = []
     for i, s in enumerate(train_slots):
         if s.kind != "conv":
             continue
         K = int(s.shape[-1])
         R = int(s.numel) // K
-        if not muon_covers(R, K):
+        if muon_covers(R, K):
+            recs.append((int(s.offset), i, R, K, int(K <= R)))
+        elif not tiled:
             raise ValueError(f"optimizer muon: conv kernel {s.name} is the matrix {R} x {K}; one "
                              f"workgroup orthogonalises a short side <= {MUON_SHORT} and a long "
-                             f"side <= {MUON_LONG} (the CIFAR networks)")
-        recs.append((int(s.offset), i, R, K, int(K <= R)))
+                             f"side <= {MUON_LONG} (the CIFAR networks); muon_tiled takes larger "
+                             f"ones")
+        elif muon_tiled_covers(R, K):
+            big.append((int(s.offset), i, R, K))
+        else:
+            raise ValueError(f"optimizer muon: conv kernel {s.name} is the matrix {R} x {K}; the "
+                             f"tiled launches orthogonalise a short side <= {MUON_TILED_SHORT} "
+                             f"and a long side <= {MUON_TILED_LONG}")
         seg[i] = 1
         q[i] = np.sqrt(np.float32(max(1.0, K / R)))
-    return np.array(recs, dtype=MUON_DTYPE), seg, q
+    tab = np.array(recs, dtype=MUON_DTYPE)
+    return (tab, seg, q, muon_tiled_tables(big)) if tiled else (tab, seg, q)
 
 
 OPT_FUSED_RMSPROP_REASON = ("optimizer rmsprop: the one-launch optimizer is SGD-momentum; rmsprop "

@@ -689,6 +689,15 @@ class StepRecorder:
                                              e.muon_tab.data_ptr(), *e.muon_shapes,
                                              e.muon_momentum, int(e.muon_nesterov),
                                              e.muon_ns_steps, 1.0)
+                tiled = []
+                if e.muon_tiled_buf is not None:
+                    # the conv kernels one workgroup cannot hold (csrc/muon_tiled.hip): 3 + 3 *
+                    # steps grouped launches between the two, into the same direction buffer
+                    from ..ops.functional import muon_tiled_sequence
+
+                    tiled = muon_tiled_sequence(plan, e.muon_tiled_buf, grad, mom,
+                                                e.muon_dir.data_ptr(), e.muon_momentum,
+                                                e.muon_nesterov, e.muon_ns_steps, 1.0)
                 i1 = plan.muon_update_pack(master, grad, mom, e.muon_dir.data_ptr(),
                                            e.params.n_train, *e.sched.launch_args(),
                                            e.gstep.data_ptr(), e.momentum, e.wd,
@@ -699,6 +708,8 @@ class StepRecorder:
                     gb = {f"grad:{b}" for b in range(len(e.buckets))}
                     pb = {f"param:{b}" for b in range(len(e.buckets))}
                     out.op_buffers[i0] = gb | {"muon"}
+                    for i in tiled:
+                        out.op_buffers[i] = gb | {"muon"}
                     out.op_buffers[i1] = gb | pb | {"muon", "lr", "gstep"}
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so

@@ -18,8 +18,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --optimizer lion   Lion (sign of an interpolated momentum, one state buffer) in one device
                      launch: --lion_beta1/_beta2, --lion_decay_skip
   --optimizer muon   Muon: conv kernels move along their momentum orthogonalised by Newton-Schulz
-                     on the matrix cores (CIFAR networks): --muon_momentum, --muon_nesterov,
-                     --muon_ns_steps, --muon_aux_lr_scale
+                     on the matrix cores: --muon_momentum, --muon_nesterov, --muon_ns_steps,
+                     --muon_aux_lr_scale; --muon_tiled for the ImageNet networks
   --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
                      one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
                      --rmsprop_wd, --rmsprop_decay_skip
@@ -386,6 +386,11 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
     p.add_argument("--muon_aux_lr_scale", type=float, default=1.0,
                    help="muon: the rate of the tensors that are not conv kernels is lr times "
                         "this, > 0.")
+    p.add_bool("muon_tiled", False,
+               "muon: conv kernels past one workgroup's reach (a short side above 64 or a long "
+               "side above 576: every ImageNet network has them) take the tiled Newton-Schulz "
+               "launches, up to a short side of 1024 and a long side of 8192, instead of being "
+               "refused.  Accepted and unused with another optimizer.")
     p.add_argument("--adam_beta1", type=_adam_beta, default=0.9,
                    help="adamw: decay of the first moment, in [0, 1).")
     p.add_argument("--adam_beta2", type=_adam_beta, default=0.999,

@@ -8,6 +8,9 @@
 2. The whole step: engines of the same network in one process, timed interleaved, rounds x
    variants, best / median / max ms/step: mom (as tuned), mom_generic (DTR_TUNE=opt_fused=0:
    sgd_update_pack + ohwi_pack, the generic path muon takes) and muon.
+3. An ImageNet network (imagenet_resnet18:128, imagenet_resnet50:128) takes --muon_tiled: part 1
+   becomes each of csrc/muon_tiled.hip's five launches alone and the whole 3 + 3 * steps
+   sequence over the network's tiled conv kernels; part 2's muon variant is muon_tiled.
 Everything is printed as JSON lines.
 
     python scripts/muon_step_time.py [cifar_resnet50:128,cifar_resnet20:128] [steps] [rounds]
@@ -31,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adam_step_time as ast  # noqa: E402
 
 ast.VARIANTS["muon"] = ({"optimizer": "muon"}, "")
+ast.VARIANTS["muon_tiled"] = ({"optimizer": "muon", "muon_tiled": True}, "")
 
 
 def _batch(fn, reps):
@@ -99,18 +103,62 @@ def kernels_alone(model, reps=20):
     return out
 
 
+def tiled_alone(model, reps=10):
+    """us per launch of the five tiled launches and of the whole sequence (5 steps)."""
+    nat = dtr.native(required=True)
+    dev = torch.device("cuda", 0)
+    dataset, size = model.split("_resnet")
+    slots = ParamStore(build_spec(dataset, int(size))).train_slots
+    tt = muon_tables(slots, tiled=True)[3]
+    buf = F.muon_tiled_buffers(tt, dev)
+    n = int(slots[-1].offset + slots[-1].numel)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    g, m = (torch.randn(n, generator=gen, device=dev) for _ in range(2))
+    d = torch.zeros(n, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+
+    class One:   # the sequence with every launch but `name` (and `epi`) left out
+        def __init__(self, name, epi=None):
+            self.name, self.epi = name, epi
+
+        def __getattr__(self, op):
+            def call(*a):
+                if op == self.name and (self.epi is None or a[4] == self.epi):
+                    getattr(nat, op)(*a)
+            return call
+
+    def seq(api, steps):
+        return lambda: F.muon_tiled_sequence(api, buf, g.data_ptr(), m.data_ptr(), d.data_ptr(),
+                                             0.5, True, steps, 1.0, tail=(st,))
+
+    seq(nat, 5)()   # (the scratch holds a real iterate before any launch is timed alone)
+    flop = sum(4.0 * int(r["SP"]) * int(r["SP"]) * int(r["LP"]) + 2.0 * int(r["SP"]) ** 3
+               for r in tt["tab"])
+    out = {"model": model, "tiled_kernels": len(tt["tab"]), "scratch_mb": tt["scratch"] * 2 / 2 ** 20,
+           "workgroups": {k: len(tt[k]) for k in ("blk", "stage", "syrk_a", "apply")},
+           "gflop_per_ns_step": round(flop / 1e9, 2)}
+    for name, api in (("moments", One("muon_tiled_moments")), ("stage", One("muon_tiled_stage")),
+                      ("syrk_a", One("muon_tiled_syrk", 0)), ("syrk_b", One("muon_tiled_syrk", 1)),
+                      ("apply", One("muon_tiled_apply")), ("unstage", One("muon_tiled_unstage"))):
+        out[name] = _batch(seq(api, 1), reps)
+    out["sequence_5_steps"] = _batch(seq(nat, 5), reps)
+    assert bool(torch.isfinite(d).all())
+    return out
+
+
 def main():
     cases = (sys.argv[1] if len(sys.argv) > 1 else
              "cifar_resnet50:128,cifar_resnet20:128").split(",")
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-    variants = ("mom", "mom_generic", "muon")
     for model in dict.fromkeys(c.split(":")[0] for c in cases):
-        print(json.dumps({"kernels_alone": kernels_alone(model)}), flush=True)
+        alone = tiled_alone if model.startswith("imagenet") else kernels_alone
+        print(json.dumps({"kernels_alone": alone(model)}), flush=True)
     for case in cases:
         if steps <= 0:
             break
         model, N = case.split(":")
+        variants = ("mom", "mom_generic", "muon_tiled" if model.startswith("imagenet") else "muon")
         engs = {v: ast.build(model, int(N), v) for v in variants}
         res = {name: [] for name in engs}
         for _ in range(rounds):

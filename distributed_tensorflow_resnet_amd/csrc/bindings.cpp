@@ -1402,6 +1402,32 @@ static Launch mk_erase_boxes(ptr_t x, int N, int H, int W, int Cpad, int s2d,
   };
 }
 
+// RandAugment in front of the input launch (randaug.hip): img -> out, both uint8 [N][3][32][32]
+// or (hwc) [N][H][W][3]; op_ids is the host's list of allowed ops, packed into the kernel
+// arguments; log (0: none) gets [N][num_ops][2].  Checked here, when the op is made.
+static Launch mk_randaug(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
+                         unsigned long long seed, ptr_t gstep, int num_ops, ptr_t tables,
+                         int table_len, std::vector<int> op_ids, ptr_t log) {
+  if (op_ids.empty() || op_ids.size() > 16)
+    throw std::invalid_argument("randaug: the op table needs 1..16 entries");
+  RandAug ra;
+  ra.tables = P<const int>(tables);
+  ra.table_len = table_len;
+  for (size_t i = 0; i < op_ids.size(); ++i) {
+    if (op_ids[i] < 0 || op_ids[i] > 13)
+      throw std::invalid_argument("randaug: op ids must be in 0..13");
+    ra.op_nibbles |= (unsigned long long)op_ids[i] << (4 * i);
+  }
+  ra.op_len = (int)op_ids.size();
+  ra.num_ops = num_ops;
+  ra.log = P<int>(log);
+  randaug_check(P<const void>(img), P<const void>(out), N, H, W, hwc, ra);
+  return [=](hipStream_t s) {
+    randaug(P<const uint8_t>(img), P<uint8_t>(out), N, H, W, hwc, seed,
+            P<const long long>(gstep), ra, s);
+  };
+}
+
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
   return [=](hipStream_t s) { stem_s2d_pack(P<const float>(w7), P<bf16>(w4), K, s); };
 }
@@ -2006,6 +2032,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_mix);
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_cut);
   def_op(m, plan, "erase_boxes", mk_erase_boxes);
+  def_op(m, plan, "randaug", mk_randaug);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

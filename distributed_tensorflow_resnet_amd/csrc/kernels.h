@@ -530,6 +530,25 @@ void erase_boxes_check(const void* x, int N, int H, int W, int Cpad, int s2d, co
 void erase_boxes(bf16* x, int N, int H, int W, int Cpad, int s2d, unsigned long long seed,
                  const long long* gstep, const Erase& er, hipStream_t s);
 
+// ---- RandAugment (randaug.hip) ----
+// A chain of num_ops ops per image on the step's uint8 batch, drawn per image: data/randaug.py
+// randaug_batch(batch, layout, seed, step, ...) is the specification.  in / out: the uploaded
+// and the augmented batch buffer, planar [N][3][32][32] or (hwc) interleaved [N][H][W][3].
+struct RandAug {
+  const int* tables = nullptr;         // [table_len] int32 (randaug_tables)
+  int table_len = 0;
+  unsigned long long op_nibbles = 0;   // the allowed op ids 0..13, entry i in bits 4i..4i+3
+  int op_len = 0;                      // 1..16 entries
+  int num_ops = 0;                     // 1..3 ops per image
+  int* log = nullptr;                  // optional [N][num_ops][2] {op, sign}
+};
+// the argument checks of randaug (std::invalid_argument), for plan recording; for hwc it also
+// asks, once per process, for the kernel's more than 64 KB of LDS
+void randaug_check(const void* in, const void* out, int N, int H, int W, int hwc,
+                   const RandAug& ra);
+void randaug(const uint8_t* in, uint8_t* out, int N, int H, int W, int hwc,
+             unsigned long long seed, const long long* gstep, const RandAug& ra, hipStream_t s);
+
 // ---- flat-parameter descriptors ----
 struct ParamSeg {          // one trainable tensor inside the flat buffers
   long long offset;        // element offset into master/grad/mom (master layout = TF HWIO)

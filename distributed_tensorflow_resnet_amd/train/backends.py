@@ -19,6 +19,7 @@ import torch
 from ..data.cifar import (MIXUP_TABLE_LEN, augment_cpu, cutmix_draw, cutmix_table, cutmix_thresh,
                           erase_draw, erase_noise_index, erase_noise_table, erase_table,
                           erase_thresh, mixup_draw, mixup_table)
+from ..data.randaug import randaug_batch
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
 from ..models.spec import ModelSpec
@@ -28,7 +29,7 @@ from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_
                                 tf_to_rmsprop, tf_to_state)
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
-                     check_mixup_alpha, check_erase, check_muon, muon_tables)
+                     check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug)
 
 
 class GPUBackend:
@@ -142,6 +143,9 @@ class GPUBackend:
     def erase_state(self):
         return self.engine.erase_state()
 
+    def randaug_state(self):
+        return self.engine.randaug_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -170,7 +174,9 @@ class CPUBackend:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 randaug_num_ops: int = 0, randaug_magnitude: int = 9,
+                 randaug_ops: str = "all"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -203,6 +209,11 @@ class CPUBackend:
             self.erase_thresh = erase_thresh(self.erase_prob)
             if self.erase_fill == "noise":
                 self.erase_noise = erase_noise_table(data_seed)
+        # RandAugment, csrc/randaug.hip's ops on the uint8 batch before augment_cpu, from the
+        # same table and draw (0 = off)
+        self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids = check_randaug(
+            randaug_num_ops, randaug_magnitude, randaug_ops)
+        self._randaug_state = None
         # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self._clip_state = None
@@ -315,6 +326,11 @@ class CPUBackend:
 
     def set_batch(self, images, labels):
         if images.dtype == torch.uint8:
+            if self.randaug_num_ops > 0:   # on the stored records, at the step about to run
+                aug, self._randaug_state = randaug_batch(
+                    images.numpy(), "chw", self.data_seed, self.step_count,
+                    self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids)
+                images = torch.from_numpy(aug)
             images = augment_cpu(images, train=True, generator=self.gen)
         self._x = images.float()
         self._y = labels.long()
@@ -631,6 +647,10 @@ class CPUBackend:
         """As Engine.erase_state (None: erasing off, or no step yet)."""
         return self._erase_state
 
+    def randaug_state(self):
+        """As Engine.randaug_state (None: RandAugment off, or no batch yet)."""
+        return self._randaug_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -763,7 +783,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 randaug_num_ops: int = 0, randaug_magnitude: int = 9,
+                 randaug_ops: str = "all"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -780,6 +802,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)
+    erase.update(randaug_num_ops=randaug_num_ops, randaug_magnitude=randaug_magnitude,
+                 randaug_ops=randaug_ops)
     if device == "gpu":
         from .engine import Engine
 

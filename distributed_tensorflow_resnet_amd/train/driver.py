@@ -232,6 +232,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            erase_area_max=flags.erase_area_max,
                            erase_aspect_min=flags.erase_aspect_min,
                            erase_fill=flags.erase_fill,
+                           randaug_num_ops=flags.randaug_num_ops,
+                           randaug_magnitude=flags.randaug_magnitude,
+                           randaug_ops=flags.randaug_ops,
                            adam_beta1=flags.adam_beta1, adam_beta2=flags.adam_beta2,
                            adam_epsilon=flags.adam_epsilon, adam_decay=flags.adam_decay,
                            adam_decay_skip=flags.adam_decay_skip,

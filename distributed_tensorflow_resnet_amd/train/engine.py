@@ -43,6 +43,7 @@ from .. import native
 from ..data.cifar import (MIXUP_TABLE_LEN, cutmix_table, cutmix_thresh, erase_noise_table,
                           erase_table, erase_thresh, mixup_table,
                           resident_steps_per_epoch, upload_resident)
+from ..data.randaug import randaug_tables
 from ..models.params import ParamStore
 from ..models.spec import BNSpec, ConvSpec, ModelSpec
 from ..parallel.buckets import assign_buckets, schedule_buckets
@@ -52,6 +53,7 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob, check_erase,
+                     check_randaug,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
@@ -144,7 +146,9 @@ class Engine:
                  rmsprop_centered: bool = False, rmsprop_wd: str = "l2",
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
-                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False):
+                 muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 randaug_num_ops: int = 0, randaug_magnitude: int = 9,
+                 randaug_ops: str = "all"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -234,6 +238,12 @@ class Engine:
         (self.erase_prob, self.erase_area_min, self.erase_area_max, self.erase_aspect_min,
          self.erase_fill) = check_erase(erase_prob, erase_area_min, erase_area_max,
                                         erase_aspect_min, erase_fill, spec.dataset)
+        # RandAugment in a launch of its own IN FRONT of the input launch (csrc/randaug.hip;
+        # data/randaug.py): each uint8 image goes through randaug_num_ops drawn ops into a second
+        # batch buffer, which the unchanged input launch then reads.  0 = off: nothing allocated,
+        # no op recorded.  The eval plans never augment.
+        self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids = check_randaug(
+            randaug_num_ops, randaug_magnitude, randaug_ops)
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -298,6 +308,18 @@ class Engine:
             if input_mode.startswith("cifar") and (spec.image_h, spec.image_w) != (32, 32):
                 raise ValueError("erase_prob > 0: not with the generic-shape CIFAR augment "
                                  f"kernel ({spec.image_h}x{spec.image_w} images)")
+        if self.randaug_num_ops > 0:
+            if input_mode == "cifar_resident":
+                raise ValueError("randaug_num_ops > 0 is not for input_mode='cifar_resident': "
+                                 "the records are picked inside the resident input kernel, so "
+                                 "there is no uint8 batch buffer to augment")
+            if input_mode not in ("cifar_u8", "imagenet_u8"):
+                raise ValueError(f"randaug_num_ops > 0 needs a uint8 batch in front of an input "
+                                 f"launch (input_mode cifar_u8 or imagenet_u8), got "
+                                 f"input_mode={input_mode!r}")
+            if input_mode == "cifar_u8" and (spec.image_h, spec.image_w) != (32, 32):
+                raise ValueError("randaug_num_ops > 0: the CIFAR kernel is for 32x32 records, "
+                                 f"got {spec.image_h}x{spec.image_w}")
         # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
         # the device and the step's input launch picks its own records through the keyed
         # permutation of global_step (data/cifar.py resident_index; csrc/data.hip).  Uploaded
@@ -627,6 +649,16 @@ class Engine:
             if self.erase_fill == "noise":
                 self.erase_noise = torch.from_numpy(erase_noise_table(self.data_seed)).to(dev)
             self.erase_log = torch.zeros((N, 5), dtype=torch.int32, device=dev)
+        self.img_ra = self.randaug_tab = self.randaug_log = None
+        if self.randaug_num_ops > 0:
+            # the augmented batch the input launch reads, the parameter table (uploaded once)
+            # and the launch's per-image {op, sign} pairs: fixed pointers.  The allowed op ids
+            # travel in the launch's arguments
+            self.img_ra = torch.zeros_like(self.img_u8)
+            self.randaug_tab = torch.from_numpy(
+                randaug_tables(self.randaug_magnitude, H, W)).to(dev)
+            self.randaug_log = torch.zeros((N, self.randaug_num_ops, 2), dtype=torch.int32,
+                                           device=dev)
         st = spec.stem
         self.stem_out = torch.empty((N, st.ho, st.wo, st.cout), dtype=BF16, device=dev)
         if spec.maxpool:
@@ -894,6 +926,15 @@ class Engine:
             return None
         torch.cuda.synchronize(self.device)
         return self.erase_log.cpu().numpy()
+
+    def randaug_state(self):
+        """The last step's RandAugment draws (synchronises): int array [N, num_ops, 2] of
+        {op, sign} per batch position, data/randaug.py randaug_draw's.  None: RandAugment off,
+        or no step yet."""
+        if self.randaug_log is None or self._steps_run == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        return self.randaug_log.cpu().numpy()
 
     def mix_head_ptrs(self) -> tuple:
         """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""

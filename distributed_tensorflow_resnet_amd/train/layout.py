@@ -484,6 +484,28 @@ def check_erase(prob, area_min=0.02, area_max=1.0 / 3.0, aspect_min=0.3, fill="z
     return prob, area_min, area_max, aspect_min, fill
 
 
+def check_randaug(num_ops=0, magnitude=9, ops="all") -> tuple:
+    """--randaug_num_ops and its sub-flags as both backends take them -> (num_ops, magnitude,
+    op ids): num_ops an integer in 0..3 (0 = off), magnitude an integer bin in 0..30, ops
+    "all" or a comma list of op names (data/randaug.py RA_OPS; at most 16 entries, repeats
+    weigh an op) -> the tuple of allowed op ids."""
+    from ..data.randaug import RA_MAX_MAGNITUDE, RA_MAX_OPS, randaug_op_table
+
+    def whole(v, what, top):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= top:
+            raise ValueError(f"{what} must be an integer in 0..{top}, got {v!r}")
+        return int(v)
+
+    num_ops = whole(num_ops, "randaug_num_ops", RA_MAX_OPS)
+    magnitude = whole(magnitude, "randaug_magnitude", RA_MAX_MAGNITUDE)
+    if not isinstance(ops, str):
+        raise ValueError(f"randaug_ops must be 'all' or a comma list of op names, got {ops!r}")
+    ids = tuple(int(i) for i in randaug_op_table(ops))
+    if len(ids) > 16:
+        raise ValueError(f"randaug_ops takes at most 16 entries, got {len(ids)}")
+    return num_ops, magnitude, ids
+
+
 def check_clip_grad_norm(c, optimizer: str) -> float:
     """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
     the norm is measured, the scale is exactly 1); not together with lars, whose trust

@@ -774,8 +774,18 @@ class StepRecorder:
             () if e.mix_table is None else
             (e.mix_table.data_ptr(), e.mix_table.numel(), *labels, e.labels_b.data_ptr(),
              e.mix_lam.data_ptr(), e.mix_log.data_ptr(), *cut))
+        self._randaug_op = None
+        img = e.img_u8.data_ptr() if e.input_mode in ("cifar_u8", "imagenet_u8") else 0
+        if e.img_ra is not None:
+            # RandAugment: a launch of its own on the main stream, directly in front of the
+            # input launch, which reads the augmented uint8 batch instead of the uploaded one
+            self._randaug_op = plan.randaug(
+                img, e.img_ra.data_ptr(), e.N, H, W, int(e.input_mode == "imagenet_u8"),
+                e.data_seed, e.gstep.data_ptr(), e.randaug_num_ops, e.randaug_tab.data_ptr(),
+                e.randaug_tab.numel(), list(e.randaug_op_ids), e.randaug_log.data_ptr())
+            img = e.img_ra.data_ptr()
         if e.input_mode == "cifar_u8":
-            plan.cifar_augment(e.img_u8.data_ptr(), e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,
+            plan.cifar_augment(img, e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,
                                e.data_seed, e.gstep.data_ptr(), 1, 0, *zero,
                                *mix(e.labels.data_ptr()))
         elif e.input_mode == "cifar_resident":
@@ -787,7 +797,7 @@ class StepRecorder:
                 e.rank, e.world, 1, e.shuffle_seed & (2 ** 64 - 1), 4, e.data_seed, 1, 0, 0,
                 *zero, *mix())
         elif e.input_mode == "imagenet_u8":
-            plan.imagenet_u8_pack(e.img_u8.data_ptr(), e.x_in.data_ptr(), e.N, H, W,
+            plan.imagenet_u8_pack(img, e.x_in.data_ptr(), e.N, H, W,
                                   e.data_seed, e.gstep.data_ptr(), 1, *zero, int(e.stem_s2d),
                                   *mix(e.labels.data_ptr()))
         elif zero[0]:
@@ -1027,6 +1037,8 @@ class StepRecorder:
             early = self._emit_persist_overlap(args)
             if self._erase_op is not None and out.op_buffers:
                 out.op_buffers[self._erase_op] = {"input"}   # the overlap plan declares its ops
+            if self._randaug_op is not None and out.op_buffers:
+                out.op_buffers[self._randaug_op] = {"input"}
             out.seg["bwd"] = (b1, plan.size())
             if e.opt_fused:   # the rest: the last bucket's segments
                 self._emit_optimizer(fused_slabs={}, gin=self._packed_gin(),

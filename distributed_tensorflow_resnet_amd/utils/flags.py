@@ -23,6 +23,8 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
                      one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
                      --rmsprop_wd, --rmsprop_decay_skip
+  --randaug_num_ops  RandAugment on the stored uint8 image, in front of the input launch:
+                     --randaug_magnitude (bin 0..30), --randaug_ops (all | a comma list of ops)
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -280,6 +282,20 @@ class FlagParser(argparse.ArgumentParser):
             if ns.erase_prob > 0 and getattr(ns, "synthetic", False):
                 self.error("--erase_prob cannot be combined with --synthetic: the synthetic "
                            "input has no input launch to erase behind")
+        if hasattr(ns, "randaug_num_ops"):
+            from ..train.layout import check_randaug
+
+            try:   # the sub-flags are checked, and otherwise unused, at --randaug_num_ops 0
+                check_randaug(ns.randaug_num_ops, ns.randaug_magnitude, ns.randaug_ops)
+            except ValueError as e:
+                self.error("--randaug_num_ops: " + str(e))
+            if ns.randaug_num_ops > 0 and getattr(ns, "synthetic", False):
+                self.error("--randaug_num_ops cannot be combined with --synthetic: the "
+                           "synthetic input has no input launch to augment in front of")
+            if ns.randaug_num_ops > 0 and getattr(ns, "resident_data", False):
+                self.error("--randaug_num_ops cannot be combined with --resident_data: the "
+                           "resident input kernel picks its records itself, so there is no "
+                           "uint8 batch to augment")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -500,6 +516,20 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="--erase_prob: 'zero' = the mean pixel of the standardised input, "
                         "'noise' = unit normal values from a host-made table (CIFAR only: an "
                         "error with ImageNet, whose inputs are not scaled).")
+    p.add_argument("--randaug_num_ops", type=int, default=0,
+                   help="RandAugment (Cubuk et al. 2020) on the device: each stored uint8 "
+                        "training image goes through this many (0..3) randomly drawn ops of "
+                        "torchvision's 14, in a launch of its own in front of the input launch "
+                        "(so before crop / flip / standardise, mixup / CutMix and erasing).  The "
+                        "draw is per image, a function of the seed, global_step and the batch "
+                        "position.  0 = off.  Evaluation never augments.  Not with --synthetic "
+                        "or --resident_data.")
+    p.add_argument("--randaug_magnitude", type=int, default=9,
+                   help="--randaug_num_ops: the magnitude bin 0..30 of every op (31 bins).")
+    p.add_argument("--randaug_ops", default="all",
+                   help="--randaug_num_ops: 'all' or a comma list (at most 16, repeats weigh) of "
+                        "Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, "
+                        "Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize.")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

@@ -35,8 +35,10 @@ COMMON_FLAGS = [
 
 # per-file extra flags (e.g. ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] keeps a
 # one-wave-per-SIMD kernel's MFMA accumulators in arch VGPRs, profiles/imagenet_wide.md).
-# muon.hip, randaug.hip: no packed fp32 arithmetic (v_pk_*_f32) in their element-wise passes
+# muon.hip, randaug.hip, augmix.hip: no packed fp32 arithmetic (v_pk_*_f32) in their
+# element-wise passes
 FILE_FLAGS: dict = {
+    "augmix.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "muon_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "randaug.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],

@@ -1428,6 +1428,41 @@ static Launch mk_randaug(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
   };
 }
 
+// AugMix in front of the input launch (augmix.hip): img -> out as randaug's; mix is the host's
+// [mix_ints / (width + 1)][width + 1] int32 table of Q8 weights and the Q16 blend factor; acc
+// (0 at width 1 or for the planar kernel) the uint16 workspace [N][3 H W]; log (0: none) gets
+// [N][width][4][2].  Checked here, when the op is made.
+static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
+                        unsigned long long seed, ptr_t gstep, int width, int depth,
+                        ptr_t tables, int table_len, ptr_t mix, int mix_ints,
+                        std::vector<int> op_ids, ptr_t acc, ptr_t log) {
+  if (op_ids.empty() || op_ids.size() > 16)
+    throw std::invalid_argument("augmix: the op table needs 1..16 entries");
+  if (width < 1 || width > 4) throw std::invalid_argument("augmix: width must be in 1..4");
+  if (mix_ints < 1 || mix_ints % (width + 1))
+    throw std::invalid_argument("augmix: the mixing table holds width + 1 int32 per entry");
+  AugMix am;
+  am.tables = P<const int>(tables);
+  am.table_len = table_len;
+  am.mix = P<const int>(mix);
+  am.mix_len = mix_ints / (width + 1);
+  for (size_t i = 0; i < op_ids.size(); ++i) {
+    if (op_ids[i] < 0 || op_ids[i] > 13)
+      throw std::invalid_argument("augmix: op ids must be in 0..13");
+    am.op_nibbles |= (unsigned long long)op_ids[i] << (4 * i);
+  }
+  am.op_len = (int)op_ids.size();
+  am.width = width;
+  am.depth = depth;
+  am.acc = P<unsigned short>(acc);
+  am.log = P<int>(log);
+  augmix_check(P<const void>(img), P<const void>(out), N, H, W, hwc, am);
+  return [=](hipStream_t s) {
+    augmix(P<const uint8_t>(img), P<uint8_t>(out), N, H, W, hwc, seed,
+           P<const long long>(gstep), am, s);
+  };
+}
+
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
   return [=](hipStream_t s) { stem_s2d_pack(P<const float>(w7), P<bf16>(w4), K, s); };
 }
@@ -2033,6 +2068,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_cut);
   def_op(m, plan, "erase_boxes", mk_erase_boxes);
   def_op(m, plan, "randaug", mk_randaug);
+  def_op(m, plan, "augmix", mk_augmix);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

@@ -549,6 +549,30 @@ void randaug_check(const void* in, const void* out, int N, int H, int W, int hwc
 void randaug(const uint8_t* in, uint8_t* out, int N, int H, int W, int hwc,
              unsigned long long seed, const long long* gstep, const RandAug& ra, hipStream_t s);
 
+// ---- AugMix (augmix.hip) ----
+// `width` chains of RandAugment's ops per image, each from the original, mixed with Q8 weights
+// and blended back into the original with a Q16 factor: data/augmix.py augmix_batch(batch,
+// layout, seed, step, ...) is the specification.  in / out as RandAug's.
+struct AugMix {
+  const int* tables = nullptr;         // [table_len] int32 (randaug_tables of bin 3 * severity)
+  int table_len = 0;
+  const int* mix = nullptr;            // [mix_len][width + 1] int32 {w_0..w_{width-1} Q8, m Q16}
+  int mix_len = 0;                     // entries (augmix_tables)
+  unsigned long long op_nibbles = 0;   // the allowed op ids 0..13, entry i in bits 4i..4i+3
+  int op_len = 0;                      // 1..16 entries
+  int width = 0;                       // 1..4 chains
+  int depth = -1;                      // 1..3 ops per chain, -1: drawn per chain
+  unsigned short* acc = nullptr;       // hwc, width > 1: the Q8 accumulator [N][3 H W]
+  int* log = nullptr;                  // optional [N][width][4][2]: {depth, table index}, then
+                                       // {op, sign} per slot (-1, -1 for a slot not run)
+};
+// the argument checks of augmix (std::invalid_argument), for plan recording; for hwc it also
+// asks, once per process, for the kernel's more than 64 KB of LDS
+void augmix_check(const void* in, const void* out, int N, int H, int W, int hwc,
+                  const AugMix& am);
+void augmix(const uint8_t* in, uint8_t* out, int N, int H, int W, int hwc,
+            unsigned long long seed, const long long* gstep, const AugMix& am, hipStream_t s);
+
 // ---- flat-parameter descriptors ----
 struct ParamSeg {          // one trainable tensor inside the flat buffers
   long long offset;        // element offset into master/grad/mom (master layout = TF HWIO)

@@ -19,6 +19,7 @@ import torch
 from ..data.cifar import (MIXUP_TABLE_LEN, augment_cpu, cutmix_draw, cutmix_table, cutmix_thresh,
                           erase_draw, erase_noise_index, erase_noise_table, erase_table,
                           erase_thresh, mixup_draw, mixup_table)
+from ..data.augmix import augmix_batch, augmix_tables
 from ..data.randaug import randaug_batch
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
@@ -29,7 +30,8 @@ from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_
                                 tf_to_rmsprop, tf_to_state)
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
-                     check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug)
+                     check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug,
+                     check_augmix)
 
 
 class GPUBackend:
@@ -146,6 +148,9 @@ class GPUBackend:
     def randaug_state(self):
         return self.engine.randaug_state()
 
+    def augmix_state(self):
+        return self.engine.augmix_state()
+
     def broadcast_parameters(self, src: int = 0):
         self.engine.broadcast_parameters(src)
         self._host_step = int(self.engine.gstep.item())
@@ -176,7 +181,9 @@ class CPUBackend:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
-                 randaug_ops: str = "all"):
+                 randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
+                 augmix_severity: int = 3, augmix_alpha: float = 1.0,
+                 augmix_ops: str = "augmix"):
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -214,6 +221,19 @@ class CPUBackend:
         self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids = check_randaug(
             randaug_num_ops, randaug_magnitude, randaug_ops)
         self._randaug_state = None
+        # AugMix in RandAugment's place, csrc/augmix.hip's chains and mix from the same tables
+        # and draw (0 = off)
+        (self.augmix_width, self.augmix_depth, self.augmix_severity, self.augmix_alpha,
+         self.augmix_op_ids) = check_augmix(augmix_width, augmix_depth, augmix_severity,
+                                            augmix_alpha, augmix_ops, self.randaug_num_ops)
+        if self.augmix_width > 0 and not spec.dataset.startswith("cifar"):
+            # set_batch augments planar CIFAR records only; the ImageNet crops reach this
+            # backend already decoded and scaled
+            raise ValueError("augmix_width > 0 on the CPU backend is for the CIFAR records, got "
+                             f"dataset {spec.dataset!r}")
+        self.augmix_mix = (augmix_tables(self.augmix_width, self.augmix_alpha, data_seed)
+                           if self.augmix_width > 0 else None)
+        self._augmix_state = None
         # global gradient-norm clipping, csrc/clip.hip's expressions in fp32 torch (0 = off)
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self._clip_state = None
@@ -330,6 +350,12 @@ class CPUBackend:
                 aug, self._randaug_state = randaug_batch(
                     images.numpy(), "chw", self.data_seed, self.step_count,
                     self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids)
+                images = torch.from_numpy(aug)
+            if self.augmix_width > 0:
+                aug, self._augmix_state = augmix_batch(
+                    images.numpy(), "chw", self.data_seed, self.step_count, self.augmix_width,
+                    self.augmix_depth, self.augmix_severity, self.augmix_op_ids,
+                    mix_table=self.augmix_mix)
                 images = torch.from_numpy(aug)
             images = augment_cpu(images, train=True, generator=self.gen)
         self._x = images.float()
@@ -651,6 +677,10 @@ class CPUBackend:
         """As Engine.randaug_state (None: RandAugment off, or no batch yet)."""
         return self._randaug_state
 
+    def augmix_state(self):
+        """As Engine.augmix_state (None: AugMix off, or no batch yet)."""
+        return self._augmix_state
+
     def _lars_trust(self, master, g):
         """The per-element trust ratio of the LARS update (csrc/lars.hip, in fp32 torch):
         per tensor eeta * |w| / (|g| + wd * |w| + epsilon) from the all-reduced gradient
@@ -706,6 +736,8 @@ class CPUBackend:
             m["erase_count"] = int(box[:, 0].sum())
             m["erase_area"] = float((box[:, 3] * box[:, 4]).sum() /
                                     (self.N * self.spec.image_h * self.spec.image_w))
+        if self.augmix_width > 0:
+            m["augmix"] = f"w{self.augmix_width}-s{self.augmix_severity}"
         return m
 
     def synchronize(self):
@@ -785,7 +817,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
-                 randaug_ops: str = "all"):
+                 randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
+                 augmix_severity: int = 3, augmix_alpha: float = 1.0,
+                 augmix_ops: str = "augmix"):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -804,6 +838,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  erase_fill=erase_fill)
     erase.update(randaug_num_ops=randaug_num_ops, randaug_magnitude=randaug_magnitude,
                  randaug_ops=randaug_ops)
+    erase.update(augmix_width=augmix_width, augmix_depth=augmix_depth,
+                 augmix_severity=augmix_severity, augmix_alpha=augmix_alpha,
+                 augmix_ops=augmix_ops)
     if device == "gpu":
         from .engine import Engine
 

@@ -235,6 +235,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            randaug_num_ops=flags.randaug_num_ops,
                            randaug_magnitude=flags.randaug_magnitude,
                            randaug_ops=flags.randaug_ops,
+                           augmix_width=flags.augmix_width, augmix_depth=flags.augmix_depth,
+                           augmix_severity=flags.augmix_severity,
+                           augmix_alpha=flags.augmix_alpha, augmix_ops=flags.augmix_ops,
                            adam_beta1=flags.adam_beta1, adam_beta2=flags.adam_beta2,
                            adam_epsilon=flags.adam_epsilon, adam_decay=flags.adam_decay,
                            adam_decay_skip=flags.adam_decay_skip,

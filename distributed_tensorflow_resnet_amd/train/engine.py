@@ -43,6 +43,7 @@ from .. import native
 from ..data.cifar import (MIXUP_TABLE_LEN, cutmix_table, cutmix_thresh, erase_noise_table,
                           erase_table, erase_thresh, mixup_table,
                           resident_steps_per_epoch, upload_resident)
+from ..data.augmix import augmix_tables
 from ..data.randaug import randaug_tables
 from ..models.params import ParamStore
 from ..models.spec import BNSpec, ConvSpec, ModelSpec
@@ -53,7 +54,7 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob, check_erase,
-                     check_randaug,
+                     check_randaug, check_augmix,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
@@ -148,7 +149,9 @@ class Engine:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
-                 randaug_ops: str = "all"):
+                 randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
+                 augmix_severity: int = 3, augmix_alpha: float = 1.0,
+                 augmix_ops: str = "augmix"):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -244,6 +247,12 @@ class Engine:
         # no op recorded.  The eval plans never augment.
         self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids = check_randaug(
             randaug_num_ops, randaug_magnitude, randaug_ops)
+        # AugMix in RandAugment's place (csrc/augmix.hip; data/augmix.py): augmix_width chains of
+        # those ops per image, each from the original, mixed and blended back into the original,
+        # into the second batch buffer.  0 = off: nothing allocated, no op recorded.
+        (self.augmix_width, self.augmix_depth, self.augmix_severity, self.augmix_alpha,
+         self.augmix_op_ids) = check_augmix(augmix_width, augmix_depth, augmix_severity,
+                                            augmix_alpha, augmix_ops, self.randaug_num_ops)
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -319,6 +328,18 @@ class Engine:
                                  f"input_mode={input_mode!r}")
             if input_mode == "cifar_u8" and (spec.image_h, spec.image_w) != (32, 32):
                 raise ValueError("randaug_num_ops > 0: the CIFAR kernel is for 32x32 records, "
+                                 f"got {spec.image_h}x{spec.image_w}")
+        if self.augmix_width > 0:
+            if input_mode == "cifar_resident":
+                raise ValueError("augmix_width > 0 is not for input_mode='cifar_resident': "
+                                 "the records are picked inside the resident input kernel, so "
+                                 "there is no uint8 batch buffer to augment")
+            if input_mode not in ("cifar_u8", "imagenet_u8"):
+                raise ValueError(f"augmix_width > 0 needs a uint8 batch in front of an input "
+                                 f"launch (input_mode cifar_u8 or imagenet_u8), got "
+                                 f"input_mode={input_mode!r}")
+            if input_mode == "cifar_u8" and (spec.image_h, spec.image_w) != (32, 32):
+                raise ValueError("augmix_width > 0: the CIFAR kernel is for 32x32 records, "
                                  f"got {spec.image_h}x{spec.image_w}")
         # input_mode "cifar_resident": the whole split (uint8 [M,3,32,32] + labels) lives on
         # the device and the step's input launch picks its own records through the keyed
@@ -659,6 +680,21 @@ class Engine:
                 randaug_tables(self.randaug_magnitude, H, W)).to(dev)
             self.randaug_log = torch.zeros((N, self.randaug_num_ops, 2), dtype=torch.int32,
                                            device=dev)
+        self.img_am = self.augmix_tab = self.augmix_mix = self.augmix_acc = self.augmix_log = None
+        if self.augmix_width > 0:
+            # the augmented batch the input launch reads, the ops' parameter table and the
+            # {weights, blend factor} table (uploaded once), the launch's per-image log and,
+            # for the interleaved ImageNet crops with more than one chain, the uint16 Q8
+            # accumulator of one batch: fixed pointers
+            self.img_am = torch.zeros_like(self.img_u8)
+            self.augmix_tab = torch.from_numpy(
+                randaug_tables(3 * self.augmix_severity, H, W)).to(dev)
+            self.augmix_mix = torch.from_numpy(
+                augmix_tables(self.augmix_width, self.augmix_alpha, self.data_seed)).to(dev)
+            self.augmix_log = torch.zeros((N, self.augmix_width, 4, 2), dtype=torch.int32,
+                                          device=dev)
+            if self.input_mode == "imagenet_u8" and self.augmix_width > 1:
+                self.augmix_acc = torch.zeros((N, 3 * H * W), dtype=torch.int16, device=dev)
         st = spec.stem
         self.stem_out = torch.empty((N, st.ho, st.wo, st.cout), dtype=BF16, device=dev)
         if spec.maxpool:
@@ -936,6 +972,15 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return self.randaug_log.cpu().numpy()
 
+    def augmix_state(self):
+        """The last step's AugMix draws (synchronises): int array [N, width, 4, 2], per chain
+        {depth, table index} and then {op, sign} per slot ((-1, -1): not run), data/augmix.py
+        augmix_log(augmix_draw(...)).  None: AugMix off, or no step yet."""
+        if self.augmix_log is None or self._steps_run == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        return self.augmix_log.cpu().numpy()
+
     def mix_head_ptrs(self) -> tuple:
         """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""
         return () if self.labels_b is None else (self.labels_b.data_ptr(), self.mix_lam.data_ptr())
@@ -1193,7 +1238,8 @@ class Engine:
         keys are the ones callers that store every scalar have always got.  With clipping
         on, `grad_norm` and `clip_scale` of the last step are added (clip_state()); with mixup
         on, `mixup_lam` (mixup_state()); with mixup or CutMix on, also `mix_mode` (0 mixup,
-        1 CutMix) and, for a CutMix step, `cutmix_area` (mix_state())."""
+        1 CutMix) and, for a CutMix step, `cutmix_area` (mix_state()); with AugMix on,
+        `augmix` ("w<width>-s<severity>")."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
@@ -1233,6 +1279,8 @@ class Engine:
             m["erase_count"] = int(box[:, 0].sum())
             m["erase_area"] = float((box[:, 3] * box[:, 4]).sum() /
                                     (self.N * self.spec.image_h * self.spec.image_w))
+        if self.augmix_width > 0:
+            m["augmix"] = f"w{self.augmix_width}-s{self.augmix_severity}"
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -506,6 +506,40 @@ def check_randaug(num_ops=0, magnitude=9, ops="all") -> tuple:
     return num_ops, magnitude, ids
 
 
+def check_augmix(width=0, depth=-1, severity=3, alpha=1.0, ops="augmix",
+                 randaug_num_ops=0) -> tuple:
+    """--augmix_width and its sub-flags as both backends take them -> (width, depth, severity,
+    alpha, op ids): width an integer in 0..4 (0 = off), depth -1 (drawn per chain) or 1..3,
+    severity an integer in 0..10 (bin 3 * severity of randaug_tables), alpha finite and > 0,
+    ops "augmix" (the paper's nine), "all" or a comma list of op names (at most 16 entries).
+    Not together with RandAugment: one policy at a time."""
+    from ..data.augmix import AM_MAX_DEPTH, AM_MAX_SEVERITY, AM_MAX_WIDTH, augmix_op_table
+
+    def whole(v, what, lo, top):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= top:
+            raise ValueError(f"{what} must be an integer in {lo}..{top}, got {v!r}")
+        return int(v)
+
+    width = whole(width, "augmix_width", 0, AM_MAX_WIDTH)
+    depth = whole(depth, "augmix_depth", -1, AM_MAX_DEPTH)
+    if depth == 0:
+        raise ValueError("augmix_depth must be -1 (drawn per chain) or in 1..3, got 0")
+    severity = whole(severity, "augmix_severity", 0, AM_MAX_SEVERITY)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.number)) or \
+            not (alpha > 0 and np.isfinite(alpha)):
+        raise ValueError(f"augmix_alpha must be finite and > 0, got {alpha!r}")
+    if not isinstance(ops, str):
+        raise ValueError(f"augmix_ops must be 'augmix', 'all' or a comma list of op names, "
+                         f"got {ops!r}")
+    ids = tuple(int(i) for i in augmix_op_table(ops))
+    if len(ids) > 16:
+        raise ValueError(f"augmix_ops takes at most 16 entries, got {len(ids)}")
+    if width > 0 and randaug_num_ops > 0:
+        raise ValueError("augmix_width > 0 cannot be combined with randaug_num_ops > 0: one "
+                         "augmentation policy at a time")
+    return width, depth, severity, float(alpha), ids
+
+
 def check_clip_grad_norm(c, optimizer: str) -> float:
     """--clip_grad_norm as both backends take it: 0 = off, a positive number or inf (inf:
     the norm is measured, the scale is exactly 1); not together with lars, whose trust

@@ -774,16 +774,25 @@ class StepRecorder:
             () if e.mix_table is None else
             (e.mix_table.data_ptr(), e.mix_table.numel(), *labels, e.labels_b.data_ptr(),
              e.mix_lam.data_ptr(), e.mix_log.data_ptr(), *cut))
-        self._randaug_op = None
+        self._preaug_op = None
         img = e.img_u8.data_ptr() if e.input_mode in ("cifar_u8", "imagenet_u8") else 0
         if e.img_ra is not None:
             # RandAugment: a launch of its own on the main stream, directly in front of the
             # input launch, which reads the augmented uint8 batch instead of the uploaded one
-            self._randaug_op = plan.randaug(
+            self._preaug_op = plan.randaug(
                 img, e.img_ra.data_ptr(), e.N, H, W, int(e.input_mode == "imagenet_u8"),
                 e.data_seed, e.gstep.data_ptr(), e.randaug_num_ops, e.randaug_tab.data_ptr(),
                 e.randaug_tab.numel(), list(e.randaug_op_ids), e.randaug_log.data_ptr())
             img = e.img_ra.data_ptr()
+        if e.img_am is not None:
+            # AugMix, in RandAugment's place (never both): same stream, same buffer declaration
+            self._preaug_op = plan.augmix(
+                img, e.img_am.data_ptr(), e.N, H, W, int(e.input_mode == "imagenet_u8"),
+                e.data_seed, e.gstep.data_ptr(), e.augmix_width, e.augmix_depth,
+                e.augmix_tab.data_ptr(), e.augmix_tab.numel(), e.augmix_mix.data_ptr(),
+                e.augmix_mix.numel(), list(e.augmix_op_ids),
+                0 if e.augmix_acc is None else e.augmix_acc.data_ptr(), e.augmix_log.data_ptr())
+            img = e.img_am.data_ptr()
         if e.input_mode == "cifar_u8":
             plan.cifar_augment(img, e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,
                                e.data_seed, e.gstep.data_ptr(), 1, 0, *zero,
@@ -1037,8 +1046,8 @@ class StepRecorder:
             early = self._emit_persist_overlap(args)
             if self._erase_op is not None and out.op_buffers:
                 out.op_buffers[self._erase_op] = {"input"}   # the overlap plan declares its ops
-            if self._randaug_op is not None and out.op_buffers:
-                out.op_buffers[self._randaug_op] = {"input"}
+            if self._preaug_op is not None and out.op_buffers:
+                out.op_buffers[self._preaug_op] = {"input"}
             out.seg["bwd"] = (b1, plan.size())
             if e.opt_fused:   # the rest: the last bucket's segments
                 self._emit_optimizer(fused_slabs={}, gin=self._packed_gin(),

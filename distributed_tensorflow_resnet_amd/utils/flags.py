@@ -25,6 +25,9 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
                      --rmsprop_wd, --rmsprop_decay_skip
   --randaug_num_ops  RandAugment on the stored uint8 image, in front of the input launch:
                      --randaug_magnitude (bin 0..30), --randaug_ops (all | a comma list of ops)
+  --augmix_width     AugMix: that many chains of those ops per image, mixed and blended back
+                     into the original, in RandAugment's place: --augmix_depth, --augmix_severity,
+                     --augmix_alpha, --augmix_ops (augmix | all | a comma list of ops)
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -296,6 +299,21 @@ class FlagParser(argparse.ArgumentParser):
                 self.error("--randaug_num_ops cannot be combined with --resident_data: the "
                            "resident input kernel picks its records itself, so there is no "
                            "uint8 batch to augment")
+        if hasattr(ns, "augmix_width"):
+            from ..train.layout import check_augmix
+
+            try:   # the sub-flags are checked, and otherwise unused, at --augmix_width 0
+                check_augmix(ns.augmix_width, ns.augmix_depth, ns.augmix_severity,
+                             ns.augmix_alpha, ns.augmix_ops, getattr(ns, "randaug_num_ops", 0))
+            except ValueError as e:
+                self.error("--augmix_width: " + str(e))
+            if ns.augmix_width > 0 and getattr(ns, "synthetic", False):
+                self.error("--augmix_width cannot be combined with --synthetic: the synthetic "
+                           "input has no input launch to augment in front of")
+            if ns.augmix_width > 0 and getattr(ns, "resident_data", False):
+                self.error("--augmix_width cannot be combined with --resident_data: the "
+                           "resident input kernel picks its records itself, so there is no "
+                           "uint8 batch to augment")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -530,6 +548,29 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="--randaug_num_ops: 'all' or a comma list (at most 16, repeats weigh) of "
                         "Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, "
                         "Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize.")
+    p.add_argument("--augmix_width", type=int, default=0,
+                   help="AugMix (Hendrycks et al. 2020) on the device: each stored uint8 training "
+                        "image goes through this many (0..4) independent chains of RandAugment's "
+                        "integer ops, all starting from the original; their results are mixed "
+                        "with Dirichlet weights and the mix is blended back into the original "
+                        "with a Beta factor, in a launch of its own in front of the input launch "
+                        "(so before crop / flip / standardise, mixup / CutMix and erasing).  The "
+                        "draw is per image, a function of the seed, global_step and the batch "
+                        "position.  0 = off.  Evaluation never augments.  Not with "
+                        "--randaug_num_ops, --synthetic or --resident_data.  No Jensen-Shannon "
+                        "loss.")
+    p.add_argument("--augmix_depth", type=int, default=-1,
+                   help="--augmix_width: ops per chain, 1..3; -1 draws 1..3 per chain.")
+    p.add_argument("--augmix_severity", type=int, default=3,
+                   help="--augmix_width: 0..10; every op takes magnitude bin 3 * severity of "
+                        "RandAugment's 31.")
+    p.add_argument("--augmix_alpha", type=float, default=1.0,
+                   help="--augmix_width: the parameter (> 0) of the Dirichlet weights and of the "
+                        "Beta blend factor, sampled on the host into a 4096-entry table.")
+    p.add_argument("--augmix_ops", default="augmix",
+                   help="--augmix_width: 'augmix' (the paper's nine: AutoContrast, Equalize, "
+                        "Posterize, Rotate, Solarize, ShearX, ShearY, TranslateX, TranslateY), "
+                        "'all' (RandAugment's 14) or a comma list (at most 16, repeats weigh).")
     p.add_bool("ema_warmup", True,
                "EMA decay min(decay, (1 + step) / (10 + step)), as TF's num_updates=global_step: "
                "the average forgets the initial weights quickly.")

@@ -431,18 +431,41 @@ static void check_mix_ptrs(const char* op, ptr_t labels_b, ptr_t mix_lam) {
     throw std::invalid_argument(std::string(op) + ": labels_b and mix_lam go together");
 }
 
-static Launch mk_softmax_xent_mix(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
-                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam) {
+// Distillation (xent_row.h): three more trailing arguments, teacher ([N][ld] fp32 teacher
+// logits, null: none), kd_alpha in [0, 1] and kd_inv_tau = 1 / temperature > 0; a fourth
+// arity of the same ops.  Without a teacher kd_alpha must be 0 and the rows are the old ones.
+static KdArgs mk_kd(const char* op, ptr_t teacher, float kd_alpha, float kd_inv_tau) {
+  KdArgs kd;
+  kd.teacher = P<const float>(teacher);
+  kd.alpha = kd_alpha;
+  kd.inv_tau = kd_inv_tau;
+  check_kd(op, kd);
+  return kd;
+}
+
+static Launch mk_softmax_xent_kd(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                                 ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                                 float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                                 int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
+                                 ptr_t teacher, float kd_alpha, float kd_inv_tau) {
   check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
   check_mix_ptrs("softmax_xent", labels_b, mix_lam);
+  const KdArgs kd = mk_kd("softmax_xent", teacher, kd_alpha, kd_inv_tau);
   return [=](hipStream_t s) {
     softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
                  P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
                  P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s,
-                 P<const int>(labels_b), P<const float>(mix_lam));
+                 P<const int>(labels_b), P<const float>(mix_lam), kd);
   };
+}
+
+static Launch mk_softmax_xent_mix(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam) {
+  return mk_softmax_xent_kd(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
+                            grad_scale, probs, ws, label_smoothing, topk, topk_out, labels_b,
+                            mix_lam, 0, 0.f, 1.f);
 }
 
 static Launch mk_softmax_xent_ls(ptr_t logits, int ld, ptr_t labels, int N, int classes,
@@ -475,13 +498,16 @@ static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t
 
 // head_fused(x, bn=[acc, gamma, beta, mmean, mvar, mean, rstd, scale, shift], momentum, eps,
 //            update_moving, w_hwio, bias, labels, shape=[N, HW, C, classes, kpad], grad_scale,
-//            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk[, labels_b, mix_lam]])
-static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam) {
+//            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk[, labels_b, mix_lam
+//            [, teacher, kd_alpha, kd_inv_tau]]])
+static Launch mk_head_fused_kd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                               float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
+                               ptr_t teacher, float kd_alpha, float kd_inv_tau) {
   check_xent_opts("head_fused", label_smoothing, topk, 0);
   check_mix_ptrs("head_fused", labels_b, mix_lam);
+  const KdArgs kd = mk_kd("head_fused", teacher, kd_alpha, kd_inv_tau);
   if (bn.size() != 9 || shape.size() != 5 || out.size() != 5)
     throw std::invalid_argument("head_fused: bn needs 9 pointers, shape 5 ints, out 5 pointers");
   HeadArgs a{};
@@ -518,7 +544,16 @@ static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, 
   a.mix_lam = P<const float>(mix_lam);
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
-  return [a](hipStream_t s) { head_fused(a, s); };
+  return [a, kd](hipStream_t s) { head_fused(a, s, kd); };
+}
+
+static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam) {
+  return mk_head_fused_kd(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
+                          std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
+                          labels_b, mix_lam, 0, 0.f, 1.f);
 }
 
 static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
@@ -542,8 +577,9 @@ static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, floa
 // (pointers as integers; bucket_of_stage a 3-sequence) plus wgrad_wgs, the backward's
 // weight-gradient workgroups; probe and shards are set by the launch functions.  A
 // missing key and a key that is no PrnArgs member both raise, naming the key -- except
-// label_smoothing, topk and topk_out, which may be left out (0, 0, null), and the mixup
-// pair labels_b and mix_lam (null; both or neither).
+// label_smoothing, topk and topk_out, which may be left out (0, 0, null), the mixup
+// pair labels_b and mix_lam (null; both or neither) and, for the forward launch only, the
+// distillation triple teacher, kd_alpha and kd_inv_tau (null, 0, 1; a KdArgs of its own).
 static Launch mk_prn(int mode, py::dict args) {
   std::vector<std::string> known;
   auto get = [&](const char* key) -> py::object {
@@ -595,8 +631,15 @@ static Launch mk_prn(int mode, py::dict args) {
   if (args.contains("topk_out")) PRN_PTR(topk_out);
   if (args.contains("labels_b")) PRN_PTR(labels_b);
   if (args.contains("mix_lam")) PRN_PTR(mix_lam);
+  KdArgs kd;   // forward launch only: the backward and the head folds read no teacher
+  if (args.contains("teacher")) kd.teacher = P<const float>(get("teacher").cast<ptr_t>());
+  if (args.contains("kd_alpha")) kd.alpha = get("kd_alpha").cast<float>();
+  if (args.contains("kd_inv_tau")) kd.inv_tau = get("kd_inv_tau").cast<float>();
+  if (mode != 0 && kd.teacher)
+    throw std::invalid_argument("prn: teacher is an argument of the forward launch (mode 0)");
   check_xent_opts("prn", a.label_smoothing, a.topk, (ptr_t)(uintptr_t)a.topk_out);
   check_mix_ptrs("prn", (ptr_t)(uintptr_t)a.labels_b, (ptr_t)(uintptr_t)a.mix_lam);
+  check_kd("prn", kd);
 #undef PRN_PTR
 #undef PRN_VAL
   for (auto kv : args) {   // (every key read above exists, so any other is unknown)
@@ -606,7 +649,7 @@ static Launch mk_prn(int mode, py::dict args) {
   }
   if (!prn_supported(a.N, a.P, a.nblocks, a.classes, a.kpad))
     throw std::invalid_argument("prn: unsupported shape");
-  if (mode == 0) return [a](hipStream_t s) { prn_forward(a, s); };
+  if (mode == 0) return [a, kd](hipStream_t s) { prn_forward(a, s, kd); };
   if (mode == 1) return [a, wgs](hipStream_t s) { prn_backward(a, wgs, s); };
   if (mode == 2) return [a](hipStream_t s) { prn_head(a, s); };
   throw std::invalid_argument("prn: mode 0 (forward), 1 (backward) or 2 (head folds)");
@@ -1994,6 +2037,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "softmax_xent", mk_softmax_xent);
   def_op(m, plan, "softmax_xent", mk_softmax_xent_ls);
   def_op(m, plan, "softmax_xent", mk_softmax_xent_mix);
+  def_op(m, plan, "softmax_xent", mk_softmax_xent_kd);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce_k);
   def_op(m, plan, "bn_bwd_apply_acc", mk_bn_bwd_apply_acc);
@@ -2002,6 +2046,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "head_fused", mk_head_fused);
   def_op(m, plan, "head_fused", mk_head_fused_ls);
   def_op(m, plan, "head_fused", mk_head_fused_mix);
+  def_op(m, plan, "head_fused", mk_head_fused_kd);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
   def_op(m, plan, "prn_infer", mk_prn_infer);

@@ -8,6 +8,7 @@
 //     TF SAME pads 0 before / 1 after for 112 -> 56); the forward records the
 //     first-max window index, the backward gathers through it (deterministic).
 #include <stdexcept>
+#include <string>
 
 #include "bn_fused.h"
 #include "common.h"
@@ -94,13 +95,16 @@ void avgpool_bwd(const bf16* dpooled, bf16* dx, int N, int HW, int C, hipStream_
 // Single 1024-thread block (N <= a few thousand rows): one wave per row at a
 // time, fixed reduction order -> deterministic loss / precision / dbias.
 // dlogits = (softmax - target) * grad_scale   (grad_scale = 1/global_batch); the row
-// math is xent_row's (xent_row.h).
-__global__ void __launch_bounds__(1024)
-softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
+// math is xent_row's (xent_row.h).  The teacher (distillation) arguments exist in the
+// `_kd` kernels only: a launch without a teacher has the arguments and the code it had.
+template <bool KD>
+__device__ __forceinline__ void
+softmax_xent_body(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                     int N, int classes, float* loss_sum, float* correct,
                     bf16* __restrict__ dlogits, float* __restrict__ dbias, float grad_scale,
                     float* __restrict__ probs, float eps, int topk, float* topk_out,
-                    const int* __restrict__ labels_b, const float* __restrict__ mix_lam) {
+                    const int* __restrict__ labels_b, const float* __restrict__ mix_lam,
+                    const KdArgs& kd) {
   extern __shared__ __attribute__((aligned(16))) float sh[];  // [16 waves][ld] dbias partial + misc
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nw = blockDim.x >> 6;
@@ -117,8 +121,11 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
     const int yb = labels_b ? labels_b[row] : -1;   // mixup: the partner's label, the row's lam
     const float lam = mix_lam ? mix_lam[row] : 1.f;
     const float zyb = (yb >= 0 && yb < classes) ? z[yb] : 0.f;
+    const float* t = KD ? kd.teacher + (long)row * ld : nullptr;   // distillation: teacher row
     const XentRow r = xent_row<0>([&](int j) { return z[lane + 64 * j]; }, lane, classes, y, zy,
-                                  eps, topk, yb, zyb, lam);
+                                  eps, topk, yb, zyb, lam,
+                                  [&](int j) { return t[lane + 64 * j]; }, KD, kd.alpha,
+                                  kd.inv_tau);
     if (lane == 0) {
       lsum += r.loss;
       csum += r.top1;
@@ -127,9 +134,8 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
     for (int c = lane; c < ld; c += 64) {
       float g = 0.f;
       if (c < classes) {
-        const float p = r.prob(z[c]);
-        if (probs) probs[(long)row * ld + c] = p;
-        g = r.grad(p, c == y, c == yb, grad_scale);
+        if (probs) probs[(long)row * ld + c] = r.prob(z[c]);
+        g = r.grad(z[c], KD ? t[c] : 0.f, c == y, c == yb, grad_scale);
       }
       if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
       db[wave * ld + c] += g;
@@ -159,6 +165,23 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
   }
 }
 
+#define DTR_XENT_PARAMS                                                                     \
+  const float *__restrict__ logits, int ld, const int *__restrict__ labels, int N, int classes, \
+      float *loss_sum, float *correct, bf16 *__restrict__ dlogits, float *__restrict__ dbias,  \
+      float grad_scale, float *__restrict__ probs, float eps, int topk, float *topk_out,       \
+      const int *__restrict__ labels_b, const float *__restrict__ mix_lam
+#define DTR_XENT_ARGS                                                                       \
+  logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias, grad_scale, probs, eps, \
+      topk, topk_out, labels_b, mix_lam
+__global__ void __launch_bounds__(1024) softmax_xent_kernel(DTR_XENT_PARAMS) {
+  softmax_xent_body<false>(DTR_XENT_ARGS, KdArgs{});
+}
+__global__ void __launch_bounds__(1024) softmax_xent_kd_kernel(DTR_XENT_PARAMS, KdArgs kd) {
+  softmax_xent_body<true>(DTR_XENT_ARGS, kd);
+}
+#undef DTR_XENT_PARAMS
+#undef DTR_XENT_ARGS
+
 // Row-parallel variant (ws != nullptr): the single-block kernel above walks the
 // rows 16 at a time and each row three times from global memory -- ~100 us for
 // 128 x 1000 ImageNet logits on the critical path.  Here one wave owns one row,
@@ -166,13 +189,13 @@ softmax_xent_kernel(const float* __restrict__ logits, int ld, const int* __restr
 // correct flag and the fp32 gradient row to `ws`; softmax_xent_reduce_kernel
 // then folds dbias (per column, rows in fixed order) and the scalars.
 // Deterministic: every sum has a fixed order independent of the grid.
-template <int VPL>
-__global__ void __launch_bounds__(256)
-softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
+template <int VPL, bool KD>
+__device__ __forceinline__ void
+softmax_xent_rows_body(const float* __restrict__ logits, int ld, const int* __restrict__ labels,
                          int N, int classes, bf16* __restrict__ dlogits, float grad_scale,
                          float* __restrict__ probs, float* __restrict__ ws, bool want_g,
                          float eps, int topk, const int* __restrict__ labels_b,
-                         const float* __restrict__ mix_lam) {
+                         const float* __restrict__ mix_lam, const KdArgs& kd) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;   // wave-uniform
@@ -188,8 +211,17 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
   const int yb = labels_b ? labels_b[row] : -1;   // mixup: the partner's label, the row's lam
   const float lam = mix_lam ? mix_lam[row] : 1.f;
   const float zyb = (yb >= 0 && yb < classes) ? z[yb] : 0.f;
+  float tv[KD ? VPL : 1] = {};   // distillation: the teacher row, register-resident like z
+  if (KD) {
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+      const int c = lane + 64 * k;
+      if (c < classes) tv[KD ? k : 0] = kd.teacher[(long)row * ld + c];
+    }
+  }
   const XentRow r = xent_row<VPL>([&](int j) { return v[j]; }, lane, classes, y, zy, eps, topk,
-                                  yb, zyb, lam);
+                                  yb, zyb, lam, [&](int j) { return tv[KD ? j : 0]; }, KD,
+                                  kd.alpha, kd.inv_tau);
   float* gw = ws + (long)row * ld;
 #pragma unroll
   for (int k = 0; k < VPL; ++k) {
@@ -197,9 +229,8 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
     if (c >= ld) break;
     float g = 0.f;
     if (c < classes) {
-      const float p = r.prob(v[k]);
-      if (probs) probs[(long)row * ld + c] = p;
-      g = r.grad(p, c == y, c == yb, grad_scale);
+      if (probs) probs[(long)row * ld + c] = r.prob(v[k]);
+      g = r.grad(v[k], tv[KD ? k : 0], c == y, c == yb, grad_scale);
     }
     if (dlogits) dlogits[(long)row * ld + c] = (bf16)g;
     if (want_g) gw[c] = g;
@@ -211,6 +242,24 @@ softmax_xent_rows_kernel(const float* __restrict__ logits, int ld, const int* __
     if (topk > 0) ws[(long)N * ld + 2L * N + row] = r.topk;
   }
 }
+
+#define DTR_ROWS_PARAMS                                                                     \
+  const float *__restrict__ logits, int ld, const int *__restrict__ labels, int N, int classes, \
+      bf16 *__restrict__ dlogits, float grad_scale, float *__restrict__ probs,                 \
+      float *__restrict__ ws, bool want_g, float eps, int topk,                                \
+      const int *__restrict__ labels_b, const float *__restrict__ mix_lam
+#define DTR_ROWS_ARGS                                                                       \
+  logits, ld, labels, N, classes, dlogits, grad_scale, probs, ws, want_g, eps, topk, labels_b, \
+      mix_lam
+template <int VPL>
+__global__ void __launch_bounds__(256) softmax_xent_rows_kernel(DTR_ROWS_PARAMS) {
+  softmax_xent_rows_body<VPL, false>(DTR_ROWS_ARGS, KdArgs{});
+}
+template <int VPL>
+__global__ void __launch_bounds__(256) softmax_xent_rows_kd_kernel(DTR_ROWS_PARAMS, KdArgs kd) {
+  softmax_xent_rows_body<VPL, true>(DTR_ROWS_ARGS, kd);
+}
+#undef DTR_ROWS_PARAMS
 
 // grid = ceil(classes / 64) blocks of 256: thread (column c, row slice q = tid / 64)
 // sums rows q, q + 4, ... ; the 4 slices are added in fixed order.  Block 0 also
@@ -288,8 +337,8 @@ __device__ __forceinline__ void head_colsum(float (&v)[8], float (*red)[C]) {
   }
 }
 
-template <int C, int UPT>
-__global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
+template <int C, int UPT, bool KD>
+__device__ __forceinline__ void head_fused_body(const HeadArgs& a, const KdArgs& kd) {
   constexpr int G = C / 8;
   __shared__ float sc_s[C], sh_s[C], mu_s[C], rs_s[C], pool_s[C], dp_s[C], g_s[64];
   __shared__ float red[4][C], red2[4][C];
@@ -376,10 +425,13 @@ __global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
     const int yb = a.labels_b ? a.labels_b[n] : -1;   // mixup: partner label, the row's lam
     const float lam = a.mix_lam ? a.mix_lam[n] : 1.f;
     const float zyb = __shfl(z, (yb >= 0 && yb < a.classes) ? yb : 0, 64);
+    float t = 0.f;   // distillation: the teacher's logit of this lane's class
+    if (KD && lane < a.classes) t = kd.teacher[(long)n * kpad + lane];
     const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
-                                  a.label_smoothing, a.topk, yb, zyb, lam);
+                                  a.label_smoothing, a.topk, yb, zyb, lam, [&](int) { return t; },
+                                  KD, kd.alpha, kd.inv_tau);
     float g = 0.f;
-    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, lane == yb, a.grad_scale);
+    if (lane < a.classes) g = r.grad(z, t, lane == y, lane == yb, a.grad_scale);
     if (lane < kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)n * kpad + lane] = gb;
@@ -438,63 +490,94 @@ __global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
   }
 }
 
+template <int C, int UPT>
+__global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
+  head_fused_body<C, UPT, false>(a, KdArgs{});
+}
+template <int C, int UPT>
+__global__ void __launch_bounds__(256) head_fused_kd_kernel(HeadArgs a, KdArgs kd) {
+  head_fused_body<C, UPT, true>(a, kd);
+}
+
+void check_kd(const char* op, const KdArgs& kd) {
+  if (kd.teacher ? !(kd.alpha >= 0.f && kd.alpha <= 1.f && kd.inv_tau > 0.f) : kd.alpha != 0.f)
+    throw std::invalid_argument(std::string(op) + ": kd_alpha in [0, 1] and kd_inv_tau > 0 with "
+                                "a teacher, kd_alpha 0 without");
+}
+
 bool head_fused_supported(int N, int HW, int C, int classes, int kpad) {
   return N > 0 && (C == 16 || C == 32 || C == 64) && HW >= 1 && HW * (C / 8) <= 4 * 256 &&
          kpad <= 64 && classes <= kpad && classes >= 1;
 }
 
-void head_fused(const HeadArgs& a, hipStream_t s) {
+void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd) {
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
+  check_kd("head_fused", kd);
   const int units = a.HW * (a.C / 8);
   const dim3 grid((unsigned)a.N);
+#define DTR_HEAD_U(C_, U_)                                                                  \
+  do {                                                                                      \
+    if (kd.teacher)                                                                         \
+      hipLaunchKernelGGL((head_fused_kd_kernel<C_, U_>), grid, dim3(256), 0, s, a, kd);      \
+    else                                                                                    \
+      hipLaunchKernelGGL((head_fused_kernel<C_, U_>), grid, dim3(256), 0, s, a);             \
+  } while (0)
 #define DTR_HEAD(C_)                                                                        \
   if (a.C == C_) {                                                                          \
-    if (units <= 256) hipLaunchKernelGGL((head_fused_kernel<C_, 1>), grid, dim3(256), 0, s, a); \
-    else if (units <= 512) hipLaunchKernelGGL((head_fused_kernel<C_, 2>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((head_fused_kernel<C_, 4>), grid, dim3(256), 0, s, a);           \
+    if (units <= 256) DTR_HEAD_U(C_, 1);                                                    \
+    else if (units <= 512) DTR_HEAD_U(C_, 2);                                               \
+    else DTR_HEAD_U(C_, 4);                                                                 \
   }
   DTR_HEAD(16)
   DTR_HEAD(32)
   DTR_HEAD(64)
 #undef DTR_HEAD
+#undef DTR_HEAD_U
   DTR_CHECK_LAUNCH();
 }
 
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias, float grad_scale,
                   float* probs, float* ws, float label_smoothing, int topk, float* topk_out,
-                  hipStream_t s, const int* labels_b, const float* mix_lam) {
+                  hipStream_t s, const int* labels_b, const float* mix_lam, const KdArgs& kd) {
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
     throw std::invalid_argument("softmax_xent: label_smoothing in [0, 1), topk >= 0 (> 0 with topk_out)");
   if ((labels_b == nullptr) != (mix_lam == nullptr))
     throw std::invalid_argument("softmax_xent: labels_b and mix_lam go together");
+  check_kd("softmax_xent", kd);
   if (ws != nullptr && ld <= 1024) {
     const dim3 grid((unsigned)((N + 3) / 4));
     const bool want_g = dbias != nullptr;
-    if (ld <= 64)
-      hipLaunchKernelGGL(softmax_xent_rows_kernel<1>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
-                         labels_b, mix_lam);
-    else if (ld <= 256)
-      hipLaunchKernelGGL(softmax_xent_rows_kernel<4>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
-                         labels_b, mix_lam);
-    else
-      hipLaunchKernelGGL(softmax_xent_rows_kernel<16>, grid, dim3(256), 0, s, logits, ld, labels,
-                         N, classes, dlogits, grad_scale, probs, ws, want_g, label_smoothing, topk,
-                         labels_b, mix_lam);
+#define DTR_ROWS(VPL_)                                                                      \
+  do {                                                                                      \
+    if (kd.teacher)                                                                         \
+      hipLaunchKernelGGL(softmax_xent_rows_kd_kernel<VPL_>, grid, dim3(256), 0, s, DTR_ROWS_ARGS, kd); \
+    else                                                                                    \
+      hipLaunchKernelGGL(softmax_xent_rows_kernel<VPL_>, grid, dim3(256), 0, s, DTR_ROWS_ARGS); \
+  } while (0)
+    const float eps = label_smoothing;
+    if (ld <= 64) DTR_ROWS(1);
+    else if (ld <= 256) DTR_ROWS(4);
+    else DTR_ROWS(16);
+#undef DTR_ROWS
     DTR_CHECK_LAUNCH();
     softmax_xent_reduce(ws, ld, N, classes, loss_sum, correct, dbias, topk_out, s);
     return;
   }
   const int threads = 1024, nw = threads / 64;
   const size_t lds = ((size_t)nw * ld + 3 * nw) * sizeof(float);
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels, N,
-                     classes, loss_sum, correct, dlogits, dbias, grad_scale, probs, label_smoothing,
-                     topk, topk_out, labels_b, mix_lam);
+  if (kd.teacher)
+    hipLaunchKernelGGL(softmax_xent_kd_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels,
+                       N, classes, loss_sum, correct, dlogits, dbias, grad_scale, probs,
+                       label_smoothing, topk, topk_out, labels_b, mix_lam, kd);
+  else
+    hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels, N,
+                       classes, loss_sum, correct, dlogits, dbias, grad_scale, probs,
+                       label_smoothing, topk, topk_out, labels_b, mix_lam);
   DTR_CHECK_LAUNCH();
 }
+#undef DTR_ROWS_ARGS
 
 // ---------------------------------------------------------------------------
 // max pool (NHWC), window k, stride s, pad_top=pad_left=pad; out-of-range taps

@@ -267,6 +267,17 @@ struct PrnItem {             // backward weight-gradient work item: one conv x o
                              // (its slab stored write-through), -1 none
   int pad_;
 };
+// Distillation (xent_row.h): the teacher logits [N][kpad] fp32 (prn_infer's layout; nullptr =
+// none), the soft weight in [0, 1] and 1 / temperature.  A trailing argument of the loss-head
+// launches, and a kernel argument of their teacher instantiations ONLY: HeadArgs, PrnArgs and
+// every kernel of a launch without a teacher keep their argument bytes and their code.
+struct KdArgs {
+  const float* teacher = nullptr;
+  float alpha = 0.f;
+  float inv_tau = 1.f;
+};
+void check_kd(const char* op, const KdArgs& kd);   // invalid_argument on a bad triple
+
 struct PrnArgs {
   const PrnBlock* blocks;
   int nblocks;
@@ -328,7 +339,7 @@ std::vector<uint32_t> device_cu_mask();
 size_t prn_lds_bytes();
 int prn_bar_words();   // barrier / readiness / queue words of PrnArgs::bar (zeroed every step)
 int prn_acc_rep();   // fp64 accumulator replicas per BatchNorm of the persistent kernels
-void prn_forward(const PrnArgs& a, hipStream_t s);
+void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd = {});
 void prn_backward(const PrnArgs& a, int wgrad_wgs, hipStream_t s);
 // the head's batch folds (loss, precision, dense bias + weight gradients), one workgroup
 void prn_head(const PrnArgs& a, hipStream_t s);
@@ -495,7 +506,7 @@ struct HeadArgs {
   const float* mix_lam = nullptr;   // (both or neither; xent_row.h)
 };
 bool head_fused_supported(int N, int HW, int C, int classes, int kpad);
-void head_fused(const HeadArgs& a, hipStream_t s);
+void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd = {});
 // topk_out (may be nullptr): the sum of the workspace's in-top-k flags
 void softmax_xent_reduce(const float* ws, int ld, int N, int classes, float* loss_sum,
                          float* correct, float* dbias, float* topk_out, hipStream_t s);
@@ -504,7 +515,8 @@ void softmax_xent(const float* logits, int ld, const int* labels, int N, int cla
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias,
                   float grad_scale, float* probs, float* ws, float label_smoothing, int topk,
                   float* topk_out, hipStream_t s, const int* labels_b = nullptr,
-                  const float* mix_lam = nullptr);   // mixup: [N] partner labels, [N] lam (xent_row.h)
+                  const float* mix_lam = nullptr,   // mixup: [N] partner labels, [N] lam (xent_row.h)
+                  const KdArgs& kd = {});           // distillation: [N][ld] teacher logits
 long softmax_xent_ws_floats(int N, int ld);
 
 // ---- max pool (ImageNet stem) ----

@@ -126,8 +126,12 @@ __device__ __forceinline__ bool block_fwd(Ctx& x, bf16x4 (&xr)[8], int bi_next,
   return true;
 }
 
-template <int P>
-__device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
+// KD: the head reads a teacher row (distillation, xent_row.h) through `kd`, an argument of
+// the teacher kernel alone: the launch without a teacher has the arguments and the code it
+// always had.
+template <int P, bool KD = false>
+__device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem,
+                                                 const KdArgs& kd = {}) {
   Ctx x;
   x.a = &a;
   x.m = carve(smem);
@@ -242,10 +246,13 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem) {
     const int yb = a.labels_b ? a.labels_b[x.img] : -1;   // mixup: partner label, the row's lam
     const float lam = a.mix_lam ? a.mix_lam[x.img] : 1.f;
     const float zyb = __shfl(z, (yb >= 0 && yb < a.classes) ? yb : 0, 64);
+    float t = 0.f;   // distillation: the teacher's logit of this lane's class
+    if (KD && lane < a.classes) t = kd.teacher[(long)x.img * a.kpad + lane];
     const XentRow r = xent_row<1>([&](int) { return z; }, lane, a.classes, y, zy,
-                                  a.label_smoothing, a.topk, yb, zyb, lam);
+                                  a.label_smoothing, a.topk, yb, zyb, lam, [&](int) { return t; },
+                                  KD, kd.alpha, kd.inv_tau);
     float g = 0.f;
-    if (lane < a.classes) g = r.grad(r.prob(z), lane == y, lane == yb, a.grad_scale);
+    if (lane < a.classes) g = r.grad(z, t, lane == y, lane == yb, a.grad_scale);
     if (lane < a.kpad) {
       const bf16 gb = (bf16)g;
       a.dlogits[(long)x.img * a.kpad + lane] = gb;
@@ -274,6 +281,13 @@ template <int P>
 __global__ void __launch_bounds__(PT, 1) prn_fwd_kernel(PrnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   prn_forward_body<P>(a, smem);
+}
+
+// the same forward with the distillation head
+template <int P>
+__global__ void __launch_bounds__(PT, 1) prn_fwd_kd_kernel(PrnArgs a, KdArgs kd) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  prn_forward_body<P, true>(a, smem, kd);
 }
 
 // ---- host ------------------------------------------------------------------------------
@@ -310,15 +324,23 @@ long prn_fwd_resident(int P) {
                   : resident_blocks(prn_fwd_kernel<4>, LDS_TOTAL);
 }
 
-void prn_forward(const PrnArgs& a, hipStream_t s) {
+void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd) {
   if (!prn_supported(a.N, a.P, a.nblocks, a.classes, a.kpad) || a.N * a.P > cu_count())
     throw std::invalid_argument("prn_forward: unsupported shape (N x P <= CUs, 3n blocks, <= 64 classes)");
   PrnArgs b = a;
   b.probe = g_prn_probe;
   b.shards = prn_shards(a.N, a.P);
-  if (a.P == 1) hipLaunchKernelGGL(prn_fwd_kernel<1>, dim3(a.N), dim3(PT), LDS_TOTAL, s, b);
-  else if (a.P == 2) hipLaunchKernelGGL(prn_fwd_kernel<2>, dim3(a.N * 2), dim3(PT), LDS_TOTAL, s, b);
-  else hipLaunchKernelGGL(prn_fwd_kernel<4>, dim3(a.N * 4), dim3(PT), LDS_TOTAL, s, b);
+#define DTR_PRN_FWD(P_)                                                                    \
+  if (a.P == P_) {                                                                         \
+    if (kd.teacher)                                                                        \
+      hipLaunchKernelGGL(prn_fwd_kd_kernel<P_>, dim3(a.N * P_), dim3(PT), LDS_TOTAL, s, b, kd); \
+    else                                                                                   \
+      hipLaunchKernelGGL(prn_fwd_kernel<P_>, dim3(a.N * P_), dim3(PT), LDS_TOTAL, s, b);      \
+  }
+  DTR_PRN_FWD(1)
+  DTR_PRN_FWD(2)
+  DTR_PRN_FWD(4)
+#undef DTR_PRN_FWD
   DTR_CHECK_LAUNCH();
 }
 

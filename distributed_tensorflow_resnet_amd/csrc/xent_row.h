@@ -17,6 +17,20 @@
 //            t_c  = eps / K + (1 - eps) * (lam * [c == y] + (1 - lam) * [c == yb])   (y == yb too)
 //   top-1 / top-k are counted against the dominant label: y if lam >= 0.5, else yb
 // A row whose lam == 1.f takes the branch above (wave-uniform) and is bit-for-bit that row.
+//
+// Knowledge distillation (a teacher row t of the same layout, alpha, 1 / tau; Hinton et al.
+// 2015): with L_h and t_c the hard loss and target above (smoothing and mixup included),
+//   q = softmax(t / tau),  p = softmax(z),  p_tau = softmax(z / tau)
+//   row loss      = (1 - alpha) * L_h + alpha * tau^2 * sum_c q_c * (log q_c - log p_tau_c)
+//   gradient g_c  = ((1 - alpha) * (p_c - t_c) + alpha * tau * (p_tau_c - q_c)) * grad_scale
+//   top-1 / top-k stay counted against the labels
+// Two more softmaxes per row, each with its own row max (max(z / tau) is max(z) / tau; the
+// teacher's is a second max fold), per-lane sums in class order and the xor-shuffle fold.
+// The KL sum takes log q_c - log p_tau_c from the two logsumexps,
+//   (t_c / tau - lse_t) - (z_c / tau - lse_s),
+// never the log of a probability, and a class whose q_c underflowed to 0 adds exactly 0.
+// Only classes < K of either row are read.  A row without a teacher (wave-uniform) takes
+// none of this and is bit-for-bit the row above.
 #pragma once
 
 #include "common.h"
@@ -29,12 +43,22 @@ struct XentRow {
   float top1, topk;      // 0 / 1 flags (topk is 0 when k == 0)
   float t_miss;          // target of a class that is no label of the row: eps / K
   float w_hit, w_hit_b;  // what the first / the second (mixup) label's class adds to it
+  // distillation (kd false: none of these is read)
+  bool kd;               // the row has a teacher (wave-uniform)
+  float alpha, inv_tau;  // the soft weight and 1 / tau
+  float a_tau;           // alpha * tau, the soft gradient's weight
+  float lse_s, lse_t;    // logsumexp of z / tau and of t / tau over the valid classes
   __device__ __forceinline__ float prob(float z) const { return __expf(z - lse); }
-  // hit / hit_b: the class is the row's first / second label.  (Sums, not a choice among
-  // four targets: the compiler turned that choice into an indexed table in scratch memory.)
-  __device__ __forceinline__ float grad(float p, bool hit, bool hit_b, float grad_scale) const {
-    const float t = t_miss + (hit ? w_hit : 0.f) + (hit_b ? w_hit_b : 0.f);
-    return (p - t) * grad_scale;
+  // z, t: the class's student and teacher logit (t any value without a teacher).  hit /
+  // hit_b: the class is the row's first / second label.  (Sums, not a choice among four
+  // targets: the compiler turned that choice into an indexed table in scratch memory.)
+  __device__ __forceinline__ float grad(float z, float t, bool hit, bool hit_b,
+                                        float grad_scale) const {
+    const float tc = t_miss + (hit ? w_hit : 0.f) + (hit_b ? w_hit_b : 0.f);
+    const float hard = prob(z) - tc;
+    if (!kd) return hard * grad_scale;
+    const float soft = __expf(z * inv_tau - lse_s) - __expf(t * inv_tau - lse_t);
+    return ((1.f - alpha) * hard + a_tau * soft) * grad_scale;
   }
 };
 
@@ -43,10 +67,13 @@ struct XentRow {
 // rows); VPL == 0: ceil(classes / 64) values, whatever `z` reads them from.  `zy` is
 // z[y] (any value when y is out of range), the same in every lane.  `yb`, `zyb`, `lam`:
 // the mixup partner's label, its logit and the row's weight of y (lam == 1.f: none).
-template <int VPL, class Z>
+// `t(j)`: the teacher row through an accessor like `z`, called only when `kd` (the row has
+// a teacher; wave-uniform) and only for classes < `classes`; `alpha`, `inv_tau`: the soft
+// weight and 1 / tau.
+template <int VPL, class Z, class T>
 __device__ __forceinline__ XentRow xent_row(Z z, int lane, int classes, int y, float zy,
-                                            float eps, int k, int yb = -1, float zyb = 0.f,
-                                            float lam = 1.f) {
+                                            float eps, int k, int yb, float zyb, float lam,
+                                            T t, bool kd, float alpha, float inv_tau) {
   const int nv = VPL > 0 ? VPL : (classes + 63) >> 6;
   XentRow r;
   float mx = -INFINITY;
@@ -113,6 +140,41 @@ __device__ __forceinline__ XentRow xent_row(Z z, int lane, int classes, int y, f
     }
     const bool finite = fabsf(zy) < INFINITY;   // false for NaN
     r.topk = (yd_ok && finite && above < k) ? 1.f : 0.f;
+  }
+  r.kd = kd;
+  if (kd) {   // wave-uniform
+    r.alpha = alpha;
+    r.inv_tau = inv_tau;
+    r.a_tau = alpha / inv_tau;
+    float mt = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < nv; ++j)
+      if (lane + 64 * j < classes) mt = fmaxf(mt, t(j));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mt = fmaxf(mt, __shfl_xor(mt, o, 64));
+    const float ms = mx * inv_tau;
+    mt *= inv_tau;
+    float ss = 0.f, st = 0.f;
+#pragma unroll
+    for (int j = 0; j < nv; ++j)
+      if (lane + 64 * j < classes) {
+        ss += __expf(z(j) * inv_tau - ms);
+        st += __expf(t(j) * inv_tau - mt);
+      }
+    ss = wave_sum(ss);
+    st = wave_sum(st);
+    r.lse_s = ms + __logf(ss);
+    r.lse_t = mt + __logf(st);
+    float kl = 0.f;
+#pragma unroll
+    for (int j = 0; j < nv; ++j)
+      if (lane + 64 * j < classes) {
+        const float lq = t(j) * inv_tau - r.lse_t;
+        const float q = __expf(lq);
+        if (q > 0.f) kl += q * (lq - (z(j) * inv_tau - r.lse_s));
+      }
+    kl = wave_sum(kl);
+    r.loss = (1.f - alpha) * r.loss + (r.a_tau / inv_tau) * kl;
   }
   return r;
 }

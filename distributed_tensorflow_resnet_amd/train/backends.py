@@ -28,6 +28,7 @@ from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_to_lion,
                                 tf_to_rmsprop, tf_to_state)
+from .distill import TorchTeacher, check_distill, soft_loss
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug,
@@ -183,7 +184,15 @@ class CPUBackend:
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
-                 augmix_ops: str = "augmix"):
+                 augmix_ops: str = "augmix", distill_alpha: float = 0.0,
+                 distill_temperature: float = 4.0, distill_teacher=None):
+        # knowledge distillation, csrc/xent_row.h's soft term in fp32 torch (train/distill.py):
+        # the teacher a TorchResNet in eval mode on the batch the student sees (0 = off)
+        self.distill_alpha, self.distill_tau = check_distill(
+            distill_alpha, distill_temperature, distill_teacher is not None, spec.dataset)
+        self.teacher = (TorchTeacher(spec, *distill_teacher) if self.distill_alpha > 0
+                        else None)
+        self._teacher_logits = None
         # mixup, csrc/data.hip's blend in fp32 torch from the same table and draw (0 = off)
         self.mixup_alpha = check_mixup_alpha(mixup_alpha)
         self.data_seed = data_seed
@@ -396,6 +405,10 @@ class CPUBackend:
             self.last_input = x
         logits = m(x, True)
         xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing, **mix)
+        if self.teacher is not None:   # smoothing and mixup stay in the hard term
+            a, self._teacher_logits = self.distill_alpha, self.teacher.logits(x)
+            xent = (1.0 - a) * xent + a * soft_loss(logits, self._teacher_logits,
+                                                    self.distill_tau).mean()
         # mean over the GLOBAL batch: local mean * (local/global), then sum-allreduce
         (xent * (self.N / self.global_batch)).backward()
         g = master.grad
@@ -711,9 +724,15 @@ class CPUBackend:
 
         return lars_trust_summary({n: v[:3] for n, v in self._lars_state.items() if not v[3]})
 
+    def distill_state(self):
+        """The teacher logits of the last step (None: distillation off, or no step yet)."""
+        return self._teacher_logits
+
     def metrics(self, top5: bool = False):
         """The last step's scalars; ``top5`` adds `precision_top5` (as Engine.metrics)."""
         m = dict(self._last)
+        if self.teacher is not None:
+            m["distill_alpha"], m["distill_temperature"] = self.distill_alpha, self.distill_tau
         if top5:
             m["precision_top5"] = self._last_top5
         if self._clip_state is not None:
@@ -819,7 +838,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
-                 augmix_ops: str = "augmix"):
+                 augmix_ops: str = "augmix", distill_alpha: float = 0.0,
+                 distill_temperature: float = 4.0, distill_teacher=None):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -841,6 +861,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
     erase.update(augmix_width=augmix_width, augmix_depth=augmix_depth,
                  augmix_severity=augmix_severity, augmix_alpha=augmix_alpha,
                  augmix_ops=augmix_ops)
+    erase.update(distill_alpha=distill_alpha, distill_temperature=distill_temperature,
+                 distill_teacher=distill_teacher)
     if device == "gpu":
         from .engine import Engine
 

@@ -214,6 +214,15 @@ def main(argv=None, kind: str = "cifar") -> int:
 
         data = CifarData(flags.train_data_path, spec.dataset, train=True)
         resident = (data.images, data.labels)
+    teacher = None
+    if flags.distill_alpha > 0:   # (the parser has checked that a directory is given)
+        from .distill import load_teacher
+
+        teacher = load_teacher(flags.distill_teacher_dir, flags.dataset,
+                               flags.distill_teacher_size, spec.num_classes)
+        H.log(f"distillation: ResNet-{flags.distill_teacher_size} teacher from "
+              f"{flags.distill_teacher_dir}, alpha {flags.distill_alpha}, temperature "
+              f"{flags.distill_temperature}")
     backend = make_backend(spec, flags.batch_size, device=device, weight_decay=flags.weight_decay,
                            lr_schedule=sched, optimizer=flags.optimizer, seed=flags.seed,
                            dist_ctx=dp_ctx, bucket_mb=flags.bucket_mb, use_graph=flags.use_graph,
@@ -254,7 +263,10 @@ def main(argv=None, kind: str = "cifar") -> int:
                            muon_nesterov=flags.muon_nesterov,
                            muon_ns_steps=flags.muon_ns_steps,
                            muon_aux_lr_scale=flags.muon_aux_lr_scale,
-                           muon_tiled=flags.muon_tiled)
+                           muon_tiled=flags.muon_tiled,
+                           distill_alpha=flags.distill_alpha,
+                           distill_temperature=flags.distill_temperature,
+                           distill_teacher=teacher)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

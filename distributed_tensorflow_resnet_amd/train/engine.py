@@ -63,6 +63,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
+from .distill import DeviceTeacher, check_distill
+
 BF16 = torch.bfloat16
 BN_DECAY = 0.997
 # Diagnostics: DTR_DIAG_SKIP=wgrad,dgrad,... drops those launches (wrong math; timing only)
@@ -151,7 +153,8 @@ class Engine:
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
-                 augmix_ops: str = "augmix"):
+                 augmix_ops: str = "augmix", distill_alpha: float = 0.0,
+                 distill_temperature: float = 4.0, distill_teacher=None):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
@@ -253,6 +256,14 @@ class Engine:
         (self.augmix_width, self.augmix_depth, self.augmix_severity, self.augmix_alpha,
          self.augmix_op_ids) = check_augmix(augmix_width, augmix_depth, augmix_severity,
                                             augmix_alpha, augmix_ops, self.randaug_num_ops)
+        # knowledge distillation (train/distill.py; csrc/xent_row.h): ``distill_teacher`` =
+        # (teacher spec, checkpoint tensors | seed).  One prn_infer launch of the teacher behind
+        # the input launches, its logits in whichever head the plan records.  alpha 0 = off:
+        # nothing allocated (a given teacher is not even built), every plan op for op the same.
+        self.distill_alpha, self.distill_tau = check_distill(
+            distill_alpha, distill_temperature, distill_teacher is not None, spec.dataset)
+        self._distill_teacher = distill_teacher if self.distill_alpha > 0 else None
+        self.teacher = None
         # shadow (exponential moving average) copy of the trainables, advanced by one launch
         # at the end of the optimizer segment (csrc/ema.hip); 0 = off: no buffer, no launch
         if not 0.0 <= ema_decay < 1.0:
@@ -419,6 +430,8 @@ class Engine:
                           else None)
         self._build_weight_layout()
         self._alloc_activations()
+        if self._distill_teacher is not None:
+            self.teacher = DeviceTeacher(self, *self._distill_teacher)
         # Persistent small-batch CIFAR step (train/persist.py, csrc/prn_*.hip): the
         # forward and the backward each as ONE launch (tune persist: -1 auto = per-rank
         # batch <= AUTO_MAX_BATCH on a supported CIFAR network, 0 off, 1 whenever supported)
@@ -985,6 +998,23 @@ class Engine:
         """The loss heads' trailing mixup arguments (labels_b, mix_lam); () with mixup off."""
         return () if self.labels_b is None else (self.labels_b.data_ptr(), self.mix_lam.data_ptr())
 
+    def head_tail_args(self) -> tuple:
+        """Every trailing argument of the loss heads: the mixup pair and, with distillation
+        on, behind it (null when mixup is off) the teacher logits, alpha and 1 / tau."""
+        mix = self.mix_head_ptrs()
+        if self.teacher is None:
+            return mix
+        return (mix or (0, 0)) + (self.teacher.logits.data_ptr(), self.distill_alpha,
+                                  1.0 / self.distill_tau)
+
+    def distill_state(self):
+        """The teacher logits [N, classes] of the last step (synchronises).  None:
+        distillation off, or no step yet."""
+        if self.teacher is None or self._steps_run == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        return self.teacher.logits[:, :self.spec.num_classes].clone()
+
     def ema_state(self):
         """{tensor name: view of its shadow in the flat EMA buffer} (None: --ema_decay 0)."""
         if self.ema is None:
@@ -1239,7 +1269,8 @@ class Engine:
         on, `grad_norm` and `clip_scale` of the last step are added (clip_state()); with mixup
         on, `mixup_lam` (mixup_state()); with mixup or CutMix on, also `mix_mode` (0 mixup,
         1 CutMix) and, for a CutMix step, `cutmix_area` (mix_state()); with AugMix on,
-        `augmix` ("w<width>-s<severity>")."""
+        `augmix` ("w<width>-s<severity>"); with distillation on, `distill_alpha` and
+        `distill_temperature`, and `cross_entropy` is the combined loss."""
         if self._cost_at != self._steps_run:
             self._run("cost", torch.cuda.current_stream().cuda_stream)
             self._cost_at = self._steps_run
@@ -1281,6 +1312,8 @@ class Engine:
                                     (self.N * self.spec.image_h * self.spec.image_w))
         if self.augmix_width > 0:
             m["augmix"] = f"w{self.augmix_width}-s{self.augmix_severity}"
+        if self.teacher is not None:   # (cross_entropy and cost are the combined loss)
+            m["distill_alpha"], m["distill_temperature"] = self.distill_alpha, self.distill_tau
         return m
 
     def sync_from_params(self, ema_loaded: bool = False):

@@ -411,6 +411,10 @@ class PersistStep:
         # dense bias and weight gradients; prn_head)
         sp = eng.scalars.data_ptr()
         mix = dict(zip(("labels_b", "mix_lam"), eng.mix_head_ptrs()))   # {} with mixup off
+        if eng.teacher is not None and fwd:   # distillation: the forward's head alone reads
+            # the teacher logits, alpha, 1 / tau; the other launches' arguments stay as they are
+            mix.update(teacher=eng.teacher.logits.data_ptr(), kd_alpha=eng.distill_alpha,
+                       kd_inv_tau=1.0 / eng.distill_tau)
         return dict(
             **mix, blocks=self.block_dev.data_ptr(), nblocks=self.nblocks, bns=self.bn_dev.data_ptr(),
             x_in=eng.x_in.data_ptr(), stem_w=eng.convs[spec.stem.name].ohwi, pool_acc=pool_ptr,

@@ -821,6 +821,11 @@ class StepRecorder:
                 e.gstep.data_ptr(), e.erase_tab.data_ptr(), e.erase_tab.numel(), e.erase_thresh,
                 noise.data_ptr() if noise is not None else 0,
                 noise.numel() if noise is not None else 0, e.erase_log.data_ptr())
+        self._teacher_op = None
+        if e.teacher is not None:
+            # distillation: the teacher's one-launch inference forward on the main stream, on
+            # the very x_in the student's forward reads next; it writes only the teacher logits
+            self._teacher_op = e.teacher.record(plan, e.x_in, e.N)
 
     def record_layers(self) -> RecordedStep:
         """The launch-per-layer step."""
@@ -910,7 +915,7 @@ class StepRecorder:
                             [N, HL * WL, F, spec.num_classes, e.kpad], 1.0 / e.global_batch,
                             [e.pooled.data_ptr(), e.dlogits.data_ptr(),
                              e.xent_ws.data_ptr(), dact.data_ptr(), fbn.bacc.data_ptr()],
-                            e.label_smoothing, e.topk, *e.mix_head_ptrs())
+                            e.label_smoothing, e.topk, *e.head_tail_args())
         else:
             self._bn_finalize(fbn, consumer_conv=False)   # consumer: bnrelu_avgpool
             plan.bnrelu_avgpool(XL.data_ptr(), fbn.scale.data_ptr(), fbn.shift.data_ptr(),
@@ -921,7 +926,7 @@ class StepRecorder:
             plan.softmax_xent(e.logits.data_ptr(), e.kpad, e.labels.data_ptr(), N,
                               spec.num_classes, sp, sp + 4, e.dlogits.data_ptr(),
                               e.dense_bias_grad, 1.0 / e.global_batch, 0, e.xent_ws.data_ptr(),
-                              e.label_smoothing, e.topk, sp + 20, *e.mix_head_ptrs())
+                              e.label_smoothing, e.topk, sp + 20, *e.head_tail_args())
         return dact
 
     def _backward(self, dact):
@@ -1048,6 +1053,11 @@ class StepRecorder:
                 out.op_buffers[self._erase_op] = {"input"}   # the overlap plan declares its ops
             if self._preaug_op is not None and out.op_buffers:
                 out.op_buffers[self._preaug_op] = {"input"}
+            if self._teacher_op is not None and out.op_buffers:
+                # (the teacher logits are no declared buffer: their only reader, the forward
+                # launch, follows this op on the main stream, and no comm-stream op touches
+                # them -- were either op moved to another stream, they would have to be one)
+                out.op_buffers[self._teacher_op] = {"input"}
             out.seg["bwd"] = (b1, plan.size())
             if e.opt_fused:   # the rest: the last bucket's segments
                 self._emit_optimizer(fused_slabs={}, gin=self._packed_gin(),

@@ -314,6 +314,16 @@ class FlagParser(argparse.ArgumentParser):
                 self.error("--augmix_width cannot be combined with --resident_data: the "
                            "resident input kernel picks its records itself, so there is no "
                            "uint8 batch to augment")
+        if hasattr(ns, "distill_alpha"):
+            from ..train.distill import check_distill
+
+            try:   # alpha > 0 needs a teacher; a teacher needs a CIFAR student
+                check_distill(ns.distill_alpha, ns.distill_temperature,
+                              bool(ns.distill_teacher_dir), getattr(ns, "dataset", "cifar10"))
+            except ValueError as e:
+                self.error("--distill_alpha: " + str(e))
+            if ns.distill_teacher_dir and (ns.distill_teacher_size - 2) % 6 != 0:
+                self.error(f"--distill_teacher_size must be 6n+2, got {ns.distill_teacher_size}")
         if hasattr(ns, "lr_decay"):
             from ..train.schedule import schedule_from_flags
 
@@ -484,6 +494,23 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                    help="Training-loss label smoothing eps in [0, 1): targets (1 - eps) * onehot "
                         "+ eps / classes (tf.losses.softmax_cross_entropy's label_smoothing).  "
                         "Evaluation is never smoothed.")
+    if not is_eval:
+        p.add_argument("--distill_teacher_dir", default="",
+                       help="Knowledge distillation (Hinton et al. 2015): the directory whose "
+                            "latest checkpoint is the frozen teacher, a CIFAR ResNet of "
+                            "--distill_teacher_size with the student's classes.  Its forward is "
+                            "one more launch per step on the batch the student sees (after every "
+                            "augmentation); it is not saved with the student, so a resumed run "
+                            "passes these flags again.  Not for the ImageNet networks.")
+        p.add_argument("--distill_teacher_size", type=int, default=110,
+                       help="--distill_teacher_dir: the teacher's depth (6n+2).")
+        p.add_argument("--distill_alpha", type=float, default=0.0,
+                       help="Weight in [0, 1] of the soft term: loss = (1 - alpha) * hard loss + "
+                            "alpha * T^2 * KL(softmax(teacher / T) || softmax(student / T)).  "
+                            "Label smoothing and mixup stay in the hard term; precision stays "
+                            "counted against the labels.  0 = off (no teacher is built).")
+        p.add_argument("--distill_temperature", type=float, default=4.0,
+                       help="--distill_alpha: the temperature T (> 0).")
     p.add_argument("--ema_decay", type=_ema_decay, default=0.0,
                    help="Keep an exponential moving average of the trainable weights on the "
                         "device: shadow -= (1 - decay) * (shadow - weight) after every step "

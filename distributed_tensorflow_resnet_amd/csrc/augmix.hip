@@ -29,6 +29,15 @@
 //     thread that then overwrites that vector, and by every thread before the next chain's
 //     first barrier, behind which the slot is written again.
 // No float, no global atomics, no inline assembly, plain C++ stores.
+//
+// Three-view fan-out for the Jensen-Shannon loss (AmFan, the `_fan` kernels; data/augmix.py
+// augmix_fanout): B stored images become 3B outputs.  Workgroup p reads source image p % B
+// wherever the kernels above read "the original".  p < B is the clean view: a straight 16-B
+// copy, its log rows -1.  p >= B runs the chains keyed on the OUTPUT position p (seed,
+// global_step, p), so one image's two views differ and a resumed run continues the sequence;
+// its thread 0 also writes labels[p] = labels[p % B] (slots < B are only read).  The HWC
+// workspace and the output slot stay keyed on p.  Without AmFan the launch is the kernel, the
+// arguments and the bits it was.
 #include <stdexcept>
 #include <string>
 
@@ -85,15 +94,41 @@ struct AmDraw {
   }
 };
 
-__global__ void __launch_bounds__(256)
-augmix_chw_kernel(const uint8_t* __restrict__ in, uint8_t* out, unsigned long long seed,
-                  const long long* __restrict__ gstep, AugMix am) {
+struct AmFan {
+  int B;         // source images; the grid has 3 B workgroups
+  int* labels;   // [3 B], the first B given
+};
+
+// the clean view's log rows, and the views' labels (workgroup-uniform p)
+__device__ __forceinline__ void am_fan_side(const AmFan& fan, const AugMix& am, int p) {
+  if (p < fan.B) {
+    if (am.log && threadIdx.x < am.width * AM_LOG_ROW)
+      am.log[(long)p * am.width * AM_LOG_ROW + threadIdx.x] = -1;
+  } else if (threadIdx.x == 0 && fan.labels) {
+    fan.labels[p] = fan.labels[p % fan.B];
+  }
+}
+
+template <bool FAN>
+__device__ __forceinline__ void
+augmix_chw_body(const uint8_t* __restrict__ in, uint8_t* out, unsigned long long seed,
+                const long long* __restrict__ gstep, const AugMix& am, const AmFan& fan) {
   constexpr int H = 32, W = 32, NV = 3 * H * W / 16;
   __shared__ uint4 orig[NV];
   __shared__ uint4 buf[2][NV];
   __shared__ RaScratch s;
   const int n = blockIdx.x, tid = threadIdx.x;
-  if (tid < NV) orig[tid] = reinterpret_cast<const uint4*>(in)[(long)n * NV + tid];
+  const int src = FAN ? n % fan.B : n;   // the stored image this output comes from
+  if (FAN) {
+    am_fan_side(fan, am, n);
+    if (n < fan.B) {   // the clean view (workgroup-uniform)
+      if (tid < NV)
+        reinterpret_cast<uint4*>(out)[(long)n * NV + tid] =
+            reinterpret_cast<const uint4*>(in)[(long)src * NV + tid];
+      return;
+    }
+  }
+  if (tid < NV) orig[tid] = reinterpret_cast<const uint4*>(in)[(long)src * NV + tid];
   AmDraw draw(seed, gstep, n);
   const int* e = am.mix + (long)draw.entry(am) * (am.width + 1);
   const unsigned m = (unsigned)e[am.width];
@@ -150,17 +185,38 @@ augmix_chw_kernel(const uint8_t* __restrict__ in, uint8_t* out, unsigned long lo
         make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+__global__ void __launch_bounds__(256)
+augmix_chw_kernel(const uint8_t* __restrict__ in, uint8_t* out, unsigned long long seed,
+                  const long long* __restrict__ gstep, AugMix am) {
+  augmix_chw_body<false>(in, out, seed, gstep, am, AmFan{});
+}
+__global__ void __launch_bounds__(256)
+augmix_chw_fan_kernel(const uint8_t* __restrict__ in, uint8_t* out, unsigned long long seed,
+                      const long long* __restrict__ gstep, AugMix am, AmFan fan) {
+  augmix_chw_body<true>(in, out, seed, gstep, am, fan);
+}
+
 extern __shared__ uint4 am_dyn[];   // RaScratch, then the image
 
-__global__ void __launch_bounds__(1024)
-augmix_hwc_kernel(const uint8_t* __restrict__ in, uint8_t* out, int H, int W,
-                  unsigned long long seed, const long long* __restrict__ gstep, AugMix am) {
+template <bool FAN>
+__device__ __forceinline__ void
+augmix_hwc_body(const uint8_t* __restrict__ in, uint8_t* out, int H, int W,
+                unsigned long long seed, const long long* __restrict__ gstep, const AugMix& am,
+                const AmFan& fan) {
   RaScratch& s = *reinterpret_cast<RaScratch*>(am_dyn);
   uint8_t* lds = reinterpret_cast<uint8_t*>(am_dyn) + sizeof(RaScratch);
   const int n = blockIdx.x, tid = threadIdx.x;
   const int nvec = 3 * H * W / 16;
-  const uint4* gin = reinterpret_cast<const uint4*>(in) + (long)n * nvec;
+  // the original: the stored image this output comes from (re-staged by every chain)
+  const uint4* gin = reinterpret_cast<const uint4*>(in) + (long)(FAN ? n % fan.B : n) * nvec;
   uint8_t* g = out + (long)n * nvec * 16;   // this image's slot of the output: the other home
+  if (FAN) {
+    am_fan_side(fan, am, n);
+    if (n < fan.B) {   // the clean view (workgroup-uniform)
+      for (int v = tid; v < nvec; v += 1024) reinterpret_cast<uint4*>(g)[v] = gin[v];
+      return;
+    }
+  }
   // 16 uint16 sums per image vector (null at width 1, where nothing is carried)
   uint4* ws = am.acc ? reinterpret_cast<uint4*>(am.acc + (long)n * nvec * 16) : nullptr;
   AmDraw draw(seed, gstep, n);
@@ -219,10 +275,24 @@ augmix_hwc_kernel(const uint8_t* __restrict__ in, uint8_t* out, int H, int W,
   }
 }
 
+__global__ void __launch_bounds__(1024)
+augmix_hwc_kernel(const uint8_t* __restrict__ in, uint8_t* out, int H, int W,
+                  unsigned long long seed, const long long* __restrict__ gstep, AugMix am) {
+  augmix_hwc_body<false>(in, out, H, W, seed, gstep, am, AmFan{});
+}
+__global__ void __launch_bounds__(1024)
+augmix_hwc_fan_kernel(const uint8_t* __restrict__ in, uint8_t* out, int H, int W,
+                      unsigned long long seed, const long long* __restrict__ gstep, AugMix am,
+                      AmFan fan) {
+  augmix_hwc_body<true>(in, out, H, W, seed, gstep, am, fan);
+}
+
 }  // namespace
 
 void augmix_check(const void* in, const void* out, int N, int H, int W, int hwc,
-                  const AugMix& am) {
+                  const AugMix& am, int fan_B) {
+  if (fan_B < 0 || (fan_B > 0 && N != 3 * fan_B))
+    throw std::invalid_argument("augmix: the three-view fan-out writes N == 3 * fan_B outputs");
   if (!in || !out || !am.tables || !am.mix)
     throw std::invalid_argument("augmix: null buffer or table");
   if (reinterpret_cast<uintptr_t>(in) % 16 || reinterpret_cast<uintptr_t>(out) % 16)
@@ -231,7 +301,8 @@ void augmix_check(const void* in, const void* out, int N, int H, int W, int hwc,
   const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
   const uintptr_t bytes = (uintptr_t)(N > 0 ? N : 0) * 3u * (uintptr_t)(H > 0 ? H : 0) *
                           (uintptr_t)(W > 0 ? W : 0);
-  if (a == b || (a < b + bytes && b < a + bytes))
+  const uintptr_t in_bytes = fan_B > 0 ? bytes / 3u : bytes;   // the fan-out reads B images
+  if (a == b || (a < b + bytes && b < a + in_bytes))
     throw std::invalid_argument("augmix: needs an output buffer of its own, not overlapping "
                                 "the input");
   if (am.width < 1 || am.width > 4) throw std::invalid_argument("augmix: width must be in 1..4");
@@ -260,21 +331,39 @@ void augmix_check(const void* in, const void* out, int N, int H, int W, int hwc,
                                 "uint16 workspace [N][3 H W]");
   // above the 64 KB a workgroup gets by default: asked for once per process, here, so that
   // it has happened when the op is made and no launch (or graph capture) has to
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(augmix_hwc_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, RA_LDS_MAX);
+  // (each kernel when it is first asked for: a run without the fan-out never touches its kernel)
+  const auto lds_attr = [](const void* kernel) {
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RA_LDS_MAX);
+  };
+  hipError_t attr;
+  if (fan_B > 0) {
+    static const hipError_t fan = lds_attr(reinterpret_cast<const void*>(augmix_hwc_fan_kernel));
+    attr = fan;
+  } else {
+    static const hipError_t plain = lds_attr(reinterpret_cast<const void*>(augmix_hwc_kernel));
+    attr = plain;
+  }
   if (attr != hipSuccess)
     throw std::runtime_error(std::string("augmix: cannot get 160 KB of LDS: ") +
                              hipGetErrorString(attr));
 }
 
 void augmix(const uint8_t* in, uint8_t* out, int N, int H, int W, int hwc,
-            unsigned long long seed, const long long* gstep, const AugMix& am, hipStream_t s) {
-  augmix_check(in, out, N, H, W, hwc, am);
+            unsigned long long seed, const long long* gstep, const AugMix& am, hipStream_t s,
+            int fan_B, int* labels) {
+  augmix_check(in, out, N, H, W, hwc, am, fan_B);
+  const AmFan fan{fan_B, labels};
+  const size_t lds = sizeof(RaScratch) + 3 * (size_t)H * W;
   if (!hwc) {
-    hipLaunchKernelGGL(augmix_chw_kernel, dim3(N), dim3(256), 0, s, in, out, seed, gstep, am);
+    if (fan_B)
+      hipLaunchKernelGGL(augmix_chw_fan_kernel, dim3(N), dim3(256), 0, s, in, out, seed, gstep,
+                         am, fan);
+    else
+      hipLaunchKernelGGL(augmix_chw_kernel, dim3(N), dim3(256), 0, s, in, out, seed, gstep, am);
+  } else if (fan_B) {
+    hipLaunchKernelGGL(augmix_hwc_fan_kernel, dim3(N), dim3(1024), lds, s, in, out, H, W, seed,
+                       gstep, am, fan);
   } else {
-    const size_t lds = sizeof(RaScratch) + 3 * (size_t)H * W;
     hipLaunchKernelGGL(augmix_hwc_kernel, dim3(N), dim3(1024), lds, s, in, out, H, W, seed,
                        gstep, am);
   }

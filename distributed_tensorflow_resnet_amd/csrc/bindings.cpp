@@ -443,20 +443,44 @@ static KdArgs mk_kd(const char* op, ptr_t teacher, float kd_alpha, float kd_inv_
   return kd;
 }
 
+// AugMix's Jensen-Shannon term (xent_row.h): two more trailing arguments, jsd_B (N == 3 *
+// jsd_B rows in triples n, n + B, n + 2B; 0: off) and jsd_weight >= 0; a fifth arity of the
+// same ops.  Not with a teacher or a mixup pair.
+static JsdArgs mk_jsd(const char* op, int jsd_B, float jsd_weight, int N, const KdArgs& kd,
+                      ptr_t labels_b) {
+  JsdArgs jsd;
+  jsd.B = jsd_B;
+  jsd.weight = jsd_weight;
+  check_jsd(op, jsd, N, kd, P<const void>(labels_b));
+  return jsd;
+}
+
+static Launch mk_softmax_xent_jsd(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
+                                  ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
+                                  float jsd_weight) {
+  check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
+  check_mix_ptrs("softmax_xent", labels_b, mix_lam);
+  const KdArgs kd = mk_kd("softmax_xent", teacher, kd_alpha, kd_inv_tau);
+  const JsdArgs jsd = mk_jsd("softmax_xent", jsd_B, jsd_weight, N, kd, labels_b);
+  return [=](hipStream_t s) {
+    softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
+                 P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
+                 P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s,
+                 P<const int>(labels_b), P<const float>(mix_lam), kd, jsd);
+  };
+}
+
 static Launch mk_softmax_xent_kd(ptr_t logits, int ld, ptr_t labels, int N, int classes,
                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
                                  ptr_t teacher, float kd_alpha, float kd_inv_tau) {
-  check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
-  check_mix_ptrs("softmax_xent", labels_b, mix_lam);
-  const KdArgs kd = mk_kd("softmax_xent", teacher, kd_alpha, kd_inv_tau);
-  return [=](hipStream_t s) {
-    softmax_xent(P<const float>(logits), ld, P<const int>(labels), N, classes, P<float>(loss_sum),
-                 P<float>(correct), P<bf16>(dlogits), P<float>(dbias), grad_scale,
-                 P<float>(probs), P<float>(ws), label_smoothing, topk, P<float>(topk_out), s,
-                 P<const int>(labels_b), P<const float>(mix_lam), kd);
-  };
+  return mk_softmax_xent_jsd(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
+                             grad_scale, probs, ws, label_smoothing, topk, topk_out, labels_b,
+                             mix_lam, teacher, kd_alpha, kd_inv_tau, 0, 0.f);
 }
 
 static Launch mk_softmax_xent_mix(ptr_t logits, int ld, ptr_t labels, int N, int classes,
@@ -499,12 +523,13 @@ static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t
 // head_fused(x, bn=[acc, gamma, beta, mmean, mvar, mean, rstd, scale, shift], momentum, eps,
 //            update_moving, w_hwio, bias, labels, shape=[N, HW, C, classes, kpad], grad_scale,
 //            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk[, labels_b, mix_lam
-//            [, teacher, kd_alpha, kd_inv_tau]]])
-static Launch mk_head_fused_kd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                               float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
-                               ptr_t teacher, float kd_alpha, float kd_inv_tau) {
+//            [, teacher, kd_alpha, kd_inv_tau[, jsd_B, jsd_weight]]]])
+static Launch mk_head_fused_jsd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
+                                ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
+                                float jsd_weight) {
   check_xent_opts("head_fused", label_smoothing, topk, 0);
   check_mix_ptrs("head_fused", labels_b, mix_lam);
   const KdArgs kd = mk_kd("head_fused", teacher, kd_alpha, kd_inv_tau);
@@ -544,7 +569,18 @@ static Launch mk_head_fused_kd(ptr_t x, std::vector<ptr_t> bn, float momentum, f
   a.mix_lam = P<const float>(mix_lam);
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
-  return [a, kd](hipStream_t s) { head_fused(a, s, kd); };
+  const JsdArgs jsd = mk_jsd("head_fused", jsd_B, jsd_weight, a.N, kd, labels_b);
+  return [a, kd, jsd](hipStream_t s) { head_fused(a, s, kd, jsd); };
+}
+
+static Launch mk_head_fused_kd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                               float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
+                               ptr_t teacher, float kd_alpha, float kd_inv_tau) {
+  return mk_head_fused_jsd(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
+                           std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
+                           labels_b, mix_lam, teacher, kd_alpha, kd_inv_tau, 0, 0.f);
 }
 
 static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
@@ -579,7 +615,8 @@ static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, floa
 // missing key and a key that is no PrnArgs member both raise, naming the key -- except
 // label_smoothing, topk and topk_out, which may be left out (0, 0, null), the mixup
 // pair labels_b and mix_lam (null; both or neither) and, for the forward launch only, the
-// distillation triple teacher, kd_alpha and kd_inv_tau (null, 0, 1; a KdArgs of its own).
+// distillation triple teacher, kd_alpha and kd_inv_tau (null, 0, 1; a KdArgs of its own) and
+// the Jensen-Shannon pair jsd_B and jsd_weight (0, 0; a JsdArgs of its own).
 static Launch mk_prn(int mode, py::dict args) {
   std::vector<std::string> known;
   auto get = [&](const char* key) -> py::object {
@@ -640,6 +677,12 @@ static Launch mk_prn(int mode, py::dict args) {
   check_xent_opts("prn", a.label_smoothing, a.topk, (ptr_t)(uintptr_t)a.topk_out);
   check_mix_ptrs("prn", (ptr_t)(uintptr_t)a.labels_b, (ptr_t)(uintptr_t)a.mix_lam);
   check_kd("prn", kd);
+  JsdArgs jsd;   // forward launch only, like the teacher
+  if (args.contains("jsd_B")) jsd.B = get("jsd_B").cast<int>();
+  if (args.contains("jsd_weight")) jsd.weight = get("jsd_weight").cast<float>();
+  if (mode != 0 && jsd.B)
+    throw std::invalid_argument("prn: jsd_B is an argument of the forward launch (mode 0)");
+  check_jsd("prn", jsd, a.N, kd, a.labels_b);
 #undef PRN_PTR
 #undef PRN_VAL
   for (auto kv : args) {   // (every key read above exists, so any other is unknown)
@@ -649,7 +692,7 @@ static Launch mk_prn(int mode, py::dict args) {
   }
   if (!prn_supported(a.N, a.P, a.nblocks, a.classes, a.kpad))
     throw std::invalid_argument("prn: unsupported shape");
-  if (mode == 0) return [a, kd](hipStream_t s) { prn_forward(a, s, kd); };
+  if (mode == 0) return [a, kd, jsd](hipStream_t s) { prn_forward(a, s, kd, jsd); };
   if (mode == 1) return [a, wgs](hipStream_t s) { prn_backward(a, wgs, s); };
   if (mode == 2) return [a](hipStream_t s) { prn_head(a, s); };
   throw std::invalid_argument("prn: mode 0 (forward), 1 (backward) or 2 (head folds)");
@@ -1475,10 +1518,13 @@ static Launch mk_randaug(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
 // [mix_ints / (width + 1)][width + 1] int32 table of Q8 weights and the Q16 blend factor; acc
 // (0 at width 1 or for the planar kernel) the uint16 workspace [N][3 H W]; log (0: none) gets
 // [N][width][4][2].  Checked here, when the op is made.
-static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
-                        unsigned long long seed, ptr_t gstep, int width, int depth,
-                        ptr_t tables, int table_len, ptr_t mix, int mix_ints,
-                        std::vector<int> op_ids, ptr_t acc, ptr_t log) {
+// A second arity appends the three-view fan-out (fan_B source images -> N == 3 * fan_B outputs,
+// labels [N] int32 with the first fan_B given, 0: none; log and acc sized for N).
+static Launch mk_augmix_fan(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
+                            unsigned long long seed, ptr_t gstep, int width, int depth,
+                            ptr_t tables, int table_len, ptr_t mix, int mix_ints,
+                            std::vector<int> op_ids, ptr_t acc, ptr_t log, int fan_B,
+                            ptr_t labels) {
   if (op_ids.empty() || op_ids.size() > 16)
     throw std::invalid_argument("augmix: the op table needs 1..16 entries");
   if (width < 1 || width > 4) throw std::invalid_argument("augmix: width must be in 1..4");
@@ -1499,11 +1545,19 @@ static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
   am.depth = depth;
   am.acc = P<unsigned short>(acc);
   am.log = P<int>(log);
-  augmix_check(P<const void>(img), P<const void>(out), N, H, W, hwc, am);
+  augmix_check(P<const void>(img), P<const void>(out), N, H, W, hwc, am, fan_B);
   return [=](hipStream_t s) {
     augmix(P<const uint8_t>(img), P<uint8_t>(out), N, H, W, hwc, seed,
-           P<const long long>(gstep), am, s);
+           P<const long long>(gstep), am, s, fan_B, P<int>(labels));
   };
+}
+
+static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
+                        unsigned long long seed, ptr_t gstep, int width, int depth,
+                        ptr_t tables, int table_len, ptr_t mix, int mix_ints,
+                        std::vector<int> op_ids, ptr_t acc, ptr_t log) {
+  return mk_augmix_fan(img, out, N, H, W, hwc, seed, gstep, width, depth, tables, table_len, mix,
+                       mix_ints, std::move(op_ids), acc, log, 0, 0);
 }
 
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
@@ -2038,6 +2092,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "softmax_xent", mk_softmax_xent_ls);
   def_op(m, plan, "softmax_xent", mk_softmax_xent_mix);
   def_op(m, plan, "softmax_xent", mk_softmax_xent_kd);
+  def_op(m, plan, "softmax_xent", mk_softmax_xent_jsd);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce);
   def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce_k);
   def_op(m, plan, "bn_bwd_apply_acc", mk_bn_bwd_apply_acc);
@@ -2047,6 +2102,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "head_fused", mk_head_fused_ls);
   def_op(m, plan, "head_fused", mk_head_fused_mix);
   def_op(m, plan, "head_fused", mk_head_fused_kd);
+  def_op(m, plan, "head_fused", mk_head_fused_jsd);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
   def_op(m, plan, "prn_infer", mk_prn_infer);
@@ -2114,6 +2170,7 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "erase_boxes", mk_erase_boxes);
   def_op(m, plan, "randaug", mk_randaug);
   def_op(m, plan, "augmix", mk_augmix);
+  def_op(m, plan, "augmix", mk_augmix_fan);
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

@@ -179,6 +179,85 @@ __global__ void __launch_bounds__(1024) softmax_xent_kernel(DTR_XENT_PARAMS) {
 __global__ void __launch_bounds__(1024) softmax_xent_kd_kernel(DTR_XENT_PARAMS, KdArgs kd) {
   softmax_xent_body<true>(DTR_XENT_ARGS, kd);
 }
+// AugMix's Jensen-Shannon head (xent_row.h): the waves stride over TRIPLES, rows n, n + B and
+// n + 2B of N = 3B, instead of rows.  Each wave runs xent_row on its three rows from memory,
+// then jsd_rows, and writes all three gradient rows; dbias and the scalars fold as above.
+__global__ void __launch_bounds__(1024) softmax_xent_jsd_kernel(DTR_XENT_PARAMS, JsdArgs jsd) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nw = blockDim.x >> 6, B = jsd.B;
+  float* db = sh;
+  float* wl = sh + nw * ld;
+  float* wc = wl + nw;
+  float* wk = wc + nw;
+  for (int c = lane; c < ld; c += 64) db[wave * ld + c] = 0.f;
+  float lsum = 0.f, csum = 0.f, ksum = 0.f;
+  const auto none = [](int) { return 0.f; };
+  for (int n = wave; n < B; n += nw) {
+    const long o0 = (long)n * ld, o1 = (long)(n + B) * ld, o2 = (long)(n + 2 * B) * ld;
+    const float *z0 = logits + o0, *z1 = logits + o1, *z2 = logits + o2;
+    const int y = labels[n];   // the image's label, for all three views
+    const bool y_ok = y >= 0 && y < classes;
+    const auto a0 = [&](int j) { return z0[lane + 64 * j]; };
+    const auto a1 = [&](int j) { return z1[lane + 64 * j]; };
+    const auto a2 = [&](int j) { return z2[lane + 64 * j]; };
+    const XentRow r0 = xent_row<0>(a0, lane, classes, y, y_ok ? z0[y] : 0.f, eps, topk, -1, 0.f,
+                                   1.f, none, false, 0.f, 1.f);
+    const XentRow r1 = xent_row<0>(a1, lane, classes, y, y_ok ? z1[y] : 0.f, eps, topk, -1, 0.f,
+                                   1.f, none, false, 0.f, 1.f);
+    const XentRow r2 = xent_row<0>(a2, lane, classes, y, y_ok ? z2[y] : 0.f, eps, topk, -1, 0.f,
+                                   1.f, none, false, 0.f, 1.f);
+    const JsdRows t = jsd_rows<0>(a0, a1, a2, lane, classes, r0, r1, r2, jsd.weight);
+    if (lane == 0) {
+      lsum += t.row_loss(0, r0);
+      csum += r0.top1 + r1.top1 + r2.top1;
+      ksum += r0.topk + r1.topk + r2.topk;
+    }
+    for (int c = lane; c < ld; c += 64) {
+      float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+      if (c < classes) {
+        const float v0 = z0[c], v1 = z1[c], v2 = z2[c];
+        if (probs) {
+          probs[o0 + c] = r0.prob(v0);
+          probs[o1 + c] = r1.prob(v1);
+          probs[o2 + c] = r2.prob(v2);
+        }
+        const float lm = t.log_m(v0, v1, v2);
+        g0 = t.grad(0, r0, v0, lm, c == y, grad_scale);
+        g1 = t.grad(1, r1, v1, lm, c == y, grad_scale);
+        g2 = t.grad(2, r2, v2, lm, c == y, grad_scale);
+      }
+      if (dlogits) {
+        dlogits[o0 + c] = (bf16)g0;
+        dlogits[o1 + c] = (bf16)g1;
+        dlogits[o2 + c] = (bf16)g2;
+      }
+      db[wave * ld + c] += (g0 + g1) + g2;
+    }
+  }
+  if (lane == 0) {
+    wl[wave] = lsum;
+    wc[wave] = csum;
+    wk[wave] = ksum;
+  }
+  __syncthreads();
+  for (int c = tid; c < ld; c += blockDim.x) {
+    float t = 0.f;
+    for (int w = 0; w < nw; ++w) t += db[w * ld + c];
+    if (dbias && c < classes) dbias[c] = t;
+  }
+  if (tid == 0) {
+    float l = 0.f, k = 0.f, k5 = 0.f;
+    for (int w = 0; w < nw; ++w) {
+      l += wl[w];
+      k += wc[w];
+      k5 += wk[w];
+    }
+    if (loss_sum) *loss_sum = l;
+    if (correct) *correct = k;
+    if (topk_out) *topk_out = k5;
+  }
+}
 #undef DTR_XENT_PARAMS
 #undef DTR_XENT_ARGS
 
@@ -259,6 +338,82 @@ template <int VPL>
 __global__ void __launch_bounds__(256) softmax_xent_rows_kd_kernel(DTR_ROWS_PARAMS, KdArgs kd) {
   softmax_xent_rows_body<VPL, true>(DTR_ROWS_ARGS, kd);
 }
+// AugMix's Jensen-Shannon head (xent_row.h): one wave owns a TRIPLE, rows n, n + B, n + 2B of
+// N = 3B, and holds all three rows in registers (3 x VPL values per lane; 48 at 1000 classes,
+// far below the 512 a wave of a 256-thread workgroup may take), so log M_c is formed from
+// registers twice (the KL sums, then the gradients) and the logits are read once.  The grid
+// covers B triples; the workspace keeps one row per view, so the reduce kernel is unchanged.
+template <int VPL>
+__global__ void __launch_bounds__(256) softmax_xent_rows_jsd_kernel(DTR_ROWS_PARAMS, JsdArgs jsd) {
+  const int lane = threadIdx.x & 63, B = jsd.B;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= B) return;   // wave-uniform
+  const long o0 = (long)n * ld, o1 = (long)(n + B) * ld, o2 = (long)(n + 2 * B) * ld;
+  float v0[VPL], v1[VPL], v2[VPL];
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) {
+    const int c = lane + 64 * k;
+    const bool in = c < classes;
+    v0[k] = in ? logits[o0 + c] : -INFINITY;
+    v1[k] = in ? logits[o1 + c] : -INFINITY;
+    v2[k] = in ? logits[o2 + c] : -INFINITY;
+  }
+  const int y = labels[n];   // the image's label, for all three views
+  const bool y_ok = y >= 0 && y < classes;
+  const auto none = [](int) { return 0.f; };
+  const auto a0 = [&](int j) { return v0[j]; };
+  const auto a1 = [&](int j) { return v1[j]; };
+  const auto a2 = [&](int j) { return v2[j]; };
+  const XentRow r0 = xent_row<VPL>(a0, lane, classes, y, y_ok ? logits[o0 + y] : 0.f, eps, topk,
+                                   -1, 0.f, 1.f, none, false, 0.f, 1.f);
+  const XentRow r1 = xent_row<VPL>(a1, lane, classes, y, y_ok ? logits[o1 + y] : 0.f, eps, topk,
+                                   -1, 0.f, 1.f, none, false, 0.f, 1.f);
+  const XentRow r2 = xent_row<VPL>(a2, lane, classes, y, y_ok ? logits[o2 + y] : 0.f, eps, topk,
+                                   -1, 0.f, 1.f, none, false, 0.f, 1.f);
+  const JsdRows t = jsd_rows<VPL>(a0, a1, a2, lane, classes, r0, r1, r2, jsd.weight);
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) {
+    const int c = lane + 64 * k;
+    if (c >= ld) break;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    if (c < classes) {
+      if (probs) {
+        probs[o0 + c] = r0.prob(v0[k]);
+        probs[o1 + c] = r1.prob(v1[k]);
+        probs[o2 + c] = r2.prob(v2[k]);
+      }
+      const float lm = t.log_m(v0[k], v1[k], v2[k]);
+      g0 = t.grad(0, r0, v0[k], lm, c == y, grad_scale);
+      g1 = t.grad(1, r1, v1[k], lm, c == y, grad_scale);
+      g2 = t.grad(2, r2, v2[k], lm, c == y, grad_scale);
+    }
+    if (dlogits) {
+      dlogits[o0 + c] = (bf16)g0;
+      dlogits[o1 + c] = (bf16)g1;
+      dlogits[o2 + c] = (bf16)g2;
+    }
+    if (want_g) {
+      ws[o0 + c] = g0;
+      ws[o1 + c] = g1;
+      ws[o2 + c] = g2;
+    }
+  }
+  if (lane == 0) {
+    float* rs = ws + (long)N * ld;
+    rs[2 * n] = t.row_loss(0, r0);
+    rs[2 * n + 1] = r0.top1;
+    rs[2 * (n + B)] = 0.f;
+    rs[2 * (n + B) + 1] = r1.top1;
+    rs[2 * (n + 2 * B)] = 0.f;
+    rs[2 * (n + 2 * B) + 1] = r2.top1;
+    if (topk > 0) {
+      float* rk = rs + 2L * N;
+      rk[n] = r0.topk;
+      rk[n + B] = r1.topk;
+      rk[n + 2 * B] = r2.topk;
+    }
+  }
+}
 #undef DTR_ROWS_PARAMS
 
 // grid = ceil(classes / 64) blocks of 256: thread (column c, row slice q = tid / 64)
@@ -337,8 +492,14 @@ __device__ __forceinline__ void head_colsum(float (&v)[8], float (*red)[C]) {
   }
 }
 
-template <int C, int UPT, bool KD>
-__device__ __forceinline__ void head_fused_body(const HeadArgs& a, const KdArgs& kd) {
+// JSD (AugMix's Jensen-Shannon head, xent_row.h): workgroup n of N = 3B also needs the logits
+// of its two partner views.  Their pooled vectors are other workgroups' outputs, so it pools
+// the partners' activations itself, in the owner's order of sums (the same bits), and three
+// waves compute the three logits rows; it writes only its own row.  No workgroup waits for
+// another.
+template <int C, int UPT, bool KD, bool JSD = false>
+__device__ __forceinline__ void head_fused_body(const HeadArgs& a, const KdArgs& kd,
+                                                const JsdArgs& jsd = {}) {
   constexpr int G = C / 8;
   __shared__ float sc_s[C], sh_s[C], mu_s[C], rs_s[C], pool_s[C], dp_s[C], g_s[64];
   __shared__ float red[4][C], red2[4][C];
@@ -411,6 +572,75 @@ __device__ __forceinline__ void head_fused_body(const HeadArgs& a, const KdArgs&
     pool_s[tid] = (float)pb;
   }
   __syncthreads();
+  if constexpr (JSD) {
+    __shared__ float pp_s[2][C];   // the partners' pooled vectors: views view + 1, view + 2 (mod 3)
+    __shared__ float z_s[3][64];   // the triple's logits rows
+    const int Bj = jsd.B, n0 = n % Bj, view = n / Bj;
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+      const long pn = n0 + ((view + 1 + q) % 3) * Bj;
+      float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int i = 0; i < UPT; ++i) {
+        const int u = tid + i * 256;
+        if (u >= nunits) continue;
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(a.x + (pn * nunits + u) * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] += fmaxf((float)v[j] * sc[j] + sh[j], 0.f);
+      }
+      head_colsum<C>(s, red);
+      __syncthreads();
+      if (tid < C) {
+        const float t = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        pp_s[q][tid] = (float)(bf16)(t / (float)HW);
+      }
+      __syncthreads();
+    }
+    if (wave < 3) {   // wave i: view i's dense row, one class per lane
+      const float* pv = wave == view ? pool_s : pp_s[(wave - view + 2) % 3];
+      float z = -INFINITY;
+      if (lane < a.classes) {
+        float acc = 0.f;
+#pragma unroll 8
+        for (int c = 0; c < C; ++c) acc += pv[c] * w_s[c * kpad + lane];
+        z = acc + a.bias[lane];
+      }
+      z_s[wave][lane] = z;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int y = a.labels[n0];   // the image's label, for all three views
+      const int ysrc = (y >= 0 && y < a.classes) ? y : 0;
+      const float z0 = z_s[0][lane], z1 = z_s[1][lane], z2 = z_s[2][lane];
+      const auto none = [](int) { return 0.f; };
+      const XentRow r0 = xent_row<1>([&](int) { return z0; }, lane, a.classes, y, z_s[0][ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const XentRow r1 = xent_row<1>([&](int) { return z1; }, lane, a.classes, y, z_s[1][ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const XentRow r2 = xent_row<1>([&](int) { return z2; }, lane, a.classes, y, z_s[2][ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const JsdRows t = jsd_rows<1>([&](int) { return z0; }, [&](int) { return z1; },
+                                    [&](int) { return z2; }, lane, a.classes, r0, r1, r2,
+                                    jsd.weight);
+      const XentRow rv = view == 0 ? r0 : view == 1 ? r1 : r2;
+      float g = 0.f;
+      if (lane < a.classes)
+        g = t.grad(view, rv, view == 0 ? z0 : view == 1 ? z1 : z2, t.log_m(z0, z1, z2), lane == y,
+                   a.grad_scale);
+      if (lane < kpad) {
+        const bf16 gb = (bf16)g;
+        a.dlogits[(long)n * kpad + lane] = gb;
+        a.ws[(long)n * kpad + lane] = g;
+        g_s[lane] = (float)gb;
+      }
+      if (lane == 0) {
+        float* rs = a.ws + (long)a.N * kpad + 2 * n;
+        rs[0] = t.row_loss(view, rv);
+        rs[1] = rv.top1;
+        if (a.topk > 0) a.ws[(long)a.N * kpad + 2L * a.N + n] = rv.topk;
+      }
+    }
+  } else
   // ---- dense + softmax cross-entropy row (wave 0, one class per lane) ----
   if (wave == 0) {
     const int y = a.labels[n];
@@ -499,6 +729,22 @@ __global__ void __launch_bounds__(256) head_fused_kd_kernel(HeadArgs a, KdArgs k
   head_fused_body<C, UPT, true>(a, kd);
 }
 
+template <int C, int UPT>
+__global__ void __launch_bounds__(256) head_fused_jsd_kernel(HeadArgs a, JsdArgs jsd) {
+  head_fused_body<C, UPT, false, true>(a, KdArgs{}, jsd);
+}
+
+void check_jsd(const char* op, const JsdArgs& jsd, int N, const KdArgs& kd,
+               const void* labels_b) {
+  if (jsd.B == 0 && jsd.weight == 0.f) return;
+  if (jsd.B < 1 || N != 3 * jsd.B || !(jsd.weight >= 0.f && jsd.weight < INFINITY))
+    throw std::invalid_argument(std::string(op) + ": jsd needs N == 3 * jsd_B rows and a "
+                                "finite jsd_weight >= 0 (jsd_B 0 and jsd_weight 0: off)");
+  if (kd.teacher || labels_b)
+    throw std::invalid_argument(std::string(op) + ": the Jensen-Shannon head takes neither a "
+                                "teacher nor a second (mixup) label");
+}
+
 void check_kd(const char* op, const KdArgs& kd) {
   if (kd.teacher ? !(kd.alpha >= 0.f && kd.alpha <= 1.f && kd.inv_tau > 0.f) : kd.alpha != 0.f)
     throw std::invalid_argument(std::string(op) + ": kd_alpha in [0, 1] and kd_inv_tau > 0 with "
@@ -510,15 +756,18 @@ bool head_fused_supported(int N, int HW, int C, int classes, int kpad) {
          kpad <= 64 && classes <= kpad && classes >= 1;
 }
 
-void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd) {
+void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd, const JsdArgs& jsd) {
   if (!head_fused_supported(a.N, a.HW, a.C, a.classes, a.kpad))
     throw std::invalid_argument("head_fused: unsupported head shape");
   check_kd("head_fused", kd);
+  check_jsd("head_fused", jsd, a.N, kd, a.labels_b);
   const int units = a.HW * (a.C / 8);
   const dim3 grid((unsigned)a.N);
 #define DTR_HEAD_U(C_, U_)                                                                  \
   do {                                                                                      \
-    if (kd.teacher)                                                                         \
+    if (jsd.B)                                                                              \
+      hipLaunchKernelGGL((head_fused_jsd_kernel<C_, U_>), grid, dim3(256), 0, s, a, jsd);    \
+    else if (kd.teacher)                                                                    \
       hipLaunchKernelGGL((head_fused_kd_kernel<C_, U_>), grid, dim3(256), 0, s, a, kd);      \
     else                                                                                    \
       hipLaunchKernelGGL((head_fused_kernel<C_, U_>), grid, dim3(256), 0, s, a);             \
@@ -540,18 +789,23 @@ void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd) {
 void softmax_xent(const float* logits, int ld, const int* labels, int N, int classes,
                   float* loss_sum, float* correct, bf16* dlogits, float* dbias, float grad_scale,
                   float* probs, float* ws, float label_smoothing, int topk, float* topk_out,
-                  hipStream_t s, const int* labels_b, const float* mix_lam, const KdArgs& kd) {
+                  hipStream_t s, const int* labels_b, const float* mix_lam, const KdArgs& kd,
+                  const JsdArgs& jsd) {
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
     throw std::invalid_argument("softmax_xent: label_smoothing in [0, 1), topk >= 0 (> 0 with topk_out)");
   if ((labels_b == nullptr) != (mix_lam == nullptr))
     throw std::invalid_argument("softmax_xent: labels_b and mix_lam go together");
   check_kd("softmax_xent", kd);
+  check_jsd("softmax_xent", jsd, N, kd, labels_b);
   if (ws != nullptr && ld <= 1024) {
-    const dim3 grid((unsigned)((N + 3) / 4));
+    // (with JSD a wave owns a triple: B = N / 3 of them)
+    const dim3 grid((unsigned)(((jsd.B ? jsd.B : N) + 3) / 4));
     const bool want_g = dbias != nullptr;
 #define DTR_ROWS(VPL_)                                                                      \
   do {                                                                                      \
-    if (kd.teacher)                                                                         \
+    if (jsd.B)                                                                              \
+      hipLaunchKernelGGL(softmax_xent_rows_jsd_kernel<VPL_>, grid, dim3(256), 0, s, DTR_ROWS_ARGS, jsd); \
+    else if (kd.teacher)                                                                    \
       hipLaunchKernelGGL(softmax_xent_rows_kd_kernel<VPL_>, grid, dim3(256), 0, s, DTR_ROWS_ARGS, kd); \
     else                                                                                    \
       hipLaunchKernelGGL(softmax_xent_rows_kernel<VPL_>, grid, dim3(256), 0, s, DTR_ROWS_ARGS); \
@@ -567,7 +821,11 @@ void softmax_xent(const float* logits, int ld, const int* labels, int N, int cla
   }
   const int threads = 1024, nw = threads / 64;
   const size_t lds = ((size_t)nw * ld + 3 * nw) * sizeof(float);
-  if (kd.teacher)
+  if (jsd.B)
+    hipLaunchKernelGGL(softmax_xent_jsd_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels,
+                       N, classes, loss_sum, correct, dlogits, dbias, grad_scale, probs,
+                       label_smoothing, topk, topk_out, labels_b, mix_lam, jsd);
+  else if (kd.teacher)
     hipLaunchKernelGGL(softmax_xent_kd_kernel, dim3(1), dim3(threads), lds, s, logits, ld, labels,
                        N, classes, loss_sum, correct, dlogits, dbias, grad_scale, probs,
                        label_smoothing, topk, topk_out, labels_b, mix_lam, kd);

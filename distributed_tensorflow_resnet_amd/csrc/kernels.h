@@ -277,6 +277,16 @@ struct KdArgs {
   float inv_tau = 1.f;
 };
 void check_kd(const char* op, const KdArgs& kd);   // invalid_argument on a bad triple
+// AugMix's Jensen-Shannon term (xent_row.h): rows n, n + B, n + 2B of N = 3B are one image's
+// clean view and two AugMix views (B = 0: none).  Like KdArgs a trailing argument of the
+// loss-head launches and a kernel argument of their `_jsd` instantiations ONLY; not combined
+// with a teacher or with mixup's second label.
+struct JsdArgs {
+  int B = 0;
+  float weight = 0.f;
+};
+// invalid_argument unless off, or N == 3B, weight finite and >= 0, no teacher, no mixup pair
+void check_jsd(const char* op, const JsdArgs& jsd, int N, const KdArgs& kd, const void* labels_b);
 
 struct PrnArgs {
   const PrnBlock* blocks;
@@ -339,7 +349,8 @@ std::vector<uint32_t> device_cu_mask();
 size_t prn_lds_bytes();
 int prn_bar_words();   // barrier / readiness / queue words of PrnArgs::bar (zeroed every step)
 int prn_acc_rep();   // fp64 accumulator replicas per BatchNorm of the persistent kernels
-void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd = {});
+void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd = {},
+                 const JsdArgs& jsd = {});
 void prn_backward(const PrnArgs& a, int wgrad_wgs, hipStream_t s);
 // the head's batch folds (loss, precision, dense bias + weight gradients), one workgroup
 void prn_head(const PrnArgs& a, hipStream_t s);
@@ -506,7 +517,8 @@ struct HeadArgs {
   const float* mix_lam = nullptr;   // (both or neither; xent_row.h)
 };
 bool head_fused_supported(int N, int HW, int C, int classes, int kpad);
-void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd = {});
+void head_fused(const HeadArgs& a, hipStream_t s, const KdArgs& kd = {},
+                const JsdArgs& jsd = {});
 // topk_out (may be nullptr): the sum of the workspace's in-top-k flags
 void softmax_xent_reduce(const float* ws, int ld, int N, int classes, float* loss_sum,
                          float* correct, float* dbias, float* topk_out, hipStream_t s);
@@ -516,7 +528,8 @@ void softmax_xent(const float* logits, int ld, const int* labels, int N, int cla
                   float grad_scale, float* probs, float* ws, float label_smoothing, int topk,
                   float* topk_out, hipStream_t s, const int* labels_b = nullptr,
                   const float* mix_lam = nullptr,   // mixup: [N] partner labels, [N] lam (xent_row.h)
-                  const KdArgs& kd = {});           // distillation: [N][ld] teacher logits
+                  const KdArgs& kd = {},            // distillation: [N][ld] teacher logits
+                  const JsdArgs& jsd = {});         // AugMix JSD: N = 3B rows in triples
 long softmax_xent_ws_floats(int N, int ld);
 
 // ---- max pool (ImageNet stem) ----
@@ -580,10 +593,13 @@ struct AugMix {
 };
 // the argument checks of augmix (std::invalid_argument), for plan recording; for hwc it also
 // asks, once per process, for the kernel's more than 64 KB of LDS
+// fan_B > 0: the three-view fan-out for the Jensen-Shannon loss -- `in` holds fan_B images,
+// N == 3 * fan_B outputs, `labels` ([N], may be null) gets labels[p] = labels[p % fan_B]
 void augmix_check(const void* in, const void* out, int N, int H, int W, int hwc,
-                  const AugMix& am);
+                  const AugMix& am, int fan_B = 0);
 void augmix(const uint8_t* in, uint8_t* out, int N, int H, int W, int hwc,
-            unsigned long long seed, const long long* gstep, const AugMix& am, hipStream_t s);
+            unsigned long long seed, const long long* gstep, const AugMix& am, hipStream_t s,
+            int fan_B = 0, int* labels = nullptr);
 
 // ---- flat-parameter descriptors ----
 struct ParamSeg {          // one trainable tensor inside the flat buffers

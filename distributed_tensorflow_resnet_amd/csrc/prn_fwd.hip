@@ -129,9 +129,15 @@ __device__ __forceinline__ bool block_fwd(Ctx& x, bf16x4 (&xr)[8], int bi_next,
 // KD: the head reads a teacher row (distillation, xent_row.h) through `kd`, an argument of
 // the teacher kernel alone: the launch without a teacher has the arguments and the code it
 // always had.
-template <int P, bool KD = false>
+// JSD: AugMix's Jensen-Shannon head (xent_row.h) through `jsd`, likewise an argument of the
+// `_jsd` kernel alone.  Behind the head barrier pool_acc is complete for EVERY image, so slice
+// 0 of image p of N = 3B reads its two partners' 64 pooled sums, rounds them to bf16 as their
+// owners do, and waves 0..2 compute the triple's three logits rows from the dense weights
+// already staged; it writes its own row only.  No barrier, no atomic, nothing before the head
+// differs.
+template <int P, bool KD = false, bool JSD = false>
 __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem,
-                                                 const KdArgs& kd = {}) {
+                                                 const KdArgs& kd = {}, const JsdArgs& jsd = {}) {
   Ctx x;
   x.a = &a;
   x.m = carve(smem);
@@ -231,6 +237,71 @@ __device__ __forceinline__ void prn_forward_body(const PrnArgs& a, char* smem,
     a.pooled[(long)x.img * 64 + tid] = pb;
     pool_s[tid] = (float)pb;
   }
+  if constexpr (JSD) {
+    float* pp = x.m.red;         // [0, 128): the partners' pooled vectors, views view + 1, + 2 (mod 3)
+    float* z_s = x.m.red + 128;  // [3][64]: the triple's logits rows
+    const int Bj = jsd.B, n0 = x.img % Bj, view = x.img / Bj;
+    if (tid >= 64 && tid < 192) {
+      const int q = (tid >> 6) - 1, c = tid & 63;
+      const long pn = n0 + ((view + 1 + q) % 3) * Bj;
+      pp[q * 64 + c] = (float)(bf16)((float)ld_sc1_d(a.pool_acc + pn * 64 + c) / 64.f);
+    }
+    __syncthreads();
+    if (x.wave < 3) {   // wave i: view i's dense row, one class per lane
+      const int lane = x.lane;
+      const float* pv = x.wave == view ? pool_s : pp + ((x.wave - view + 2) % 3) * 64;
+      float z = -INFINITY;
+      if (lane < a.classes) {
+        float acc = 0.f;
+#pragma unroll 8
+        for (int c = 0; c < 64; ++c) acc += pv[c] * wd[c * a.kpad + lane];
+        z = acc + a.dense_b[lane];
+      }
+      z_s[x.wave * 64 + lane] = z;
+    }
+    __syncthreads();
+    if (x.wave == 0) {
+      const int lane = x.lane;
+      const int y = a.labels[n0];   // the image's label, for all three views
+      const int ysrc = (y >= 0 && y < a.classes) ? y : 0;
+      const float z0 = z_s[lane], z1 = z_s[64 + lane], z2 = z_s[128 + lane];
+      const auto none = [](int) { return 0.f; };
+      const XentRow r0 = xent_row<1>([&](int) { return z0; }, lane, a.classes, y, z_s[ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const XentRow r1 = xent_row<1>([&](int) { return z1; }, lane, a.classes, y, z_s[64 + ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const XentRow r2 = xent_row<1>([&](int) { return z2; }, lane, a.classes, y, z_s[128 + ysrc],
+                                     a.label_smoothing, a.topk, -1, 0.f, 1.f, none, false, 0.f, 1.f);
+      const JsdRows t = jsd_rows<1>([&](int) { return z0; }, [&](int) { return z1; },
+                                    [&](int) { return z2; }, lane, a.classes, r0, r1, r2,
+                                    jsd.weight);
+      const XentRow rv = view == 0 ? r0 : view == 1 ? r1 : r2;
+      float g = 0.f;
+      if (lane < a.classes)
+        g = t.grad(view, rv, view == 0 ? z0 : view == 1 ? z1 : z2, t.log_m(z0, z1, z2), lane == y,
+                   a.grad_scale);
+      if (lane < a.kpad) {
+        const bf16 gb = (bf16)g;
+        a.dlogits[(long)x.img * a.kpad + lane] = gb;
+        a.ws[(long)x.img * a.kpad + lane] = g;
+        pool_s[128 + lane] = (float)gb;
+      }
+      if (lane == 0) {
+        float* rs = a.ws + (long)a.N * a.kpad + 2 * x.img;
+        rs[0] = t.row_loss(view, rv);
+        rs[1] = rv.top1;
+        if (a.topk > 0) a.ws[(long)a.N * a.kpad + 2L * a.N + x.img] = rv.topk;
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {
+      float d = 0.f;
+      for (int k = 0; k < a.kpad; ++k) d += pool_s[128 + k] * wd[tid * a.kpad + k];
+      const float db = (float)(bf16)d;
+      a.dpool[(long)x.img * 64 + tid] = (float)(bf16)(db * (1.f / 64.f));
+    }
+    return;
+  }
   __syncthreads();
   if (x.wave == 0) {
     const int lane = x.lane;
@@ -290,6 +361,13 @@ __global__ void __launch_bounds__(PT, 1) prn_fwd_kd_kernel(PrnArgs a, KdArgs kd)
   prn_forward_body<P, true>(a, smem, kd);
 }
 
+// the same forward with the Jensen-Shannon head
+template <int P>
+__global__ void __launch_bounds__(PT, 1) prn_fwd_jsd_kernel(PrnArgs a, JsdArgs jsd) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  prn_forward_body<P, false, true>(a, smem, KdArgs{}, jsd);
+}
+
 // ---- host ------------------------------------------------------------------------------
 long long* g_prn_probe = nullptr;
 void prn_set_probe(long long* p) { g_prn_probe = p; }
@@ -324,7 +402,8 @@ long prn_fwd_resident(int P) {
                   : resident_blocks(prn_fwd_kernel<4>, LDS_TOTAL);
 }
 
-void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd) {
+void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd, const JsdArgs& jsd) {
+  check_jsd("prn_forward", jsd, a.N, kd, a.labels_b);
   if (!prn_supported(a.N, a.P, a.nblocks, a.classes, a.kpad) || a.N * a.P > cu_count())
     throw std::invalid_argument("prn_forward: unsupported shape (N x P <= CUs, 3n blocks, <= 64 classes)");
   PrnArgs b = a;
@@ -332,7 +411,9 @@ void prn_forward(const PrnArgs& a, hipStream_t s, const KdArgs& kd) {
   b.shards = prn_shards(a.N, a.P);
 #define DTR_PRN_FWD(P_)                                                                    \
   if (a.P == P_) {                                                                         \
-    if (kd.teacher)                                                                        \
+    if (jsd.B)                                                                             \
+      hipLaunchKernelGGL(prn_fwd_jsd_kernel<P_>, dim3(a.N * P_), dim3(PT), LDS_TOTAL, s, b, jsd); \
+    else if (kd.teacher)                                                                   \
       hipLaunchKernelGGL(prn_fwd_kd_kernel<P_>, dim3(a.N * P_), dim3(PT), LDS_TOTAL, s, b, kd); \
     else                                                                                   \
       hipLaunchKernelGGL(prn_fwd_kernel<P_>, dim3(a.N * P_), dim3(PT), LDS_TOTAL, s, b);      \

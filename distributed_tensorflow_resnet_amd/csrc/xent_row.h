@@ -31,6 +31,19 @@
 // never the log of a probability, and a class whose q_c underflowed to 0 adds exactly 0.
 // Only classes < K of either row are read.  A row without a teacher (wave-uniform) takes
 // none of this and is bit-for-bit the row above.
+//
+// AugMix's Jensen-Shannon consistency term (Hendrycks et al. 2020) couples THREE rows, the
+// clean view and two AugMix views of one image (rows n, n + B, n + 2B of N = 3B): with
+// l_i = z_i - lse(z_i), p_i = exp(l_i), weight w and L_h / t_c the hard loss and target above,
+//   log M_c  = logsumexp_i(l_ic) - log 3          (max-shifted over the three views)
+//   KL_i     = sum_c p_ic * (l_ic - log M_c)      (a class with p_ic == 0 adds exactly 0)
+//   JSD      = (KL_0 + KL_1 + KL_2) / 3
+//   triple's loss = L_h(z_0, y) + w * JSD,   reported as 3 x that by the clean row, 0 by the others
+//   g_ic     = ([i == 0] * 3 * (p_0c - t_c) + w * p_ic * (l_ic - log M_c - KL_i)) * grad_scale
+// (grad_scale is 1 / N, so the clean view's hard term weighs 1 / B.)  log M_c replaces the
+// paper's clamp of M to [1e-7, 1]: it is never the log of a probability.  Every row keeps its
+// own top-1 / top-k flags against the image's label.  The hard part of each row is xent_row;
+// jsd_rows is a second step over the three rows' accessors, shared by every `_jsd` kernel.
 #pragma once
 
 #include "common.h"
@@ -39,6 +52,7 @@ namespace dtr {
 
 struct XentRow {
   float lse;             // logsumexp of the valid classes
+  float mx, lgs;         // its two parts, row max and log of the shifted sum (lse = mx + lgs)
   float loss;            // the row's loss (0 at eps == 0 for an out-of-range label, as before)
   float top1, topk;      // 0 / 1 flags (topk is 0 when k == 0)
   float t_miss;          // target of a class that is no label of the row: eps / K
@@ -59,6 +73,10 @@ struct XentRow {
     if (!kd) return hard * grad_scale;
     const float soft = __expf(z * inv_tau - lse_s) - __expf(t * inv_tau - lse_t);
     return ((1.f - alpha) * hard + a_tau * soft) * grad_scale;
+  }
+  // t_c alone (the JSD heads form p_c themselves)
+  __device__ __forceinline__ float target(bool hit, bool hit_b) const {
+    return t_miss + (hit ? w_hit : 0.f) + (hit_b ? w_hit_b : 0.f);
   }
 };
 
@@ -97,7 +115,9 @@ __device__ __forceinline__ XentRow xent_row(Z z, int lane, int classes, int y, f
   for (int j = 0; j < nv; ++j)
     if (lane + 64 * j < classes) se += __expf(z(j) - mx);
   se = wave_sum(se);
-  r.lse = mx + __logf(se);
+  r.mx = mx;
+  r.lgs = __logf(se);
+  r.lse = mx + r.lgs;
   const bool y_ok = y >= 0 && y < classes;
   r.t_miss = eps / (float)classes;
   r.w_hit = 1.f - eps;
@@ -177,6 +197,73 @@ __device__ __forceinline__ XentRow xent_row(Z z, int lane, int classes, int y, f
     r.loss = (1.f - alpha) * r.loss + (r.a_tau / inv_tau) * kl;
   }
   return r;
+}
+
+// The Jensen-Shannon step over a triple (header comment).  mx[i], lgs[i]: view i's row max
+// and the log of its shifted sum.  A log-probability is (z - mx) - lgs, not z - lse: with
+// logits of magnitude 100 and more, lse's own rounding (half an ulp of 128 and up) would
+// enter every l_ic and, times w, the gradient.
+struct JsdRows {
+  float mx[3], lgs[3], kl[3], w;
+  __device__ __forceinline__ float logp(int i, float z) const {
+    return (z - sel(mx, i)) - sel(lgs, i);
+  }
+  __device__ __forceinline__ float jsd() const { return (kl[0] + kl[1] + kl[2]) * (1.f / 3.f); }
+  // log M_c from the class's three logits (NaN only where all three p underflowed to 0 with
+  // l = -inf; no caller uses it there)
+  __device__ __forceinline__ float log_m(float z0, float z1, float z2) const {
+    const float l0 = logp(0, z0), l1 = logp(1, z1), l2 = logp(2, z2);
+    const float m = fmaxf(l0, fmaxf(l1, l2));
+    return m + __logf(__expf(l0 - m) + __expf(l1 - m) + __expf(l2 - m)) - 1.09861229f;
+  }
+  // w * p_ic * (l_ic - log M_c - KL_i): view i's soft gradient of a class, before grad_scale
+  // (`i` may be a run-time view: a choice among three values, not an indexed read)
+  __device__ __forceinline__ float soft(int i, float z, float lm) const {
+    const float l = logp(i, z), p = __expf(l);
+    return p > 0.f ? w * p * (l - lm - sel(kl, i)) : 0.f;
+  }
+  static __device__ __forceinline__ float sel(const float (&a)[3], int i) {
+    return i == 0 ? a[0] : i == 1 ? a[1] : a[2];
+  }
+  // view i's whole gradient of a class; `r` is that view's XentRow
+  __device__ __forceinline__ float grad(int i, const XentRow& r, float z, float lm, bool hit,
+                                        float grad_scale) const {
+    const float h = i == 0 ? 3.f * (__expf(logp(0, z)) - r.target(hit, false)) : 0.f;
+    return (h + soft(i, z, lm)) * grad_scale;
+  }
+  // what view i's row reports as its loss
+  __device__ __forceinline__ float row_loss(int i, const XentRow& r) const {
+    return i == 0 ? 3.f * (r.loss + w * jsd()) : 0.f;
+  }
+};
+
+// `z0(j)`, `z1(j)`, `z2(j)`: the three views' accessors, as xent_row's `z`; `r0..r2` their
+// XentRows.  Per-lane sums in class order, then the xor-shuffle fold, as everywhere here.
+template <int VPL, class Z0, class Z1, class Z2>
+__device__ __forceinline__ JsdRows jsd_rows(Z0 z0, Z1 z1, Z2 z2, int lane, int classes,
+                                            const XentRow& r0, const XentRow& r1,
+                                            const XentRow& r2, float w) {
+  const int nv = VPL > 0 ? VPL : (classes + 63) >> 6;
+  JsdRows t;
+  t.mx[0] = r0.mx, t.mx[1] = r1.mx, t.mx[2] = r2.mx;
+  t.lgs[0] = r0.lgs, t.lgs[1] = r1.lgs, t.lgs[2] = r2.lgs;
+  t.w = w;
+  float k0 = 0.f, k1 = 0.f, k2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < nv; ++j)
+    if (lane + 64 * j < classes) {
+      const float a = z0(j), b = z1(j), c = z2(j);
+      const float lm = t.log_m(a, b, c);
+      const float l0 = t.logp(0, a), l1 = t.logp(1, b), l2 = t.logp(2, c);
+      const float p0 = __expf(l0), p1 = __expf(l1), p2 = __expf(l2);
+      if (p0 > 0.f) k0 += p0 * (l0 - lm);
+      if (p1 > 0.f) k1 += p1 * (l1 - lm);
+      if (p2 > 0.f) k2 += p2 * (l2 - lm);
+    }
+  t.kl[0] = wave_sum(k0);
+  t.kl[1] = wave_sum(k1);
+  t.kl[2] = wave_sum(k2);
+  return t;
 }
 
 }  // namespace dtr

@@ -146,3 +146,21 @@ def augmix_batch(batch_u8, layout: str, seed: int, step: int, width: int = 3, de
     out = out.transpose(0, 3, 1, 2) if layout == "chw" else out
     return np.ascontiguousarray(out), log
 
+
+def augmix_fanout(batch_u8, labels, layout: str, seed: int, step: int, width: int = 3,
+                  depth: int = -1, severity: int = 3, op_table=None, tables=None,
+                  mix_table=None, alpha: float = 1.0):
+    """AugMix's three views for the Jensen-Shannon loss: B images and labels ->
+    ([3B, ...] uint8, [3B] labels, [3B, width, 4, 2] log).  Position p holds source image
+    p % B: p < B is a copy (the clean view; its log rows are -1), p >= B runs the chains of
+    augmix_batch keyed on the OUTPUT position p, so the two views of one image differ."""
+    x, y = np.asarray(batch_u8), np.asarray(labels)
+    B = len(x)
+    if len(y) != B:
+        raise ValueError(f"{B} images but {len(y)} labels")
+    rep = np.concatenate([x, x, x])
+    # augmix_batch keys image n of its batch on n: positions 0..3B-1, of which B.. are kept
+    out, log = augmix_batch(rep, layout, seed, step, width, depth, severity, op_table, tables,
+                            mix_table, alpha)
+    out[:B], log[:B] = x, -1
+    return out, np.concatenate([y, y, y]), log

@@ -19,7 +19,7 @@ import torch
 from ..data.cifar import (MIXUP_TABLE_LEN, augment_cpu, cutmix_draw, cutmix_table, cutmix_thresh,
                           erase_draw, erase_noise_index, erase_noise_table, erase_table,
                           erase_thresh, mixup_draw, mixup_table)
-from ..data.augmix import augmix_batch, augmix_tables
+from ..data.augmix import augmix_batch, augmix_fanout, augmix_tables
 from ..data.randaug import randaug_batch
 from ..models.params import ParamStore
 from ..models.resnet_torch import TorchResNet
@@ -29,10 +29,11 @@ from ..parallel.dist import local_device_index
 from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_to_lion,
                                 tf_to_rmsprop, tf_to_state)
 from .distill import TorchTeacher, check_distill, soft_loss
+from .jsd import jsd_loss
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug,
-                     check_augmix)
+                     check_augmix, check_augmix_jsd)
 
 
 class GPUBackend:
@@ -185,7 +186,17 @@ class CPUBackend:
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
                  augmix_ops: str = "augmix", distill_alpha: float = 0.0,
-                 distill_temperature: float = 4.0, distill_teacher=None):
+                 distill_temperature: float = 4.0, distill_teacher=None,
+                 augmix_jsd: bool = False, augmix_jsd_weight: float = 12.0):
+        # AugMix's Jensen-Shannon loss (train/jsd.py, the formulas of csrc/xent_row.h): the
+        # model runs on 3 * batch_size rows, the clean batch and two AugMix views of it from
+        # data/augmix.py's fan-out; batch_size keeps counting loaded images
+        self.augmix_jsd, self.augmix_jsd_weight = check_augmix_jsd(
+            augmix_jsd, augmix_jsd_weight, augmix_width, mixup_alpha, cutmix_alpha, erase_prob,
+            distill_alpha)
+        self.jsd_B = batch_size if self.augmix_jsd else 0
+        if self.augmix_jsd:
+            batch_size, global_batch = 3 * batch_size, 3 * global_batch if global_batch else None
         # knowledge distillation, csrc/xent_row.h's soft term in fp32 torch (train/distill.py):
         # the teacher a TorchResNet in eval mode on the batch the student sees (0 = off)
         self.distill_alpha, self.distill_tau = check_distill(
@@ -360,7 +371,13 @@ class CPUBackend:
                     images.numpy(), "chw", self.data_seed, self.step_count,
                     self.randaug_num_ops, self.randaug_magnitude, self.randaug_op_ids)
                 images = torch.from_numpy(aug)
-            if self.augmix_width > 0:
+            if self.jsd_B:   # B records -> 3B views and labels, keyed by output position
+                aug, lab, self._augmix_state = augmix_fanout(
+                    images.numpy(), labels.numpy(), "chw", self.data_seed, self.step_count,
+                    self.augmix_width, self.augmix_depth, self.augmix_severity,
+                    self.augmix_op_ids, mix_table=self.augmix_mix)
+                images, labels = torch.from_numpy(aug), torch.from_numpy(lab)
+            elif self.augmix_width > 0:
                 aug, self._augmix_state = augmix_batch(
                     images.numpy(), "chw", self.data_seed, self.step_count, self.augmix_width,
                     self.augmix_depth, self.augmix_severity, self.augmix_op_ids,
@@ -404,7 +421,11 @@ class CPUBackend:
             x = self._erase(x)
             self.last_input = x
         logits = m(x, True)
-        xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing, **mix)
+        if self.jsd_B:   # the clean views' hard loss + w * JSD, a mean over the B images
+            xent = jsd_loss(logits, self._y, self.jsd_B, self.augmix_jsd_weight,
+                            self.label_smoothing)
+        else:
+            xent, _ = m.loss(logits, self._y, self.wd, self.label_smoothing, **mix)
         if self.teacher is not None:   # smoothing and mixup stay in the hard term
             a, self._teacher_logits = self.distill_alpha, self.teacher.logits(x)
             xent = (1.0 - a) * xent + a * soft_loss(logits, self._teacher_logits,
@@ -757,6 +778,8 @@ class CPUBackend:
                                     (self.N * self.spec.image_h * self.spec.image_w))
         if self.augmix_width > 0:
             m["augmix"] = f"w{self.augmix_width}-s{self.augmix_severity}"
+            if self.jsd_B:
+                m["augmix"] += f"-jsd{self.augmix_jsd_weight:g}"
         return m
 
     def synchronize(self):
@@ -839,7 +862,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
                  augmix_ops: str = "augmix", distill_alpha: float = 0.0,
-                 distill_temperature: float = 4.0, distill_teacher=None):
+                 distill_temperature: float = 4.0, distill_teacher=None,
+                 augmix_jsd: bool = False, augmix_jsd_weight: float = 12.0):
     """device: gpu | cpu | auto.  ``resident`` (GPU, input_mode='cifar_resident'): the
     (images, labels) of the split the engine keeps on the device."""
     if device == "auto":
@@ -863,6 +887,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  augmix_ops=augmix_ops)
     erase.update(distill_alpha=distill_alpha, distill_temperature=distill_temperature,
                  distill_teacher=distill_teacher)
+    erase.update(augmix_jsd=augmix_jsd, augmix_jsd_weight=augmix_jsd_weight)
     if device == "gpu":
         from .engine import Engine
 

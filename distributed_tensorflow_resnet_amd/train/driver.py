@@ -266,7 +266,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            muon_tiled=flags.muon_tiled,
                            distill_alpha=flags.distill_alpha,
                            distill_temperature=flags.distill_temperature,
-                           distill_teacher=teacher)
+                           distill_teacher=teacher,
+                           augmix_jsd=flags.augmix_jsd,
+                           augmix_jsd_weight=flags.augmix_jsd_weight)
     eng = getattr(backend, "engine", None)
     if fault_reason and eng is not None and not eng.persist:
         eng.persist_reason = fault_reason

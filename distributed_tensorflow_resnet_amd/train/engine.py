@@ -54,7 +54,7 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPTW_DTYPE, SEG_DTYPE, WGD_DTYPE, _ceil, _pow2ceil, lars_tables,
                      OPT_FUSED_CLIP_REASON, CLIP_CHUNK, MIXUP_INPUT_MODES, check_clip_grad_norm,
                      check_mixup_alpha, check_cutmix_alpha, check_mix_switch_prob, check_erase,
-                     check_randaug, check_augmix,
+                     check_randaug, check_augmix, check_augmix_jsd,
                      lars_trust_summary, opt_tile, param_segments, sgd_tiles_work,
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
@@ -154,13 +154,26 @@ class Engine:
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
                  augmix_ops: str = "augmix", distill_alpha: float = 0.0,
-                 distill_temperature: float = 4.0, distill_teacher=None):
+                 distill_temperature: float = 4.0, distill_teacher=None,
+                 augmix_jsd: bool = False, augmix_jsd_weight: float = 12.0):
         # global gradient-norm clipping (csrc/clip.hip): 0 = off (nothing allocated, no op
         # recorded), inf = the norm is only measured
         self.clip_grad_norm = check_clip_grad_norm(clip_grad_norm, optimizer)
         self.nat = native(required=True)
         tune.validate(k for k, *_ in self.nat.tune_table())
         self.spec = spec
+        # AugMix's Jensen-Shannon loss (csrc/xent_row.h): ``batch_size`` keeps counting loaded
+        # images, the engine is built for N = 3 * batch_size rows -- rows n, n + B, n + 2B are
+        # image n's clean view and two AugMix views.  The host fills the first B slots of the
+        # uint8 batch and of the labels; the fan-out launch (csrc/augmix.hip) writes the rest in
+        # front of the input launch, and whichever head the plan records couples the triples.
+        # BatchNorm sees all 3B rows.  Off: jsd_B 0, every plan op for op the same.
+        self.augmix_jsd, self.augmix_jsd_weight = check_augmix_jsd(
+            augmix_jsd, augmix_jsd_weight, augmix_width, mixup_alpha, cutmix_alpha, erase_prob,
+            distill_alpha)
+        self.jsd_B = batch_size if self.augmix_jsd else 0
+        if self.augmix_jsd:
+            batch_size, global_batch = 3 * batch_size, 3 * global_batch if global_batch else None
         self.N = batch_size
         self.device = torch.device(device or "cuda")
         self.dist = dist_ctx
@@ -466,14 +479,26 @@ class Engine:
         # why the persistent step is off ("" = on); never on a GPU shared by several ranks
         # (its grids need every CU to themselves), and the same choice on EVERY rank (the
         # two plans issue different collectives)
-        if pm == 0:
-            reason = "tune persist=0"
-        elif pm != 1 and self.N > _persist.AUTO_MAX_BATCH:
-            reason = f"per-rank batch {self.N} > {_persist.AUTO_MAX_BATCH} (auto)"
-        elif gpu_shared_by_ranks(self.dist, didx):
-            reason = "GPU shared by several ranks"
-        else:
-            reason = _persist.check(self)
+        def persist_reason(rows: int) -> str:
+            if pm == 0:
+                return "tune persist=0"
+            if pm != 1 and rows > _persist.AUTO_MAX_BATCH:
+                return f"per-rank batch {rows} > {_persist.AUTO_MAX_BATCH} (auto)"
+            if gpu_shared_by_ranks(self.dist, didx):
+                return "GPU shared by several ranks"
+            n, self.N = self.N, rows   # (check reads the engine's batch)
+            try:
+                return _persist.check(self)
+            finally:
+                self.N = n
+
+        reason = persist_reason(self.N)
+        if self.augmix_jsd and reason and not persist_reason(self.jsd_B):
+            # B rows would take the persistent step, the 3B rows of the triples cannot: no
+            # silent change of path
+            raise ValueError(f"augmix_jsd: batch_size {self.jsd_B} selects the persistent step, "
+                             f"but its 3 x {self.jsd_B} rows do not fit it ({reason}); lower "
+                             "batch_size or choose the per-layer step (tune persist=0)")
         if self.dist is not None and self.dist.active and not self.dist._agree(reason == ""):
             reason = reason or "another rank cannot run the persistent step"
         self.persist_reason = reason
@@ -1000,8 +1025,11 @@ class Engine:
 
     def head_tail_args(self) -> tuple:
         """Every trailing argument of the loss heads: the mixup pair and, with distillation
-        on, behind it (null when mixup is off) the teacher logits, alpha and 1 / tau."""
+        on, behind it (null when mixup is off) the teacher logits, alpha and 1 / tau; with
+        the Jensen-Shannon loss on (never with either), nulls for those and (B, weight)."""
         mix = self.mix_head_ptrs()
+        if self.jsd_B:
+            return (0, 0, 0, 0.0, 1.0, self.jsd_B, self.augmix_jsd_weight)
         if self.teacher is None:
             return mix
         return (mix or (0, 0)) + (self.teacher.logits.data_ptr(), self.distill_alpha,
@@ -1229,13 +1257,16 @@ class Engine:
         """Copy a host/device batch into the static input buffers."""
         self._no_host_input("set_batch")
         if self.input_mode in ("cifar_u8", "imagenet_u8"):
-            self.img_u8.copy_(images, non_blocking=True)
+            # (Jensen-Shannon loss: the first B slots; the fan-out launch writes the rest)
+            (self.img_u8[:self.jsd_B] if self.jsd_B else self.img_u8).copy_(
+                images, non_blocking=True)
         else:
             x = images
             if x.dim() == 4 and tuple(x.shape) != tuple(self.x_in.shape):
                 x = self._stem_input(x)
             self.x_in.copy_(x, non_blocking=True)
-        self.labels.copy_(labels.to(torch.int32), non_blocking=True)
+        (self.labels[:self.jsd_B] if self.jsd_B else self.labels).copy_(
+            labels.to(torch.int32), non_blocking=True)
 
     def _no_host_input(self, what: str):
         if self.input_mode == "cifar_resident":
@@ -1312,6 +1343,8 @@ class Engine:
                                     (self.N * self.spec.image_h * self.spec.image_w))
         if self.augmix_width > 0:
             m["augmix"] = f"w{self.augmix_width}-s{self.augmix_severity}"
+            if self.jsd_B:   # (cross_entropy is the clean views' loss + w * JSD; precision
+                m["augmix"] += f"-jsd{self.augmix_jsd_weight:g}"   # is over all three views)
         if self.teacher is not None:   # (cross_entropy and cost are the combined loss)
             m["distill_alpha"], m["distill_temperature"] = self.distill_alpha, self.distill_tau
         return m

@@ -506,6 +506,33 @@ def check_randaug(num_ops=0, magnitude=9, ops="all") -> tuple:
     return num_ops, magnitude, ids
 
 
+def check_augmix_jsd(jsd=False, weight=12.0, augmix_width=0, mixup_alpha=0.0, cutmix_alpha=0.0,
+                     erase_prob=0.0, distill_alpha=0.0):
+    """--augmix_jsd / --augmix_jsd_weight as both backends take them -> (on, weight).  The
+    Jensen-Shannon term needs AugMix's views and is not composed with the other batch
+    transforms or with a teacher: each would have to say what it does to a triple."""
+    try:
+        weight = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"augmix_jsd_weight must be a number, got {weight!r}") from None
+    if not 0.0 <= weight < float("inf"):   # NaN included
+        raise ValueError(f"augmix_jsd_weight must be finite and >= 0, got {weight!r}")
+    if not jsd:
+        return False, weight
+    if int(augmix_width) < 1:
+        raise ValueError("augmix_jsd needs augmix_width > 0: the loss compares the clean image "
+                         "with two AugMix views of it")
+    for name, v, why in (
+            ("mixup_alpha", mixup_alpha, "a mixed row has two labels and no clean view"),
+            ("cutmix_alpha", cutmix_alpha, "a pasted box would differ between the three views"),
+            ("erase_prob", erase_prob, "an erased box would differ between the three views"),
+            ("distill_alpha", distill_alpha, "the loss heads take a teacher row or a triple, "
+                                             "not both")):
+        if float(v) > 0:
+            raise ValueError(f"augmix_jsd cannot be combined with {name} > 0: {why}")
+    return True, weight
+
+
 def check_augmix(width=0, depth=-1, severity=3, alpha=1.0, ops="augmix",
                  randaug_num_ops=0) -> tuple:
     """--augmix_width and its sub-flags as both backends take them -> (width, depth, severity,

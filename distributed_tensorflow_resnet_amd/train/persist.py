@@ -415,6 +415,8 @@ class PersistStep:
             # the teacher logits, alpha, 1 / tau; the other launches' arguments stay as they are
             mix.update(teacher=eng.teacher.logits.data_ptr(), kd_alpha=eng.distill_alpha,
                        kd_inv_tau=1.0 / eng.distill_tau)
+        if eng.jsd_B and fwd:   # the Jensen-Shannon head: likewise the forward's alone
+            mix.update(jsd_B=eng.jsd_B, jsd_weight=eng.augmix_jsd_weight)
         return dict(
             **mix, blocks=self.block_dev.data_ptr(), nblocks=self.nblocks, bns=self.bn_dev.data_ptr(),
             x_in=eng.x_in.data_ptr(), stem_w=eng.convs[spec.stem.name].ohwi, pool_acc=pool_ptr,

@@ -791,7 +791,9 @@ class StepRecorder:
                 e.data_seed, e.gstep.data_ptr(), e.augmix_width, e.augmix_depth,
                 e.augmix_tab.data_ptr(), e.augmix_tab.numel(), e.augmix_mix.data_ptr(),
                 e.augmix_mix.numel(), list(e.augmix_op_ids),
-                0 if e.augmix_acc is None else e.augmix_acc.data_ptr(), e.augmix_log.data_ptr())
+                0 if e.augmix_acc is None else e.augmix_acc.data_ptr(), e.augmix_log.data_ptr(),
+                # Jensen-Shannon loss: the first B slots fan out into N = 3B views and labels
+                *((e.jsd_B, e.labels.data_ptr()) if e.jsd_B else ()))
             img = e.img_am.data_ptr()
         if e.input_mode == "cifar_u8":
             plan.cifar_augment(img, e.x_in.data_ptr(), e.N, H, W, e.cpad_in, 4,

@@ -28,6 +28,9 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --augmix_width     AugMix: that many chains of those ops per image, mixed and blended back
                      into the original, in RandAugment's place: --augmix_depth, --augmix_severity,
                      --augmix_alpha, --augmix_ops (augmix | all | a comma list of ops)
+  --augmix_jsd       AugMix's Jensen-Shannon consistency loss: every loaded image trains as three
+                     views (clean + two AugMix draws, 3 x --batch_size rows) and --augmix_jsd_weight
+                     (12) x JSD of their predictions joins the clean view's cross-entropy
   --lr_decay         piecewise | cosine | poly, with --lr_peak, --lr_warmup_steps/_from,
                      --lr_decay_steps, --lr_end, --lr_poly_power (evaluated on the device)
   --bucket_mb        gradient all-reduce bucket size
@@ -310,6 +313,17 @@ class FlagParser(argparse.ArgumentParser):
             if ns.augmix_width > 0 and getattr(ns, "synthetic", False):
                 self.error("--augmix_width cannot be combined with --synthetic: the synthetic "
                            "input has no input launch to augment in front of")
+            if hasattr(ns, "augmix_jsd"):
+                from ..train.layout import check_augmix_jsd
+
+                try:   # needs the views; not with mixup / CutMix / erasing / distillation
+                    check_augmix_jsd(ns.augmix_jsd, ns.augmix_jsd_weight, ns.augmix_width,
+                                     getattr(ns, "mixup_alpha", 0.0),
+                                     getattr(ns, "cutmix_alpha", 0.0),
+                                     getattr(ns, "erase_prob", 0.0),
+                                     getattr(ns, "distill_alpha", 0.0))
+                except ValueError as e:
+                    self.error("--augmix_jsd: " + str(e))
             if ns.augmix_width > 0 and getattr(ns, "resident_data", False):
                 self.error("--augmix_width cannot be combined with --resident_data: the "
                            "resident input kernel picks its records itself, so there is no "
@@ -584,8 +598,20 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "(so before crop / flip / standardise, mixup / CutMix and erasing).  The "
                         "draw is per image, a function of the seed, global_step and the batch "
                         "position.  0 = off.  Evaluation never augments.  Not with "
-                        "--randaug_num_ops, --synthetic or --resident_data.  No Jensen-Shannon "
-                        "loss.")
+                        "--randaug_num_ops, --synthetic or --resident_data.")
+    p.add_bool("augmix_jsd", False,
+               "--augmix_width: AugMix's Jensen-Shannon consistency loss.  A step loads "
+               "--batch_size images and trains 3 x that many rows: the clean image and two "
+               "independent AugMix views of it (one more launch fans the stored batch out; "
+               "BatchNorm sees all rows).  loss = mean over images of [cross-entropy of the "
+               "clean view (label smoothing included) + --augmix_jsd_weight x JSD(p_clean, "
+               "p_aug1, p_aug2)], with log M formed as a logsumexp instead of the paper's clamp "
+               "of M to [1e-7, 1]; precision is counted over all three views.  Not with "
+               "--mixup_alpha, --cutmix_alpha, --erase_prob or --distill_alpha; refused where "
+               "3 x --batch_size no longer fits the step the batch size selects.")
+    p.add_argument("--augmix_jsd_weight", type=float, default=12.0,
+                   help="--augmix_jsd: the weight w >= 0 of the Jensen-Shannon term (the paper's "
+                        "12).")
     p.add_argument("--augmix_depth", type=int, default=-1,
                    help="--augmix_width: ops per chain, 1..3; -1 draws 1..3 per chain.")
     p.add_argument("--augmix_severity", type=int, default=3,

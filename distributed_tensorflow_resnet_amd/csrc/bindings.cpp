@@ -1134,6 +1134,97 @@ static Launch mk_muon_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir
                                    nseg, muon_seg, q_seg, bf, lr_out, kPiecewise);
 }
 
+// The Shampoo launches (shampoo.hip).  The tables are device copies of what train/layout.py
+// shampoo_block_table builds; the counts are the host's.
+static Launch mk_shampoo_stats(ptr_t grad, ptr_t tab, int nblocks, ptr_t L, ptr_t Rt, float beta2,
+                               float grad_scale, ptr_t gstep, ptr_t start, int every, ptr_t fail) {
+  if (!grad || !tab || !L || !Rt || !gstep) throw std::invalid_argument("shampoo_stats: null buffer");
+  if ((grad | L | Rt) & 15)
+    throw std::invalid_argument("shampoo_stats: grad, L and Rt must be 16-byte aligned");
+  if (nblocks <= 0) throw std::invalid_argument("shampoo_stats: at least one block");
+  if (!(beta2 > 0.f && beta2 <= 1.f)) throw std::invalid_argument("shampoo_stats: beta2 in (0, 1]");
+  if (every < 1) throw std::invalid_argument("shampoo_stats: every >= 1");
+  return [=](hipStream_t s) {
+    shampoo_stats(P<const float>(grad), P<const ShampooBlock>(tab), nblocks, P<float>(L),
+                  P<float>(Rt), beta2, grad_scale, P<const long long>(gstep),
+                  P<const long long>(start), every, P<int>(fail), s);
+  };
+}
+
+static Launch mk_shampoo_roots(ptr_t tab, int nblocks, int sides, ptr_t L, ptr_t Rt, ptr_t PL,
+                               ptr_t PR, ptr_t gstep, ptr_t start, int every, float epsilon,
+                               ptr_t fail) {
+  if (!tab || !L || !PL || !gstep) throw std::invalid_argument("shampoo_roots: null buffer");
+  if (sides != 1 && sides != 2) throw std::invalid_argument("shampoo_roots: sides 1 or 2");
+  if (sides == 2 && (!Rt || !PR)) throw std::invalid_argument("shampoo_roots: null buffer");
+  if ((L | Rt | PL | PR) & 15)
+    throw std::invalid_argument("shampoo_roots: the state buffers must be 16-byte aligned");
+  if (nblocks <= 0) throw std::invalid_argument("shampoo_roots: at least one block");
+  if (every < 1) throw std::invalid_argument("shampoo_roots: every >= 1");
+  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
+    throw std::invalid_argument("shampoo_roots: epsilon positive and finite");
+  return [=](hipStream_t s) {
+    shampoo_roots(P<const ShampooBlock>(tab), nblocks, sides, P<const float>(L),
+                  P<const float>(Rt), P<float>(PL), P<float>(PR), P<const long long>(gstep),
+                  P<const long long>(start), every, epsilon, P<int>(fail), s);
+  };
+}
+
+static Launch mk_shampoo_precondition(ptr_t grad, ptr_t tab, int nblocks, ptr_t PL, ptr_t PR,
+                                      ptr_t dir, ptr_t part, float grad_scale) {
+  if (!grad || !tab || !PL || !PR || !dir || !part)
+    throw std::invalid_argument("shampoo_precondition: null buffer");
+  if ((grad | PL | PR | dir) & 15)
+    throw std::invalid_argument("shampoo_precondition: grad, PL, PR and dir must be 16-byte aligned");
+  if (nblocks <= 0) throw std::invalid_argument("shampoo_precondition: at least one block");
+  return [=](hipStream_t s) {
+    shampoo_precondition(P<const float>(grad), P<const ShampooBlock>(tab), nblocks,
+                         P<const float>(PL), P<const float>(PR), P<float>(dir), P<double>(part),
+                         grad_scale, s);
+  };
+}
+
+static Launch mk_shampoo_graft(ptr_t part, ptr_t ttab, int ntensors, int nseg, ptr_t out) {
+  if (!part || !ttab || !out) throw std::invalid_argument("shampoo_graft: null buffer");
+  if (ntensors <= 0 || nseg <= 0) throw std::invalid_argument("shampoo_graft: ntensors, nseg > 0");
+  return [=](hipStream_t s) {
+    shampoo_graft(P<const double>(part), P<const ShampooTensor>(ttab), ntensors, nseg,
+                  P<float>(out), s);
+  };
+}
+
+static Launch mk_shampoo_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                           float init, long long warm_steps, float warm_from,
+                                           float warm_to, std::vector<long long> bounds,
+                                           std::vector<float> vals, ptr_t gstep, float momentum,
+                                           float wd, float grad_scale, ptr_t segs, int nseg,
+                                           ptr_t pre_seg, ptr_t graft, ptr_t bf, ptr_t lr_out,
+                                           LrDecayArgs decay) {
+  if ((master | grad | mom | dir) & 15)
+    throw std::invalid_argument("shampoo_update_pack: master, grad, mom and dir must be 16-byte aligned");
+  if (!master || !grad || !mom || !dir || !segs || !pre_seg || !graft || !gstep)
+    throw std::invalid_argument("shampoo_update_pack: null buffer");
+  if (n < 0 || nseg <= 0) throw std::invalid_argument("shampoo_update_pack: n >= 0 and nseg > 0");
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    shampoo_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), P<const float>(dir),
+                        n, sc, P<const long long>(gstep), momentum, wd, grad_scale,
+                        P<const ParamSeg>(segs), nseg, P<const int>(pre_seg), P<const float>(graft),
+                        P<bf16>(bf), P<float>(lr_out), s);
+  };
+}
+
+static Launch mk_shampoo_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                     float init, long long warm_steps, float warm_from,
+                                     float warm_to, std::vector<long long> bounds,
+                                     std::vector<float> vals, ptr_t gstep, float momentum, float wd,
+                                     float grad_scale, ptr_t segs, int nseg, ptr_t pre_seg,
+                                     ptr_t graft, ptr_t bf, ptr_t lr_out) {
+  return mk_shampoo_update_pack_decay(master, grad, mom, dir, n, init, warm_steps, warm_from,
+                                      warm_to, bounds, vals, gstep, momentum, wd, grad_scale, segs,
+                                      nseg, pre_seg, graft, bf, lr_out, kPiecewise);
+}
+
 // The tiled Muon launches (muon_tiled.hip).  The tables are device copies of what
 // train/layout.py muon_tiled_tables builds; the counts are the host's.
 static Launch mk_muon_tiled_moments(ptr_t grad, ptr_t mom, ptr_t tab, ptr_t blk_t, int nblocks,
@@ -2148,6 +2239,12 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "muon_tiled_unstage", mk_muon_tiled_unstage);
   def_op(m, plan, "muon_update_pack", mk_muon_update_pack);
   def_op(m, plan, "muon_update_pack", mk_muon_update_pack_decay);
+  def_op(m, plan, "shampoo_stats", mk_shampoo_stats);
+  def_op(m, plan, "shampoo_roots", mk_shampoo_roots);
+  def_op(m, plan, "shampoo_precondition", mk_shampoo_precondition);
+  def_op(m, plan, "shampoo_graft", mk_shampoo_graft);
+  def_op(m, plan, "shampoo_update_pack", mk_shampoo_update_pack);
+  def_op(m, plan, "shampoo_update_pack", mk_shampoo_update_pack_decay);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
   def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);
@@ -2263,6 +2360,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("lars_seg_bytes", []() { return (int)sizeof(LarsSeg); });
   m.def("muon_tensor_bytes", []() { return (int)sizeof(MuonTensor); });
   m.def("muon_covers", &muon_covers);
+  m.def("shampoo_block_bytes", []() { return (int)sizeof(ShampooBlock); });
+  m.def("shampoo_tensor_bytes", []() { return (int)sizeof(ShampooTensor); });
   m.def("muon_tiled_tensor_bytes", []() { return (int)sizeof(MuonTiledTensor); });
   m.def("muon_work_bytes", []() { return (int)sizeof(MuonWork); });
   m.def("muon_tiled_covers", &muon_tiled_covers);

@@ -216,6 +216,58 @@ void muon_tiled_apply(bf16* scratch, const MuonTiledTensor* tab, const MuonWork*
 // dir = X as fp32 in M's orientation, the tensor's own elements only.
 void muon_tiled_unstage(const bf16* scratch, float* dir, const MuonTiledTensor* tab,
                         const MuonWork* work, int nwork, hipStream_t st);
+// Blocked Shampoo with SGD grafting (shampoo.hip).  One record per 64 x 64 block of a conv
+// kernel's row-major R x K master: `offset` of its first element in the flat buffers, the
+// leading dimension K, the live size r x k (<= 64 each; ragged at the edges), its parameter
+// segment and its slot in the state buffers L, Rt, PL, PR ([slot][64][64] fp32, zero outside
+// the live part; the roots start as the identity on it).
+constexpr int SH_BLOCK = 64;
+struct ShampooBlock {
+  long long offset;
+  int K;
+  int r, k;
+  int seg;
+  int slot;
+  int pad;
+};
+// One record per preconditioned tensor: its blocks [block0, block0 + nblocks) of the table.
+struct ShampooTensor {
+  int block0, nblocks;
+  int seg;
+  int pad;
+};
+// The step count every launch below derives on the device: t = *gstep - *start + 1 (start may
+// be null: 0).  One workgroup per block: L = beta2 L + c G G^T and Rt = beta2 Rt + c G^T G with
+// G the block of grad_scale * grad (only read) and c = 1 - beta2 rounded once from fp64, or 1
+// when beta2 is 1.  On a step with t % every == 0 it also clears *fail (optional).
+void shampoo_stats(const float* grad, const ShampooBlock* tab, int nblocks, float* L, float* Rt,
+                   float beta2, float grad_scale, const long long* gstep, const long long* start,
+                   int every, int* fail, hipStream_t st);
+// One workgroup per (block, side), sides = 2 (1: only L -> PL, at the live size r).  Unless
+// t % every == 0 nothing happens.  Else the coupled Newton iteration for
+// (A + epsilon ||A||_F I)^(-1/4), at most 32 steps in LDS; the live part of the root slot is
+// overwritten unless the iteration ends at max|Mk - I| >= 1e-2 or not finite, which adds 1 to
+// *fail (optional) instead.
+void shampoo_roots(const ShampooBlock* tab, int nblocks, int sides, const float* L, const float* Rt,
+                   float* PL, float* PR, const long long* gstep, const long long* start, int every,
+                   float epsilon, int* fail, hipStream_t st);
+// One workgroup per block: U = PL G PR into dir at the block's elements, and part[2 b],
+// part[2 b + 1] = the block's sums of g'^2 and U^2 (fp64 from the wave on).
+void shampoo_precondition(const float* grad, const ShampooBlock* tab, int nblocks, const float* PL,
+                          const float* PR, float* dir, double* part, float grad_scale,
+                          hipStream_t st);
+// One wave per tensor: gn = ||g'||, un = ||U|| from its blocks' partials in table order;
+// out[seg] = gn / un (exactly 1 where a norm is not > 0), out[nseg + seg] = gn,
+// out[2 nseg + seg] = un.
+void shampoo_graft(const double* part, const ShampooTensor* ttab, int ntensors, int nseg,
+                   float* out, hipStream_t st);
+// One launch of muon_update_pack's shape: sgd_update_pack's update with momentum, bit for bit,
+// where pre_seg[segment] == 0; else with graft[segment] * dir in place of grad_scale * grad.
+// master, grad, mom and dir must be 16-byte aligned.
+void shampoo_update_pack(float* master, const float* grad, float* mom, const float* dir, long n,
+                         const LrSchedule& s, const long long* gstep, float momentum, float wd,
+                         float grad_scale, const ParamSeg* segs, int nseg, const int* pre_seg,
+                         const float* graft, bf16* bf, float* lr_out, hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

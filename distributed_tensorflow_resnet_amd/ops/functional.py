@@ -449,3 +449,80 @@ def muon_orthogonalize_tiled(grad, mom, shapes, offsets=None, *, momentum=0.95, 
         muon_tiled_sequence(native(), buf, grad.data_ptr(), mom.data_ptr(), out.data_ptr(),
                             momentum, nesterov, steps, grad_scale, tail=(_stream(),))
     return out
+
+
+def _shampoo_table(recs, device):
+    """Device copy of train/layout.py shampoo_block_table(recs)'s block table, and the host one."""
+    import numpy as np
+
+    from ..train.layout import SHAMPOO_DTYPE, SHAMPOO_TENSOR_DTYPE, shampoo_block_table
+
+    nat = native()
+    assert SHAMPOO_DTYPE.itemsize == nat.shampoo_block_bytes()
+    assert SHAMPOO_TENSOR_DTYPE.itemsize == nat.shampoo_tensor_bytes()
+    blocks, _ = shampoo_block_table(recs)
+    return torch.from_numpy(blocks.view(np.uint8).copy()).to(device), blocks
+
+
+def _shampoo_state(x, nblocks, name):
+    _check(x, torch.float32, 3, name)
+    if tuple(x.shape) != (nblocks, 64, 64):
+        raise ValueError(f"{name} must be [{nblocks}, 64, 64], got {tuple(x.shape)}")
+
+
+def shampoo_roots(stat, root, sizes, *, epsilon=1e-6, step=1, every=1, fail=None):
+    """csrc/shampoo.hip's roots launch on single sides: slot i of ``stat`` ([n, 64, 64] fp32,
+    zero outside its live sizes[i] x sizes[i] part) is a symmetric positive semi-definite
+    statistic A, and the live part of slot i of ``root`` becomes (A + epsilon ||A||_F I)^(-1/4)
+    by the coupled Newton iteration -- when ``step`` (the 1-based step count, put into a step
+    word on the device) is a multiple of ``every``; otherwise the launch changes nothing.  A
+    slot whose iteration fails keeps its root and adds 1 to ``fail`` (int32 [1], optional).
+    Returns ``root``."""
+    n = len(sizes)
+    _shampoo_state(stat, n, "stat")
+    _shampoo_state(root, n, "root")
+    if any(not 1 <= int(s) <= 64 for s in sizes):
+        raise ValueError("every live size must be in [1, 64]")
+    # (a block table of n x n matrices back to back: only r and the slot are read)
+    recs, off = [], 0
+    for i, s in enumerate(sizes):
+        recs.append((off, i, int(s), int(s)))
+        off += int(s) * int(s)
+    dtab, _ = _shampoo_table(recs, stat.device)
+    gstep = torch.tensor([int(step) - 1], dtype=torch.int64, device=stat.device)
+    native().shampoo_roots(dtab.data_ptr(), n, 1, stat.data_ptr(), 0, root.data_ptr(), 0,
+                           gstep.data_ptr(), 0, int(every), float(epsilon), _ptr(fail), _stream())
+    return root
+
+
+def shampoo_stats_precondition(grad, shapes, offsets, L, Rt, PL, PR, *, beta2=1.0, grad_scale=1.0,
+                               out=None):
+    """csrc/shampoo.hip's stats and precondition launches on bare tensors: every (R, K) of
+    ``shapes`` is the row-major matrix at the matching element of ``offsets`` in the flat fp32
+    ``grad`` (only read), cut into 64 x 64 blocks in train/layout.py shampoo_block_table's
+    order; L, Rt, PL, PR are [blocks, 64, 64].  L and Rt are updated in place
+    (beta2 L + c G G^T, beta2 Rt + c G^T G) and U = PL G PR is written into ``out`` (default:
+    zeros like grad) at the blocks' elements.  Returns (out, part, blocks): part is the fp64
+    [blocks, 2] table of each block's sums of g'^2 and U^2, blocks the host table."""
+    _check(grad, torch.float32, 1, "grad")
+    out = torch.zeros_like(grad) if out is None else out
+    _check(out, torch.float32, 1, "out")
+    if len(offsets) != len(shapes) or out.numel() != grad.numel():
+        raise ValueError("one offset per shape, and grad and out of one length")
+    recs = []
+    for i, (o, (R, K)) in enumerate(zip(offsets, shapes)):
+        if R < 1 or K < 1 or o < 0 or o + R * K > grad.numel():
+            raise ValueError(f"matrix {R} x {K} at {o} is outside the {grad.numel()} elements")
+        recs.append((int(o), i, int(R), int(K)))
+    dtab, blocks = _shampoo_table(recs, grad.device)
+    nb = len(blocks)
+    for x, name in ((L, "L"), (Rt, "Rt"), (PL, "PL"), (PR, "PR")):
+        _shampoo_state(x, nb, name)
+    part = torch.zeros(nb, 2, dtype=torch.float64, device=grad.device)
+    gstep = torch.zeros(1, dtype=torch.int64, device=grad.device)
+    nat = native()
+    nat.shampoo_stats(grad.data_ptr(), dtab.data_ptr(), nb, L.data_ptr(), Rt.data_ptr(),
+                      float(beta2), float(grad_scale), gstep.data_ptr(), 0, 1, 0, _stream())
+    nat.shampoo_precondition(grad.data_ptr(), dtab.data_ptr(), nb, PL.data_ptr(), PR.data_ptr(),
+                             out.data_ptr(), part.data_ptr(), float(grad_scale), _stream())
+    return out, part, blocks

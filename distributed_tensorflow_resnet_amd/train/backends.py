@@ -27,13 +27,14 @@ from ..models.spec import ModelSpec
 from ..ops import reference as ref
 from ..parallel.dist import local_device_index
 from ..utils.checkpoint import (check_rmsprop_form, state_to_tf, tf_to_adam, tf_to_lion,
-                                tf_to_rmsprop, tf_to_state)
+                                tf_to_rmsprop, tf_to_shampoo, tf_to_state)
 from .distill import TorchTeacher, check_distill, soft_loss
 from .jsd import jsd_loss
 from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corrections, lamb_trust_summary,  # noqa: E501
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug,
-                     check_augmix, check_augmix_jsd)
+                     check_augmix, check_augmix_jsd, check_shampoo, shampoo_tables,
+                     shampoo_identity_roots, shampoo_graft_summary)
 
 
 class GPUBackend:
@@ -94,7 +95,19 @@ class GPUBackend:
                     "beta1": eng.adam_beta1, "beta2": eng.adam_beta2}
         rms = {"ms": eng.rms_ms, "mg": eng.rms_mg} if eng.rmsprop else None
         return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam,
-                           lion=eng.lion, rmsprop=rms)
+                           lion=eng.lion, rmsprop=rms, shampoo=self._shampoo_slots())
+
+    def _shampoo_slots(self):
+        """state_to_tf's / tf_to_shampoo's dict over the engine's block state (None: not shampoo)."""
+        eng = self.engine
+        if not eng.shampoo:
+            return None
+        st = eng.shampoo_state()
+        return {**{k: st[k] for k in ("L", "R", "PL", "PR")},
+                "tensors": [(n, int(t["block0"]), int(t["nblocks"]))
+                            for n, t in zip(eng.shampoo_names, eng.shampoo_tensors)],
+                "start_step": int(eng.shampoo_start.item()),
+                "identity": shampoo_identity_roots(eng.shampoo_blocks)}
 
     def load_state(self, tensors):
         eng = self.engine
@@ -110,6 +123,8 @@ class GPUBackend:
             eng.set_adam_start(tf_to_adam(tensors, eng.params, eng.mom, eng.adam_v))
         if eng.lion:
             tf_to_lion(tensors, eng.params, eng.mom)
+        if eng.shampoo:
+            eng.set_shampoo_start(tf_to_shampoo(tensors, self._shampoo_slots()))
         eng.sync_from_params(ema_loaded=True)
         self._host_step = gs
 
@@ -182,6 +197,8 @@ class CPUBackend:
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
+                 shampoo_precond_every: int = 10,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -285,7 +302,7 @@ class CPUBackend:
         self.last_eval_top5 = 0.0  # in-top-5 count of the last evaluate_batch
         self.momentum = momentum
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon or rmsprop, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon, shampoo or rmsprop, got {optimizer!r}")
         # adamw, csrc/adam.hip's expressions in fp32 torch: the first moment in `mom`, the
         # second in `adam_v`; t counts from adam_start
         self.adam = optimizer == "adamw"
@@ -340,6 +357,19 @@ class CPUBackend:
             self.muon_tab = list(tab) + (list(tiled[0]["tab"]) if tiled else [])
             self.muon_mask = torch.repeat_interleave(
                 torch.from_numpy(seg).bool(), torch.tensor([s.numel for s in self.store.train_slots]))
+        # shampoo, csrc/shampoo.hip's formulas in torch (the roots by fp64 eigh instead of the
+        # coupled Newton iteration): the block state in the kernels' [blocks, 64, 64] layout
+        self.shampoo = optimizer == "shampoo"
+        self.shampoo_beta2, self.shampoo_epsilon, self.shampoo_every = check_shampoo(
+            shampoo_beta2, shampoo_epsilon, shampoo_precond_every, self.clip_grad_norm, optimizer)
+        self.shampoo_start, self._shampoo_last, self.shampoo_failed = 0, {}, 0
+        if self.shampoo:
+            (self.shampoo_blocks, self.shampoo_tensors, _,
+             self.shampoo_names) = shampoo_tables(self.store.train_slots)
+            nb = len(self.shampoo_blocks)
+            self.shampoo_L, self.shampoo_R = torch.zeros(nb, 64, 64), torch.zeros(nb, 64, 64)
+            self.shampoo_PL, self.shampoo_PR = (
+                torch.from_numpy(p) for p in shampoo_identity_roots(self.shampoo_blocks))
         if lars_skip not in ("vectors", "none"):
             raise ValueError(f"lars_skip must be vectors or none, got {lars_skip!r}")
         self.lars = optimizer == "lars"
@@ -460,6 +490,8 @@ class CPUBackend:
                 self._rmsprop_update(master, g, lr)
             elif self.muon:
                 self._muon_update(master, g, gp, lr)
+            elif self.shampoo:
+                self._shampoo_update(master, g, lr)
             elif self.lars:
                 self.mom.mul_(self.momentum).add_(gp)
                 master.sub_(lr * self._lars_trust(master, g) * self.mom)
@@ -590,6 +622,76 @@ class CPUBackend:
             master[sl] = (w - (lr * self.wd) * w) - (lr * float(self.muon_q[int(rec["seg"])])) * o_dir
         self.mom[aux] = m_aux
         master[aux] = w_aux
+
+    def _shampoo_update(self, master, g, lr):
+        """csrc/shampoo.hip's five launches in torch: per 64 x 64 block of a conv kernel the
+        statistics L, R, on a refresh step (t % every == 0) the roots
+        (A + eps ||A||_F I)^(-1/4) by fp64 eigh, U = PL G PR; per tensor c = ||g|| / ||U||; then
+        mom's update with c U in place of the gradient of a conv kernel."""
+        t = self.step_count - self.shampoo_start + 1
+        refresh = t % self.shampoo_every == 0
+        b2 = float(np.float32(self.shampoo_beta2))
+        c1 = 1.0 if b2 == 1.0 else float(np.float32(1.0 - b2))
+        if refresh:
+            self.shampoo_failed = 0
+        d = g.clone()
+        for blk in self.shampoo_blocks:
+            o, K, r, k, s = (int(blk[f]) for f in ("offset", "K", "r", "k", "slot"))
+            idx = o + torch.arange(r)[:, None] * K + torch.arange(k)[None, :]
+            G = g[idx]
+            sides = ((self.shampoo_L[s, :r, :r], G @ G.t(), self.shampoo_PL[s, :r, :r]),
+                     (self.shampoo_R[s, :k, :k], G.t() @ G, self.shampoo_PR[s, :k, :k]))
+            for A, gram, P in sides:
+                A.mul_(b2).add_(c1 * gram)
+                if refresh:
+                    root = self._shampoo_root(A)
+                    if root is None:
+                        self.shampoo_failed += 1
+                    else:
+                        P.copy_(root)
+            d[idx] = sides[0][2] @ G @ sides[1][2]
+        for name, ten in zip(self.shampoo_names, self.shampoo_tensors):
+            slot = self.store.train_slots[int(ten["seg"])]
+            sl = slice(slot.offset, slot.offset + slot.numel)
+            gn, un = float(g[sl].double().norm()), float(d[sl].double().norm())
+            c = float(np.float32(gn / un)) if gn > 0 and un > 0 else 1.0
+            d[sl] = c * d[sl]
+            self._shampoo_last[name] = (gn, un, c)
+        self.mom.mul_(self.momentum).add_(d + self.wd * master)
+        master.sub_(lr * self.mom)
+
+    def _shampoo_root(self, A):
+        """(A + eps ||A||_F I)^(-1/4) of a symmetric positive semi-definite fp32 matrix by fp64
+        eigh, as fp32; None where it does not exist (a zero or non-finite statistic)."""
+        A = A.double()
+        D = A + self.shampoo_epsilon * float(A.norm()) * torch.eye(A.shape[0], dtype=torch.float64)
+        if not bool(torch.isfinite(D).all()):
+            return None
+        w, V = torch.linalg.eigh(D)
+        if not float(w.min()) > 0:
+            return None
+        return ((V * w.pow(-0.25)) @ V.t()).float()
+
+    def shampoo_state(self):
+        """As Engine.shampoo_state (None unless the optimizer is shampoo)."""
+        if not self.shampoo:
+            return None
+        bufs = {"L": self.shampoo_L, "R": self.shampoo_R, "PL": self.shampoo_PL,
+                "PR": self.shampoo_PR}
+        return {"t": self.step_count - self.shampoo_start, "tensors": dict(self._shampoo_last),
+                "failed": self.shampoo_failed, "state_bytes": 4 * 4 * self.shampoo_L.numel(),
+                **bufs}
+
+    def _shampoo_slots(self):
+        """state_to_tf's / tf_to_shampoo's dict over the block state (None: not shampoo)."""
+        if not self.shampoo:
+            return None
+        st = self.shampoo_state()
+        return {**{k: st[k] for k in ("L", "R", "PL", "PR")},
+                "tensors": [(n, int(t["block0"]), int(t["nblocks"]))
+                            for n, t in zip(self.shampoo_names, self.shampoo_tensors)],
+                "start_step": self.shampoo_start,
+                "identity": shampoo_identity_roots(self.shampoo_blocks)}
 
     def _lamb_update(self, master, g, lr):
         """csrc/lamb.hip's three stages in fp32 torch (the norms in fp64, as the kernels'
@@ -766,6 +868,9 @@ class CPUBackend:
             m["optimizer"] = "rmsprop"
         if self.muon:
             m["optimizer"] = "muon"
+        if self.shampoo:
+            m["optimizer"] = "shampoo"
+            m.update(shampoo_graft_summary(self._shampoo_last))
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -795,7 +900,7 @@ class CPUBackend:
                     "beta2": self.adam_beta2}
         rms = {"ms": self.rms_ms, "mg": self.rms_mg} if self.rmsprop else None
         return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam,
-                           lion=self.lion, rmsprop=rms)
+                           lion=self.lion, rmsprop=rms, shampoo=self._shampoo_slots())
 
     def load_state(self, tensors):
         with torch.no_grad():
@@ -810,17 +915,22 @@ class CPUBackend:
                 tf_to_lion(tensors, self.store, self.mom)
             if self.rmsprop:   # (after the weights, as the adam and lion slots)
                 tf_to_rmsprop(tensors, self.store, self.rms_ms, self.rms_mg, self.mom)
+            if self.shampoo:
+                self.shampoo_start = tf_to_shampoo(tensors, self._shampoo_slots())
 
     def broadcast_parameters(self, src: int = 0):
         if self.dist is not None and self.world > 1:
             with torch.no_grad():
                 for t in (self.store.master, self.store.stats, self.mom) + (
                         (self.ema,) if self.ema is not None else ()) + (
-                        (self.adam_v,) if self.adam else ()):
+                        (self.adam_v,) if self.adam else ()) + (
+                        (self.shampoo_L, self.shampoo_R, self.shampoo_PL, self.shampoo_PR)
+                        if self.shampoo else ()):
                     self.dist.broadcast(t.data, src)
-                s = torch.tensor([self.step_count, self.adam_start])
+                s = torch.tensor([self.step_count, self.adam_start, self.shampoo_start])
                 self.dist.broadcast(s, src)
-                self.step_count, self.adam_start = (int(x) for x in s.tolist())
+                self.step_count, self.adam_start, self.shampoo_start = (
+                    int(x) for x in s.tolist())
 
     # -------------------------------------------------------------- eval
     def evaluate_batch(self, images, labels):
@@ -858,6 +968,8 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
+                 shampoo_precond_every: int = 10,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -876,7 +988,9 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                 rmsprop_centered=rmsprop_centered, rmsprop_wd=rmsprop_wd,
                 rmsprop_decay_skip=rmsprop_decay_skip, muon_momentum=muon_momentum,
                 muon_nesterov=muon_nesterov, muon_ns_steps=muon_ns_steps,
-                muon_aux_lr_scale=muon_aux_lr_scale, muon_tiled=muon_tiled)
+                muon_aux_lr_scale=muon_aux_lr_scale, muon_tiled=muon_tiled,
+                shampoo_beta2=shampoo_beta2, shampoo_epsilon=shampoo_epsilon,
+                shampoo_precond_every=shampoo_precond_every)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

@@ -264,6 +264,9 @@ def main(argv=None, kind: str = "cifar") -> int:
                            muon_ns_steps=flags.muon_ns_steps,
                            muon_aux_lr_scale=flags.muon_aux_lr_scale,
                            muon_tiled=flags.muon_tiled,
+                           shampoo_beta2=flags.shampoo_beta2,
+                           shampoo_epsilon=flags.shampoo_epsilon,
+                           shampoo_precond_every=flags.shampoo_precond_every,
                            distill_alpha=flags.distill_alpha,
                            distill_temperature=flags.distill_temperature,
                            distill_teacher=teacher,

@@ -59,7 +59,9 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPTIMIZERS, OPT_FUSED_ADAM_REASON, adam_decay_table, check_adam,
                      OPT_FUSED_LAMB_REASON, check_adam_trust, lamb_trust_summary,
                      OPT_FUSED_LION_REASON, check_lion, OPT_FUSED_RMSPROP_REASON, check_rmsprop,
-                     MUON_DTYPE, OPT_FUSED_MUON_REASON, check_muon, muon_tables)
+                     MUON_DTYPE, OPT_FUSED_MUON_REASON, check_muon, muon_tables,
+                     SHAMPOO_DTYPE, SHAMPOO_TENSOR_DTYPE, OPT_FUSED_SHAMPOO_REASON, check_shampoo,
+                     shampoo_tables, shampoo_identity_roots, shampoo_graft_summary)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -150,6 +152,8 @@ class Engine:
                  rmsprop_decay_skip: str = "none", muon_momentum: float = 0.95,
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
+                 shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
+                 shampoo_precond_every: int = 10,
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -182,7 +186,7 @@ class Engine:
         self.wd = float(weight_decay)
         self.momentum = float(momentum)
         if optimizer not in OPTIMIZERS:
-            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon or rmsprop, got {optimizer!r}")
+            raise ValueError(f"optimizer must be mom, sgd, lars, adamw, lion, muon, shampoo or rmsprop, got {optimizer!r}")
         if lars_skip not in LARS_SKIPS:
             raise ValueError(f"lars_skip must be one of {LARS_SKIPS}, got {lars_skip!r}")
         # lars: SGD-momentum at a per-tensor rate lr * trust (csrc/lars.hip); the momentum
@@ -230,6 +234,14 @@ class Engine:
         # muon_tiled: conv kernels outside muon_covers (the ImageNet networks) take the tiled
         # launches of csrc/muon_tiled.hip instead of being refused; off: nothing allocated
         self.muon_tiled = bool(muon_tiled) and self.muon
+        # shampoo: every conv kernel, cut into 64 x 64 blocks, moves along PL G PR rescaled to
+        # the length of its SGD step (csrc/shampoo.hip: statistics, roots every
+        # shampoo_precond_every steps, direction, grafting norm, flat update); every other
+        # tensor takes mom's update.  The momentum buffer means what it means for mom; the
+        # block state, the direction buffer and the tables exist only for it
+        self.shampoo = optimizer == "shampoo"
+        self.shampoo_beta2, self.shampoo_epsilon, self.shampoo_every = check_shampoo(
+            shampoo_beta2, shampoo_epsilon, shampoo_precond_every, self.clip_grad_norm, optimizer)
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -410,6 +422,12 @@ class Engine:
             if self.rmsprop_centered:
                 self.rms_mg = torch.zeros(self.params.n_train, device=dev)
         self.muon_dir = torch.zeros(self.params.n_train, device=dev) if self.muon else None
+        self.shampoo_dir = self.shampoo_start = self.shampoo_fail = None
+        if self.shampoo:
+            self.shampoo_dir = torch.zeros(self.params.n_train, device=dev)
+            # the step the statistics count from (t = global_step - start + 1), as adam_start
+            self.shampoo_start = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.shampoo_fail = torch.zeros(1, dtype=torch.int32, device=dev)
         self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
         # loss_sum, correct, lr, l2, health word (persistent step), in-top-5 count
         self.scalars = torch.zeros(8, device=dev)
@@ -473,6 +491,9 @@ class Engine:
         if self.muon and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_MUON_REASON
+        if self.shampoo and self.opt_fused:
+            self.opt_fused = False
+            self.opt_fused_reason = OPT_FUSED_SHAMPOO_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -616,6 +637,23 @@ class Engine:
 
                 self.muon_tiled_buf = muon_tiled_buffers(tiled[0], dev)
             self.muon_seg, self.muon_q = torch.from_numpy(seg).to(dev), torch.from_numpy(q).to(dev)
+        self.shampoo_tab = self.shampoo_state_buf = None
+        if self.shampoo:
+            # one record per 64 x 64 block of every conv kernel, one per conv kernel, the
+            # segment flags; L, Rt, PL, PR as [4][blocks][64][64] (the roots from the identity),
+            # the blocks' partial sums and (c, ||g'||, ||U||) per segment: fixed pointers
+            blocks, tens, seg, names = shampoo_tables(ps.train_slots)
+            assert SHAMPOO_DTYPE.itemsize == self.nat.shampoo_block_bytes()
+            assert SHAMPOO_TENSOR_DTYPE.itemsize == self.nat.shampoo_tensor_bytes()
+            self.shampoo_blocks, self.shampoo_tensors, self.shampoo_names = blocks, tens, names
+            self.shampoo_tab = torch.from_numpy(blocks.view(np.uint8).copy()).to(dev)
+            self.shampoo_ttab = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
+            self.shampoo_seg = torch.from_numpy(seg).to(dev)
+            self.shampoo_state_buf = torch.zeros(4, len(blocks), 64, 64, device=dev)
+            for i, p in enumerate(shampoo_identity_roots(blocks)):
+                self.shampoo_state_buf[2 + i].copy_(torch.from_numpy(p))
+            self.shampoo_part = torch.zeros(2 * len(blocks), dtype=torch.float64, device=dev)
+            self.shampoo_out = torch.ones(3, self.nseg, device=dev)
         self.clip_part = self.clip_out = None
         if self.clip_grad_norm > 0:
             # chunk partials and the {norm, scale} slot: fixed pointers
@@ -966,6 +1004,29 @@ class Engine:
         if self.rmsprop_centered:
             st["mg"] = self.rms_mg.view(-1)
         return st
+
+    def shampoo_state(self):
+        """The shampoo optimizer's last step (synchronises): {"t": its 1-based step count,
+        "tensors": {conv kernel name: (||g'||, ||U||, c)}, "failed": blocks whose root iteration
+        failed at the last refresh, "state_bytes": bytes of L, Rt, PL and PR, "L" / "R" / "PL" /
+        "PR": views [blocks, 64, 64] of the state}.  None unless the optimizer is shampoo."""
+        if not self.shampoo:
+            return None
+        torch.cuda.synchronize(self.device)
+        c, gn, un = self.shampoo_out.cpu().tolist()
+        buf = self.shampoo_state_buf
+        return {"t": int(self.gstep.item()) - int(self.shampoo_start.item()),
+                "tensors": {n: (gn[s], un[s], c[s])
+                            for n, s in zip(self.shampoo_names, self.shampoo_tensors["seg"])},
+                "failed": int(self.shampoo_fail.item()),
+                "state_bytes": buf.numel() * buf.element_size(),
+                "L": buf[0], "R": buf[1], "PL": buf[2], "PR": buf[3]}
+
+    def set_shampoo_start(self, step: int):
+        """The step the refresh schedule counts from (a restore's: the checkpoint's
+        shampoo_start_step, or global_step when the state restarts)."""
+        if self.shampoo:
+            self.shampoo_start.fill_(int(step))
 
     def set_adam_start(self, step: int):
         """The step the moments count from (a restore's: the checkpoint's adam_start_step, or
@@ -1330,6 +1391,9 @@ class Engine:
             m["optimizer"] = "rmsprop"
         if self.muon:
             m["optimizer"] = "muon"
+        if self.shampoo:
+            m["optimizer"] = "shampoo"
+            m.update(shampoo_graft_summary(self.shampoo_state()["tensors"]))
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
@@ -1364,6 +1428,8 @@ class Engine:
             ts += (self.adam_v, self.adam_start)
         if self.rmsprop:
             ts += (self.rms_ms,) + ((self.rms_mg,) if self.rmsprop_centered else ())
+        if self.shampoo:
+            ts += (self.shampoo_state_buf, self.shampoo_start)
         return ts + (self.ema,) if self.ema is not None else ts
 
     def broadcast_parameters(self, src: int = 0):

@@ -102,6 +102,10 @@ class LoggingTensorHook(Hook):
                 clip += ", optimizer: rmsprop"
             if m.get("optimizer") == "muon":   # --optimizer muon
                 clip += ", optimizer: muon"
+            if m.get("optimizer") == "shampoo":   # --optimizer shampoo
+                clip += (f", optimizer: shampoo, graft min/median/max = "
+                         f"{m['shampoo_graft_min']:.4g}/{m['shampoo_graft_median']:.4g}/"
+                         f"{m['shampoo_graft_max']:.4g}")
             mix = ""
             if "mix_mode" in m:   # --mixup_alpha / --cutmix_alpha
                 mix = (f", cutmix lam = {m['mixup_lam']:.6g} (area {m['cutmix_area']})"

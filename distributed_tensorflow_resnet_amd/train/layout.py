@@ -134,7 +134,7 @@ OPT_FUSED_CLIP_REASON = ("clip_grad_norm: the norm is taken over the complete gr
                          "before the update")
 
 
-OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion", "muon", "rmsprop")
+OPTIMIZERS = ("mom", "sgd", "lars", "adamw", "lion", "muon", "shampoo", "rmsprop")
 ADAM_DECAYS = ("decoupled", "l2")
 ADAM_DECAY_SKIPS = ("none", "vectors")
 OPT_FUSED_ADAM_REASON = ("optimizer adamw: the one-launch optimizer is SGD-momentum; adamw takes "
@@ -332,6 +332,95 @@ def muon_tables(train_slots, tiled=False):
         q[i] = np.sqrt(np.float32(max(1.0, K / R)))
     tab = np.array(recs, dtype=MUON_DTYPE)
     return (tab, seg, q, muon_tiled_tables(big)) if tiled else (tab, seg, q)
+
+
+OPT_FUSED_SHAMPOO_REASON = ("optimizer shampoo: the direction of a conv kernel is a matrix function "
+                            "of its whole gradient (preconditioner blocks, then a per-tensor "
+                            "grafting norm); it takes five generic launches")
+SHAMPOO_BLOCK = 64        # csrc/optim.h SH_BLOCK: the fixed block size
+SHAMPOO_DTYPE = np.dtype([   # csrc/optim.h ShampooBlock
+    ("offset", "<i8"), ("K", "<i4"), ("r", "<i4"), ("k", "<i4"), ("seg", "<i4"), ("slot", "<i4"),
+    ("pad", "<i4"),
+])
+SHAMPOO_TENSOR_DTYPE = np.dtype([   # csrc/optim.h ShampooTensor
+    ("block0", "<i4"), ("nblocks", "<i4"), ("seg", "<i4"), ("pad", "<i4"),
+])
+
+
+def check_shampoo(beta2=1.0, epsilon=1e-6, precond_every=10, clip_grad_norm: float = 0.0,
+                  optimizer: str = "shampoo", adam_trust="off"):
+    """The shampoo flags as both backends take them: (beta2, epsilon, precond_every).  beta2 in
+    (0, 1] (1: the statistics are sums), epsilon positive and finite in fp32, precond_every an
+    integer >= 1.  With the shampoo optimizer, clip_grad_norm is refused (grafting fixes the
+    length of every conv kernel's step from the unclipped gradient)."""
+    try:
+        b2, eps, every = float(beta2), float(epsilon), int(precond_every)
+    except (TypeError, ValueError):
+        raise ValueError(f"shampoo_beta2, shampoo_epsilon and shampoo_precond_every must be "
+                         f"numbers, got {beta2!r}, {epsilon!r}, {precond_every!r}") from None
+    if not 0.0 < b2 <= 1.0 or not float(np.float32(b2)) > 0.0:   # NaN included
+        raise ValueError(f"shampoo_beta2 must be in (0, 1], got {b2!r}")
+    if not 0.0 < float(np.float32(eps)) < float("inf"):
+        raise ValueError(f"shampoo_epsilon must be positive (and finite in fp32), got {eps!r}")
+    if every != float(precond_every) or every < 1:
+        raise ValueError(f"shampoo_precond_every must be an integer >= 1, got {precond_every!r}")
+    if optimizer == "shampoo" and float(clip_grad_norm) > 0:
+        raise ValueError("clip_grad_norm cannot be combined with optimizer shampoo: grafting "
+                         "gives every conv kernel's step the length of the unclipped gradient")
+    return b2, eps, every
+
+
+def shampoo_block_table(recs):
+    """The block table of the shampoo launches (csrc/shampoo.hip) for `recs`, a list of
+    (offset, segment, R, K): every row-major R x K matrix cut into ceil(R / 64) x ceil(K / 64)
+    blocks, row blocks first, the state slots numbered in table order.  Returns (blocks,
+    SHAMPOO_DTYPE; tensors, SHAMPOO_TENSOR_DTYPE: each matrix's run of blocks)."""
+    B, blocks, tens = SHAMPOO_BLOCK, [], []
+    for off, seg, R, K in recs:
+        tens.append((len(blocks), _ceil(R, B) * _ceil(K, B), seg, 0))
+        for bi in range(_ceil(R, B)):
+            for bj in range(_ceil(K, B)):
+                blocks.append((off + bi * B * K + bj * B, K, min(B, R - bi * B),
+                               min(B, K - bj * B), seg, len(blocks), 0))
+    return np.array(blocks, dtype=SHAMPOO_DTYPE), np.array(tens, dtype=SHAMPOO_TENSOR_DTYPE)
+
+
+def shampoo_tables(train_slots):
+    """shampoo_block_table over the conv kernels of the trainable slots (segment order; the
+    HWIO master of a conv kernel is the row-major R x K matrix, R = kh kw C), plus the segment
+    flags muon_tables gives (int32 per segment, 1 = conv kernel, preconditioned) and the names
+    of the preconditioned tensors in table order."""
+    recs, names, seg = [], [], np.zeros(len(train_slots), np.int32)
+    for i, s in enumerate(train_slots):
+        if s.kind != "conv":
+            continue
+        K = int(s.shape[-1])
+        recs.append((int(s.offset), i, int(s.numel) // K, K))
+        names.append(s.name)
+        seg[i] = 1
+    blocks, tens = shampoo_block_table(recs)
+    return blocks, tens, seg, names
+
+
+def shampoo_identity_roots(blocks):
+    """The initial root slots [nblocks, 64, 64] of one side pair: (PL, PR), the identity on
+    each block's live part, zero elsewhere."""
+    B = SHAMPOO_BLOCK
+    pl, pr = (np.zeros((len(blocks), B, B), np.float32) for _ in range(2))
+    d = np.arange(B)
+    for b in blocks:
+        pl[b["slot"], d[:b["r"]], d[:b["r"]]] = 1.0
+        pr[b["slot"], d[:b["k"]], d[:b["k"]]] = 1.0
+    return pl, pr
+
+
+def shampoo_graft_summary(state):
+    """min / median / max grafting factor over a shampoo_state()["tensors"] dict."""
+    c = sorted(v[2] for v in state.values())
+    if not c:
+        return {}
+    return {"shampoo_graft_min": c[0], "shampoo_graft_median": c[len(c) // 2],
+            "shampoo_graft_max": c[-1]}
 
 
 OPT_FUSED_RMSPROP_REASON = ("optimizer rmsprop: the one-launch optimizer is SGD-momentum; rmsprop "

@@ -711,6 +711,36 @@ class StepRecorder:
                     for i in tiled:
                         out.op_buffers[i] = gb | {"muon"}
                     out.op_buffers[i1] = gb | pb | {"muon", "lr", "gstep"}
+            elif e.shampoo:
+                # five launches (csrc/shampoo.hip) over the block table: statistics, roots (a
+                # no-op on the device unless t % every == 0), direction and block partials,
+                # the per-tensor grafting factor, the flat update (other tensors: mom's).
+                # grad is complete here, as for lars
+                sb, tab, nb = e.shampoo_state_buf, e.shampoo_tab.data_ptr(), len(e.shampoo_blocks)
+                L, Rt, PL, PR = (sb[i].data_ptr() for i in range(4))
+                t = (e.gstep.data_ptr(), e.shampoo_start.data_ptr(), e.shampoo_every)
+                i0 = plan.shampoo_stats(grad, tab, nb, L, Rt, e.shampoo_beta2, 1.0, *t,
+                                        e.shampoo_fail.data_ptr())
+                plan.shampoo_roots(tab, nb, 2, L, Rt, PL, PR, *t, e.shampoo_epsilon,
+                                   e.shampoo_fail.data_ptr())
+                plan.shampoo_precondition(grad, tab, nb, PL, PR, e.shampoo_dir.data_ptr(),
+                                          e.shampoo_part.data_ptr(), 1.0)
+                plan.shampoo_graft(e.shampoo_part.data_ptr(), e.shampoo_ttab.data_ptr(),
+                                   len(e.shampoo_tensors), e.nseg, e.shampoo_out.data_ptr())
+                i1 = plan.shampoo_update_pack(master, grad, mom, e.shampoo_dir.data_ptr(),
+                                              e.params.n_train, *e.sched.launch_args(),
+                                              e.gstep.data_ptr(), e.momentum, e.wd, 1.0,
+                                              e.segs.data_ptr(), e.nseg, e.shampoo_seg.data_ptr(),
+                                              e.shampoo_out.data_ptr(), e.wbf.data_ptr(), sp + 8,
+                                              *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
+                    out.op_buffers[i0] = gb | {"shampoo", "gstep"}
+                    out.op_buffers[i0 + 1] = {"shampoo", "gstep"}
+                    out.op_buffers[i0 + 2] = gb | {"shampoo"}
+                    out.op_buffers[i0 + 3] = {"shampoo"}
+                    out.op_buffers[i1] = gb | pb | {"shampoo", "lr", "gstep"}
             elif e.clip_grad_norm > 0:
                 # as for lars: grad is complete here and every other stream is joined, so
                 # every rank forms the same norm from the same bits

@@ -12,7 +12,10 @@ saves ``<name>/Lion`` in place of ``<name>/Momentum`` (no extra scalars); a run 
 ``--optimizer rmsprop`` saves tf.train.RMSPropOptimizer's slots in their creation order
 (``rms``, then ``mg`` if centered, then ``momentum``): ``<name>/RMSProp`` and
 ``<name>/RMSProp_1``, centered ``<name>/RMSProp``, ``<name>/RMSProp_1`` and
-``<name>/RMSProp_2``, in place of ``<name>/Momentum`` (no extra scalars).  ``max_to_keep``
+``<name>/RMSProp_2``, in place of ``<name>/Momentum`` (no extra scalars); a run with
+``--optimizer shampoo`` keeps ``<name>/Momentum`` and adds, per conv kernel,
+``<name>/shampoo_L``, ``_R``, ``_PL`` and ``_PR`` (each [blocks, 64, 64]) plus the int64
+``shampoo_start_step``.  ``max_to_keep``
 = 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
@@ -50,6 +53,12 @@ def rmsprop_suffixes(centered: bool) -> dict:
     return {"ms": RMSPROP_SUFFIXES[0], "mom": RMSPROP_SUFFIXES[1]}
 
 
+# shampoo's block state per conv kernel, each [blocks, 64, 64], and the step its refresh
+# schedule counts from; the momentum stays ``<name>/Momentum``
+SHAMPOO_SUFFIXES = {"L": "/shampoo_L", "R": "/shampoo_R", "PL": "/shampoo_PL", "PR": "/shampoo_PR"}
+SHAMPOO_START = "shampoo_start_step"
+
+
 def adam_beta_powers(t_done: int, beta1: float, beta2: float):
     """TF 1.12's beta1_power / beta2_power variables after t_done Adam steps: b^(t_done + 1)
     (they start at b and are multiplied by b after every step), from the fp32 betas in fp64,
@@ -60,7 +69,8 @@ def adam_beta_powers(t_done: int, beta1: float, beta2: float):
 
 def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
                 ema: torch.Tensor | None = None, adam: dict | None = None,
-                lion: bool = False, rmsprop: dict | None = None) -> dict[str, np.ndarray]:
+                lion: bool = False, rmsprop: dict | None = None,
+                shampoo: dict | None = None) -> dict[str, np.ndarray]:
     """ParamStore (+flat momentum, +flat EMA shadows, in the same layout) -> {TF name: array}.
     ``ema`` adds ``<name>/ExponentialMovingAverage`` per trainable; without it the entries
     are exactly the reference's.  ``adam`` (an adamw run: {"v": flat second moment,
@@ -70,7 +80,10 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
     Adam steps) and the int64 ``adam_start_step``, which restore goes by.  ``lion`` (a lion
     run): `momentum` is its m and goes out as ``<name>/Lion``, no ``/Momentum``.  ``rmsprop``
     (an rmsprop run: {"ms": flat mean square, "mg": flat mean gradient or None}): `momentum`,
-    ms and mg go out under rmsprop_suffixes(mg is not None), no ``/Momentum``."""
+    ms and mg go out under rmsprop_suffixes(mg is not None), no ``/Momentum``.  ``shampoo`` (a
+    shampoo run: {"L", "R", "PL", "PR": [blocks, 64, 64], "tensors": [(name, block0, nblocks)],
+    "start_step"}): each conv kernel's run of blocks goes out as ``<name>/shampoo_L`` ... and
+    the int64 ``shampoo_start_step`` is added; ``/Momentum`` stays."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
@@ -101,7 +114,41 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
         p1, p2 = adam_beta_powers(int(global_step) - start, adam["beta1"], adam["beta2"])
         out["beta1_power"], out["beta2_power"] = np.array(p1), np.array(p2)
         out[ADAM_START] = np.array(start, dtype=np.int64)
+    if shampoo is not None:
+        for key, suffix in SHAMPOO_SUFFIXES.items():
+            buf = shampoo[key].detach().float().cpu().numpy()
+            for name, b0, nb in shampoo["tensors"]:
+                out[name + suffix] = buf[b0:b0 + nb].copy()
+        out[SHAMPOO_START] = np.array(int(shampoo["start_step"]), dtype=np.int64)
     return out
+
+
+def tf_to_shampoo(tensors: dict, shampoo: dict) -> int:
+    """Load the block state of a shampoo run (state_to_tf's ``shampoo`` dict: its buffers are
+    written in place) from {TF name: array}; returns the step the refresh schedule counts from.
+    With every slot present they are loaded and the start step is the checkpoint's
+    ``shampoo_start_step``.  Otherwise (e.g. a `mom` checkpoint) the statistics start from
+    zero, the roots from the identity (``shampoo["identity"]``: (PL, PR) arrays) and the count
+    at the checkpoint's global_step; one log line says so."""
+    gs = int(np.asarray(tensors.get("global_step", 0)))
+    keys = [name + suffix for name, _, _ in shampoo["tensors"] for suffix in SHAMPOO_SUFFIXES.values()]
+    absent = [k for k in keys if k not in tensors]
+    if absent:
+        print(f"INFO:tensorflow:checkpoint has no shampoo slots for {len(absent)} of {len(keys)} "
+              f"entries (e.g. {absent[0]}): the statistics start from zero, the roots from the "
+              f"identity and the refresh schedule restarts at step {gs}", flush=True)
+        shampoo["L"].data.zero_()
+        shampoo["R"].data.zero_()
+        for key, a in zip(("PL", "PR"), shampoo["identity"]):
+            shampoo[key].data.copy_(torch.from_numpy(a))
+        return gs
+    for key, suffix in SHAMPOO_SUFFIXES.items():
+        for name, b0, nb in shampoo["tensors"]:
+            a = np.asarray(tensors[name + suffix], dtype=np.float32)
+            if a.shape != (nb, 64, 64):
+                raise ValueError(f"{name + suffix}: shape {a.shape}, expected {(nb, 64, 64)}")
+            shampoo[key].data[b0:b0 + nb].copy_(torch.from_numpy(a))
+    return int(np.asarray(tensors.get(SHAMPOO_START, 0)))
 
 
 def tf_to_adam(tensors: dict, store, m: torch.Tensor, v: torch.Tensor) -> int:

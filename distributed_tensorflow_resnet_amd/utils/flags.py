@@ -20,6 +20,9 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --optimizer muon   Muon: conv kernels move along their momentum orthogonalised by Newton-Schulz
                      on the matrix cores: --muon_momentum, --muon_nesterov, --muon_ns_steps,
                      --muon_aux_lr_scale; --muon_tiled for the ImageNet networks
+  --optimizer shampoo  blocked Shampoo with SGD grafting: fp32 inverse fourth roots of 64 x 64
+                     statistics blocks on the matrix cores: --shampoo_beta2, --shampoo_epsilon,
+                     --shampoo_precond_every
   --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
                      one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
                      --rmsprop_wd, --rmsprop_decay_skip
@@ -257,6 +260,14 @@ class FlagParser(argparse.ArgumentParser):
                            getattr(ns, "optimizer", "mom"))
             except ValueError as e:
                 self.error(str(e))
+        if hasattr(ns, "shampoo_beta2"):
+            from ..train.layout import check_shampoo
+
+            try:
+                check_shampoo(ns.shampoo_beta2, ns.shampoo_epsilon, ns.shampoo_precond_every,
+                              getattr(ns, "clip_grad_norm", 0.0), getattr(ns, "optimizer", "mom"))
+            except ValueError as e:
+                self.error(str(e))
         if hasattr(ns, "adam_trust"):
             from ..train.layout import check_adam_trust
 
@@ -414,7 +425,7 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                "global_step (no per-step host work; the order is a function of --seed and "
                "the step, so a resumed run continues its epoch).  Ignored otherwise.")
     p.add_argument("--weight_decay", type=float, default=d["weight_decay"])
-    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion", "muon", "rmsprop"),
+    p.add_argument("--optimizer", default="mom", choices=("mom", "sgd", "lars", "adamw", "lion", "muon", "shampoo", "rmsprop"),
                    help="mom / sgd: the reference's optimizers.  lars: SGD-momentum at a "
                         "per-tensor rate lr * trust, trust = eeta * |w| / (|g| + wd * |w| + "
                         "epsilon) (layer-wise adaptive rate scaling, for large global batches).  "
@@ -433,7 +444,22 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
                         "Nesterov momentum orthogonalised by a quintic Newton-Schulz iteration "
                         "(bf16 on the matrix cores), at lr * sqrt(max(1, K / R)) with decoupled "
                         "weight decay; BN and dense tensors take mom's update at lr * "
-                        "--muon_aux_lr_scale.  Not with --clip_grad_norm.")
+                        "--muon_aux_lr_scale.  Not with --clip_grad_norm.  shampoo (Gupta et "
+                        "al. 2018; Anil et al. 2020): every conv kernel, cut into 64 x 64 "
+                        "blocks, moves along PL G PR with PL, PR the inverse fourth roots of the "
+                        "blocks' gradient statistics (fp32 on the matrix cores, refreshed every "
+                        "--shampoo_precond_every steps), rescaled per tensor to the length of "
+                        "the SGD step (grafting), so the presets' rates stay valid; BN and dense "
+                        "tensors take mom's update.  The state is four times the conv weights.  "
+                        "Not with --clip_grad_norm.")
+    p.add_argument("--shampoo_beta2", type=float, default=1.0,
+                   help="shampoo: decay of the statistics, in (0, 1]; 1 (default) sums them.")
+    p.add_argument("--shampoo_epsilon", type=float, default=1e-6,
+                   help="shampoo: the ridge eps * ||A||_F added to a statistic before its root, "
+                        "positive and finite.")
+    p.add_argument("--shampoo_precond_every", type=int, default=10,
+                   help="shampoo: steps between two refreshes of the roots, >= 1.  Accepted and "
+                        "unused with another optimizer, as the other two.")
     p.add_argument("--muon_momentum", type=float, default=0.95,
                    help="muon: momentum of the conv kernels, in [0, 1) (the other tensors keep "
                         "mom's 0.9).")

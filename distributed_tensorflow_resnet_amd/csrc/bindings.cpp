@@ -413,11 +413,12 @@ static Launch mk_avgpool_bwd(ptr_t dp, ptr_t dx, int N, int HW, int C) {
   return [=](hipStream_t s) { avgpool_bwd(P<const bf16>(dp), P<bf16>(dx), N, HW, C, s); };
 }
 
-// The loss-head ops take three trailing arguments that default to (0, 0, null):
-// label_smoothing in [0, 1), topk (k of the in-top-k count, 0: none) and topk_out (the
-// count; softmax_xent_reduce takes topk_out alone, head_fused the first two -- its flags
-// go to the workspace).  Each op is registered at both arities, so a call without them
-// means what it always meant.
+// The loss-head ops take optional trailing arguments in four groups, each registered as an
+// arity of its own (kXentTail, kHeadTail below): a call that stops before a group means what it
+// meant before the group existed.
+// First, three that default to (0, 0, null): label_smoothing in [0, 1), topk (k of the
+// in-top-k count, 0: none) and topk_out (the count; softmax_xent_reduce takes topk_out
+// alone, head_fused the first two -- its flags go to the workspace).
 static void check_xent_opts(const char* op, float label_smoothing, int topk, ptr_t topk_out) {
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || topk < 0 || (topk_out && topk == 0))
     throw std::invalid_argument(std::string(op) + ": label_smoothing in [0, 1), topk >= 0 "
@@ -425,15 +426,15 @@ static void check_xent_opts(const char* op, float label_smoothing, int topk, ptr
 }
 
 // Mixup (xent_row.h): two more trailing arguments, labels_b ([N] partner labels) and mix_lam
-// ([N] fp32 lam per row), both or neither; a third arity of the same ops.
+// ([N] fp32 lam per row), both or neither (null, null).
 static void check_mix_ptrs(const char* op, ptr_t labels_b, ptr_t mix_lam) {
   if ((labels_b == 0) != (mix_lam == 0))
     throw std::invalid_argument(std::string(op) + ": labels_b and mix_lam go together");
 }
 
 // Distillation (xent_row.h): three more trailing arguments, teacher ([N][ld] fp32 teacher
-// logits, null: none), kd_alpha in [0, 1] and kd_inv_tau = 1 / temperature > 0; a fourth
-// arity of the same ops.  Without a teacher kd_alpha must be 0 and the rows are the old ones.
+// logits, null: none), kd_alpha in [0, 1] and kd_inv_tau = 1 / temperature > 0 (null, 0, 1).
+// Without a teacher kd_alpha must be 0 and the rows are the old ones.
 static KdArgs mk_kd(const char* op, ptr_t teacher, float kd_alpha, float kd_inv_tau) {
   KdArgs kd;
   kd.teacher = P<const float>(teacher);
@@ -444,8 +445,8 @@ static KdArgs mk_kd(const char* op, ptr_t teacher, float kd_alpha, float kd_inv_
 }
 
 // AugMix's Jensen-Shannon term (xent_row.h): two more trailing arguments, jsd_B (N == 3 *
-// jsd_B rows in triples n, n + B, n + 2B; 0: off) and jsd_weight >= 0; a fifth arity of the
-// same ops.  Not with a teacher or a mixup pair.
+// jsd_B rows in triples n, n + B, n + 2B; 0: off) and jsd_weight >= 0 (0, 0).  Not with a
+// teacher or a mixup pair.
 static JsdArgs mk_jsd(const char* op, int jsd_B, float jsd_weight, int N, const KdArgs& kd,
                       ptr_t labels_b) {
   JsdArgs jsd;
@@ -455,12 +456,20 @@ static JsdArgs mk_jsd(const char* op, int jsd_B, float jsd_weight, int N, const 
   return jsd;
 }
 
-static Launch mk_softmax_xent_jsd(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
-                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
-                                  ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
-                                  float jsd_weight) {
+// The defaults of the groups above, in argument order; head_fused has no topk_out.
+static const auto kMixKdJsdTail = std::make_tuple(
+    ptr_t(0), ptr_t(0),    // labels_b, mix_lam
+    ptr_t(0), 0.f, 1.f,    // teacher, kd_alpha, kd_inv_tau
+    0, 0.f);               // jsd_B, jsd_weight
+static const auto kXentTail = std::tuple_cat(std::make_tuple(0.f, 0, ptr_t(0)), kMixKdJsdTail);
+static const auto kHeadTail = std::tuple_cat(std::make_tuple(0.f, 0), kMixKdJsdTail);
+
+static Launch mk_softmax_xent(ptr_t logits, int ld, ptr_t labels, int N, int classes,
+                              ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
+                              float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
+                              int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
+                              ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
+                              float jsd_weight) {
   check_xent_opts("softmax_xent", label_smoothing, topk, topk_out);
   check_mix_ptrs("softmax_xent", labels_b, mix_lam);
   const KdArgs kd = mk_kd("softmax_xent", teacher, kd_alpha, kd_inv_tau);
@@ -473,63 +482,24 @@ static Launch mk_softmax_xent_jsd(ptr_t logits, int ld, ptr_t labels, int N, int
   };
 }
 
-static Launch mk_softmax_xent_kd(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                                 ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                                 float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
-                                 int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam,
-                                 ptr_t teacher, float kd_alpha, float kd_inv_tau) {
-  return mk_softmax_xent_jsd(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
-                             grad_scale, probs, ws, label_smoothing, topk, topk_out, labels_b,
-                             mix_lam, teacher, kd_alpha, kd_inv_tau, 0, 0.f);
-}
-
-static Launch mk_softmax_xent_mix(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                                  ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                                  float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
-                                  int topk, ptr_t topk_out, ptr_t labels_b, ptr_t mix_lam) {
-  return mk_softmax_xent_kd(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
-                            grad_scale, probs, ws, label_smoothing, topk, topk_out, labels_b,
-                            mix_lam, 0, 0.f, 1.f);
-}
-
-static Launch mk_softmax_xent_ls(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                                 ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                                 float grad_scale, ptr_t probs, ptr_t ws, float label_smoothing,
-                                 int topk, ptr_t topk_out) {
-  return mk_softmax_xent_mix(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
-                             grad_scale, probs, ws, label_smoothing, topk, topk_out, 0, 0);
-}
-
-static Launch mk_softmax_xent(ptr_t logits, int ld, ptr_t labels, int N, int classes,
-                              ptr_t loss_sum, ptr_t correct, ptr_t dlogits, ptr_t dbias,
-                              float grad_scale, ptr_t probs, ptr_t ws) {
-  return mk_softmax_xent_ls(logits, ld, labels, N, classes, loss_sum, correct, dlogits, dbias,
-                            grad_scale, probs, ws, 0.f, 0, 0);
-}
-
-static Launch mk_softmax_xent_reduce_k(ptr_t ws, int ld, int N, int classes, ptr_t loss_sum,
-                                       ptr_t correct, ptr_t dbias, ptr_t topk_out) {
+static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t loss_sum,
+                                     ptr_t correct, ptr_t dbias, ptr_t topk_out) {
   return [=](hipStream_t s) {
     softmax_xent_reduce(P<const float>(ws), ld, N, classes, P<float>(loss_sum), P<float>(correct),
                         P<float>(dbias), P<float>(topk_out), s);
   };
 }
 
-static Launch mk_softmax_xent_reduce(ptr_t ws, int ld, int N, int classes, ptr_t loss_sum,
-                                     ptr_t correct, ptr_t dbias) {
-  return mk_softmax_xent_reduce_k(ws, ld, N, classes, loss_sum, correct, dbias, 0);
-}
-
 // head_fused(x, bn=[acc, gamma, beta, mmean, mvar, mean, rstd, scale, shift], momentum, eps,
 //            update_moving, w_hwio, bias, labels, shape=[N, HW, C, classes, kpad], grad_scale,
 //            out=[pooled, dlogits, ws, dact, bacc][, label_smoothing, topk[, labels_b, mix_lam
 //            [, teacher, kd_alpha, kd_inv_tau[, jsd_B, jsd_weight]]]])
-static Launch mk_head_fused_jsd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
-                                ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
-                                float jsd_weight) {
+static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
+                            int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
+                            std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
+                            float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
+                            ptr_t teacher, float kd_alpha, float kd_inv_tau, int jsd_B,
+                            float jsd_weight) {
   check_xent_opts("head_fused", label_smoothing, topk, 0);
   check_mix_ptrs("head_fused", labels_b, mix_lam);
   const KdArgs kd = mk_kd("head_fused", teacher, kd_alpha, kd_inv_tau);
@@ -571,41 +541,6 @@ static Launch mk_head_fused_jsd(ptr_t x, std::vector<ptr_t> bn, float momentum, 
     throw std::invalid_argument("head_fused: unsupported head shape");
   const JsdArgs jsd = mk_jsd("head_fused", jsd_B, jsd_weight, a.N, kd, labels_b);
   return [a, kd, jsd](hipStream_t s) { head_fused(a, s, kd, jsd); };
-}
-
-static Launch mk_head_fused_kd(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                               float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam,
-                               ptr_t teacher, float kd_alpha, float kd_inv_tau) {
-  return mk_head_fused_jsd(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
-                           std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
-                           labels_b, mix_lam, teacher, kd_alpha, kd_inv_tau, 0, 0.f);
-}
-
-static Launch mk_head_fused_mix(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                                int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                                std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                                float label_smoothing, int topk, ptr_t labels_b, ptr_t mix_lam) {
-  return mk_head_fused_kd(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
-                          std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
-                          labels_b, mix_lam, 0, 0.f, 1.f);
-}
-
-static Launch mk_head_fused_ls(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                               int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                               std::vector<int> shape, float grad_scale, std::vector<ptr_t> out,
-                               float label_smoothing, int topk) {
-  return mk_head_fused_mix(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
-                           std::move(shape), grad_scale, std::move(out), label_smoothing, topk,
-                           0, 0);
-}
-
-static Launch mk_head_fused(ptr_t x, std::vector<ptr_t> bn, float momentum, float eps,
-                            int update_moving, ptr_t w, ptr_t bias, ptr_t labels,
-                            std::vector<int> shape, float grad_scale, std::vector<ptr_t> out) {
-  return mk_head_fused_ls(x, std::move(bn), momentum, eps, update_moving, w, bias, labels,
-                          std::move(shape), grad_scale, std::move(out), 0.f, 0);
 }
 
 // Persistent small-batch CIFAR step (prn_fwd.hip, prn_bwd.hip).  mode 0: forward launch,
@@ -812,14 +747,16 @@ static Launch mk_ohwi_pack(ptr_t master, ptr_t segs, ptr_t tile0, int nseg, long
   };
 }
 
-// The four ops that evaluate the schedule are bound twice: with the piecewise schedule's
-// six arguments alone, and with one trailing LrDecayArgs.
-static Launch mk_sgd_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                       long long warm_steps, float warm_from, float warm_to,
-                                       std::vector<long long> bounds, std::vector<float> vals,
-                                       ptr_t gstep, float momentum, float wd, float grad_scale,
-                                       int use_momentum, ptr_t segs, int nseg, ptr_t bf,
-                                       ptr_t lr_out, int update, LrDecayArgs decay) {
+// The ops that evaluate the schedule take the piecewise schedule's six arguments and one
+// optional trailing LrDecayArgs: each is registered without it (kPiecewiseTail) and with it.
+static const std::tuple<LrDecayArgs> kPiecewiseTail{kPiecewise};
+
+static Launch mk_sgd_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                 long long warm_steps, float warm_from, float warm_to,
+                                 std::vector<long long> bounds, std::vector<float> vals,
+                                 ptr_t gstep, float momentum, float wd, float grad_scale,
+                                 int use_momentum, ptr_t segs, int nseg, ptr_t bf, ptr_t lr_out,
+                                 int update, LrDecayArgs decay) {
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     sgd_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
@@ -828,24 +765,12 @@ static Launch mk_sgd_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long
   };
 }
 
-static Launch mk_sgd_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                 long long warm_steps, float warm_from, float warm_to,
-                                 std::vector<long long> bounds, std::vector<float> vals,
-                                 ptr_t gstep, float momentum, float wd, float grad_scale,
-                                 int use_momentum, ptr_t segs, int nseg, ptr_t bf, ptr_t lr_out,
-                                 int update) {
-  return mk_sgd_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
-                                  bounds, vals, gstep, momentum, wd, grad_scale, use_momentum,
-                                  segs, nseg, bf, lr_out, update, kPiecewise);
-}
-
-static Launch mk_sgd_tiles_decay(ptr_t master, ptr_t grad, ptr_t mom, float init,
-                                 long long warm_steps, float warm_from, float warm_to,
-                                 std::vector<long long> bounds, std::vector<float> vals,
-                                 ptr_t gstep, float momentum, float wd, float grad_scale,
-                                 int use_momentum, ptr_t segs, ptr_t work, ptr_t blk_seg,
-                                 int nblocks, ptr_t bf, ptr_t lr_out, ptr_t ticket, ptr_t gin,
-                                 ptr_t gout, int pack, LrDecayArgs decay) {
+static Launch mk_sgd_tiles(ptr_t master, ptr_t grad, ptr_t mom, float init, long long warm_steps,
+                           float warm_from, float warm_to, std::vector<long long> bounds,
+                           std::vector<float> vals, ptr_t gstep, float momentum, float wd,
+                           float grad_scale, int use_momentum, ptr_t segs, ptr_t work,
+                           ptr_t blk_seg, int nblocks, ptr_t bf, ptr_t lr_out, ptr_t ticket,
+                           ptr_t gin, ptr_t gout, int pack, LrDecayArgs decay) {
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     sgd_tiles(P<float>(master), P<float>(grad), P<float>(mom), sc, P<long long>(gstep),
@@ -853,17 +778,6 @@ static Launch mk_sgd_tiles_decay(ptr_t master, ptr_t grad, ptr_t mom, float init
               P<const OptWork>(work), P<const int>(blk_seg), nblocks, P<bf16>(bf),
               P<float>(lr_out), P<unsigned>(ticket), P<const bf16>(gin), P<bf16>(gout), pack, s);
   };
-}
-
-static Launch mk_sgd_tiles(ptr_t master, ptr_t grad, ptr_t mom, float init,
-                           long long warm_steps, float warm_from, float warm_to,
-                           std::vector<long long> bounds, std::vector<float> vals, ptr_t gstep,
-                           float momentum, float wd, float grad_scale, int use_momentum,
-                           ptr_t segs, ptr_t work, ptr_t blk_seg, int nblocks, ptr_t bf,
-                           ptr_t lr_out, ptr_t ticket, ptr_t gin, ptr_t gout, int pack) {
-  return mk_sgd_tiles_decay(master, grad, mom, init, warm_steps, warm_from, warm_to, bounds, vals,
-                            gstep, momentum, wd, grad_scale, use_momentum, segs, work, blk_seg,
-                            nblocks, bf, lr_out, ticket, gin, gout, pack, kPiecewise);
 }
 
 static Launch mk_lars_norms(ptr_t master, ptr_t grad, ptr_t segs, ptr_t lsegs, ptr_t blk_seg,
@@ -884,12 +798,12 @@ static Launch mk_lars_trust(ptr_t part, ptr_t lsegs, int nseg, float eeta, float
   };
 }
 
-static Launch mk_lars_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                        long long warm_steps, float warm_from, float warm_to,
-                                        std::vector<long long> bounds, std::vector<float> vals,
-                                        ptr_t gstep, float momentum, float wd, float grad_scale,
-                                        ptr_t segs, int nseg, ptr_t trust, ptr_t bf,
-                                        ptr_t lr_out, LrDecayArgs decay) {
+static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float momentum, float wd, float grad_scale,
+                                  ptr_t segs, int nseg, ptr_t trust, ptr_t bf, ptr_t lr_out,
+                                  LrDecayArgs decay) {
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     lars_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), n, sc,
@@ -897,16 +811,6 @@ static Launch mk_lars_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, lon
                      P<const ParamSeg>(segs), nseg, P<const float>(trust), P<bf16>(bf),
                      P<float>(lr_out), s);
   };
-}
-
-static Launch mk_lars_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                  long long warm_steps, float warm_from, float warm_to,
-                                  std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, float momentum, float wd, float grad_scale,
-                                  ptr_t segs, int nseg, ptr_t trust, ptr_t bf, ptr_t lr_out) {
-  return mk_lars_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
-                                   bounds, vals, gstep, momentum, wd, grad_scale, segs, nseg,
-                                   trust, bf, lr_out, kPiecewise);
 }
 
 static Launch mk_grad_sqnorm(ptr_t grad, long long n, ptr_t part) {
@@ -921,12 +825,12 @@ static Launch mk_clip_scale(ptr_t part, int nchunks, float c, ptr_t out) {
   return [=](hipStream_t s) { clip_scale(P<const double>(part), nchunks, c, P<float>(out), s); };
 }
 
-static Launch mk_sgd_clip_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, long n,
-                                            float init, long long warm_steps, float warm_from,
-                                            float warm_to, std::vector<long long> bounds,
-                                            std::vector<float> vals, ptr_t gstep, float momentum,
-                                            float wd, ptr_t clip, int use_momentum, ptr_t segs,
-                                            int nseg, ptr_t bf, ptr_t lr_out, LrDecayArgs decay) {
+static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
+                                      long long warm_steps, float warm_from, float warm_to,
+                                      std::vector<long long> bounds, std::vector<float> vals,
+                                      ptr_t gstep, float momentum, float wd, ptr_t clip,
+                                      int use_momentum, ptr_t segs, int nseg, ptr_t bf,
+                                      ptr_t lr_out, LrDecayArgs decay) {
   if (!clip) throw std::invalid_argument("sgd_clip_update_pack: no clip slot");
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
@@ -937,40 +841,59 @@ static Launch mk_sgd_clip_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom,
   };
 }
 
-static Launch mk_sgd_clip_update_pack(ptr_t master, ptr_t grad, ptr_t mom, long n, float init,
-                                      long long warm_steps, float warm_from, float warm_to,
-                                      std::vector<long long> bounds, std::vector<float> vals,
-                                      ptr_t gstep, float momentum, float wd, ptr_t clip,
-                                      int use_momentum, ptr_t segs, int nseg, ptr_t bf,
-                                      ptr_t lr_out) {
-  return mk_sgd_clip_update_pack_decay(master, grad, mom, n, init, warm_steps, warm_from, warm_to,
-                                       bounds, vals, gstep, momentum, wd, clip, use_momentum,
-                                       segs, nseg, bf, lr_out, kPiecewise);
+// The argument checks the flat-update ops below share; `op` names the op in the message.
+// `names` lists the buffers as the op's message does.
+static void check_aligned16(const char* op, const char* names, std::initializer_list<ptr_t> ptrs) {
+  ptr_t any = 0;
+  for (ptr_t p : ptrs) any |= p;
+  if (any & 15)
+    throw std::invalid_argument(std::string(op) + ": " + names + " must be 16-byte aligned");
+}
+
+static void check_non_null(const char* op, std::initializer_list<ptr_t> ptrs) {
+  for (ptr_t p : ptrs)
+    if (!p) throw std::invalid_argument(std::string(op) + ": null buffer");
+}
+
+static void check_flat_size(const char* op, long n, int nseg) {
+  if (n < 0 || nseg <= 0) throw std::invalid_argument(std::string(op) + ": n >= 0 and nseg > 0");
+}
+
+static void check_unit_coefs(const char* op, const char* a_name, float a, const char* b_name,
+                             float b) {
+  if (!(a >= 0.f && a < 1.f) || !(b >= 0.f && b < 1.f))
+    throw std::invalid_argument(std::string(op) + ": " + a_name + " and " + b_name + " in [0, 1)");
+}
+
+static void check_epsilon(const char* op, float epsilon) {
+  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
+    throw std::invalid_argument(std::string(op) + ": epsilon must be positive and finite");
+}
+
+// decay_mode "decoupled" | "l2": whether it is the decoupled one
+static int decay_mode_decoupled(const char* op, const std::string& decay_mode) {
+  if (decay_mode != "decoupled" && decay_mode != "l2")
+    throw std::invalid_argument(std::string(op) + ": decay mode '" + decay_mode +
+                                "' (decoupled, l2)");
+  return decay_mode == "decoupled";
 }
 
 // adam_update_pack: clip = 0 takes grad_scale, else the scale is the device value clip[1];
 // decay_mode "decoupled" | "l2"
-static Launch mk_adam_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, long n,
-                                        float init, long long warm_steps, float warm_from,
-                                        float warm_to, std::vector<long long> bounds,
-                                        std::vector<float> vals, ptr_t gstep, ptr_t start_step,
-                                        float beta1, float beta2, float epsilon,
-                                        float grad_scale, ptr_t clip, std::string decay_mode,
-                                        ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
-                                        ptr_t lr_out, ptr_t adam_out, LrDecayArgs decay) {
-  if ((master | grad | m | v) & 15)
-    throw std::invalid_argument("adam_update_pack: master, grad, m and v must be 16-byte aligned");
-  if (!master || !grad || !m || !v || !segs || !wd_seg || !gstep || !start_step)
-    throw std::invalid_argument("adam_update_pack: null buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("adam_update_pack: n >= 0 and nseg > 0");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
-    throw std::invalid_argument("adam_update_pack: beta1 and beta2 in [0, 1)");
-  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
-    throw std::invalid_argument("adam_update_pack: epsilon must be positive and finite");
-  if (decay_mode != "decoupled" && decay_mode != "l2")
-    throw std::invalid_argument("adam_update_pack: decay mode '" + decay_mode +
-                                "' (decoupled, l2)");
-  const int decoupled = decay_mode == "decoupled";
+static Launch mk_adam_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                  float epsilon, float grad_scale, ptr_t clip,
+                                  std::string decay_mode, ptr_t segs, int nseg, ptr_t wd_seg,
+                                  ptr_t bf, ptr_t lr_out, ptr_t adam_out, LrDecayArgs decay) {
+  const char* op = "adam_update_pack";
+  check_aligned16(op, "master, grad, m and v", {master, grad, m, v});
+  check_non_null(op, {master, grad, m, v, segs, wd_seg, gstep, start_step});
+  check_flat_size(op, n, nseg);
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
+  check_epsilon(op, epsilon);
+  const int decoupled = decay_mode_decoupled(op, decay_mode);
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     adam_update_pack(P<float>(master), P<const float>(grad), P<float>(m), P<float>(v), n, sc,
@@ -981,33 +904,18 @@ static Launch mk_adam_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, ptr_t
   };
 }
 
-static Launch mk_adam_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, long n, float init,
+// lion_update_pack: clip as in adam_update_pack
+static Launch mk_lion_update_pack(ptr_t master, ptr_t grad, ptr_t m, long n, float init,
                                   long long warm_steps, float warm_from, float warm_to,
                                   std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
-                                  float epsilon, float grad_scale, ptr_t clip,
-                                  std::string decay_mode, ptr_t segs, int nseg, ptr_t wd_seg,
-                                  ptr_t bf, ptr_t lr_out, ptr_t adam_out) {
-  return mk_adam_update_pack_decay(master, grad, m, v, n, init, warm_steps, warm_from, warm_to,
-                                   bounds, vals, gstep, start_step, beta1, beta2, epsilon,
-                                   grad_scale, clip, decay_mode, segs, nseg, wd_seg, bf, lr_out,
-                                   adam_out, kPiecewise);
-}
-
-// lion_update_pack: adam_update_pack's alignment and coefficient checks; clip as there
-static Launch mk_lion_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, long n, float init,
-                                        long long warm_steps, float warm_from, float warm_to,
-                                        std::vector<long long> bounds, std::vector<float> vals,
-                                        ptr_t gstep, float beta1, float beta2, float grad_scale,
-                                        ptr_t clip, ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
-                                        ptr_t lr_out, LrDecayArgs decay) {
-  if ((master | grad | m) & 15)
-    throw std::invalid_argument("lion_update_pack: master, grad and m must be 16-byte aligned");
-  if (!master || !grad || !m || !segs || !wd_seg || !gstep)
-    throw std::invalid_argument("lion_update_pack: null buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("lion_update_pack: n >= 0 and nseg > 0");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
-    throw std::invalid_argument("lion_update_pack: beta1 and beta2 in [0, 1)");
+                                  ptr_t gstep, float beta1, float beta2, float grad_scale,
+                                  ptr_t clip, ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
+                                  ptr_t lr_out, LrDecayArgs decay) {
+  const char* op = "lion_update_pack";
+  check_aligned16(op, "master, grad and m", {master, grad, m});
+  check_non_null(op, {master, grad, m, segs, wd_seg, gstep});
+  check_flat_size(op, n, nseg);
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     lion_update_pack(P<float>(master), P<const float>(grad), P<float>(m), n, sc,
@@ -1017,40 +925,24 @@ static Launch mk_lion_update_pack_decay(ptr_t master, ptr_t grad, ptr_t m, long 
   };
 }
 
-static Launch mk_lion_update_pack(ptr_t master, ptr_t grad, ptr_t m, long n, float init,
-                                  long long warm_steps, float warm_from, float warm_to,
-                                  std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, float beta1, float beta2, float grad_scale,
-                                  ptr_t clip, ptr_t segs, int nseg, ptr_t wd_seg, ptr_t bf,
-                                  ptr_t lr_out) {
-  return mk_lion_update_pack_decay(master, grad, m, n, init, warm_steps, warm_from, warm_to,
-                                   bounds, vals, gstep, beta1, beta2, grad_scale, clip, segs,
-                                   nseg, wd_seg, bf, lr_out, kPiecewise);
-}
-
-// rmsprop_update_pack: lion_update_pack's alignment and coefficient checks, adam_update_pack's
-// epsilon and decay-mode ("l2" | "decoupled") checks; mg is needed only when centered
-static Launch mk_rmsprop_update_pack_decay(ptr_t master, ptr_t grad, ptr_t ms, ptr_t mg,
-                                           ptr_t mom, long n, float init, long long warm_steps,
-                                           float warm_from, float warm_to,
-                                           std::vector<long long> bounds, std::vector<float> vals,
-                                           ptr_t gstep, float rho, float momentum, float epsilon,
-                                           float grad_scale, ptr_t clip, int centered,
-                                           std::string decay_mode, ptr_t segs, int nseg,
-                                           ptr_t wd_seg, ptr_t bf, ptr_t lr_out,
-                                           LrDecayArgs decay) {
-  if ((master | grad | ms | mom | (centered ? mg : 0)) & 15)
-    throw std::invalid_argument(
-        "rmsprop_update_pack: master, grad, ms, mom (and mg) must be 16-byte aligned");
-  if (!master || !grad || !ms || !mom || !segs || !wd_seg || !gstep)
-    throw std::invalid_argument("rmsprop_update_pack: null buffer");
+// rmsprop_update_pack: decay_mode "l2" | "decoupled" (its message lists them in that order, so
+// that check stays here); mg is needed only when centered
+static Launch mk_rmsprop_update_pack(ptr_t master, ptr_t grad, ptr_t ms, ptr_t mg, ptr_t mom,
+                                     long n, float init, long long warm_steps, float warm_from,
+                                     float warm_to, std::vector<long long> bounds,
+                                     std::vector<float> vals, ptr_t gstep, float rho,
+                                     float momentum, float epsilon, float grad_scale, ptr_t clip,
+                                     int centered, std::string decay_mode, ptr_t segs, int nseg,
+                                     ptr_t wd_seg, ptr_t bf, ptr_t lr_out, LrDecayArgs decay) {
+  const char* op = "rmsprop_update_pack";
+  check_aligned16(op, "master, grad, ms, mom (and mg)",
+                  {master, grad, ms, mom, centered ? mg : 0});
+  check_non_null(op, {master, grad, ms, mom, segs, wd_seg, gstep});
   if (centered && !mg)
     throw std::invalid_argument("rmsprop_update_pack: centered needs the mg buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("rmsprop_update_pack: n >= 0 and nseg > 0");
-  if (!(rho >= 0.f && rho < 1.f) || !(momentum >= 0.f && momentum < 1.f))
-    throw std::invalid_argument("rmsprop_update_pack: rho and momentum in [0, 1)");
-  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
-    throw std::invalid_argument("rmsprop_update_pack: epsilon must be positive and finite");
+  check_flat_size(op, n, nseg);
+  check_unit_coefs(op, "rho", rho, "momentum", momentum);
+  check_epsilon(op, epsilon);
   if (decay_mode != "decoupled" && decay_mode != "l2")
     throw std::invalid_argument("rmsprop_update_pack: decay mode '" + decay_mode +
                                 "' (l2, decoupled)");
@@ -1063,19 +955,6 @@ static Launch mk_rmsprop_update_pack_decay(ptr_t master, ptr_t grad, ptr_t ms, p
                         P<const ParamSeg>(segs), nseg, P<const float>(wd_seg), P<bf16>(bf),
                         P<float>(lr_out), s);
   };
-}
-
-static Launch mk_rmsprop_update_pack(ptr_t master, ptr_t grad, ptr_t ms, ptr_t mg, ptr_t mom,
-                                     long n, float init, long long warm_steps, float warm_from,
-                                     float warm_to, std::vector<long long> bounds,
-                                     std::vector<float> vals, ptr_t gstep, float rho,
-                                     float momentum, float epsilon, float grad_scale, ptr_t clip,
-                                     int centered, std::string decay_mode, ptr_t segs, int nseg,
-                                     ptr_t wd_seg, ptr_t bf, ptr_t lr_out) {
-  return mk_rmsprop_update_pack_decay(master, grad, ms, mg, mom, n, init, warm_steps, warm_from,
-                                      warm_to, bounds, vals, gstep, rho, momentum, epsilon,
-                                      grad_scale, clip, centered, decay_mode, segs, nseg, wd_seg,
-                                      bf, lr_out, kPiecewise);
 }
 
 // The Muon launches (muon.hip).  rows / cols: the host's copy of the device table's R and K,
@@ -1101,18 +980,16 @@ static Launch mk_muon_orthogonalize(ptr_t grad, ptr_t mom, ptr_t dir, ptr_t tab,
   };
 }
 
-static Launch mk_muon_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
-                                        float init, long long warm_steps, float warm_from,
-                                        float warm_to, std::vector<long long> bounds,
-                                        std::vector<float> vals, ptr_t gstep, float momentum,
-                                        float wd, float aux_scale, float grad_scale, ptr_t segs,
-                                        int nseg, ptr_t muon_seg, ptr_t q_seg, ptr_t bf,
-                                        ptr_t lr_out, LrDecayArgs decay) {
-  if ((master | grad | mom | dir) & 15)
-    throw std::invalid_argument("muon_update_pack: master, grad, mom and dir must be 16-byte aligned");
-  if (!master || !grad || !mom || !dir || !segs || !muon_seg || !q_seg || !gstep)
-    throw std::invalid_argument("muon_update_pack: null buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("muon_update_pack: n >= 0 and nseg > 0");
+static Launch mk_muon_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                  float init, long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, float momentum, float wd, float aux_scale,
+                                  float grad_scale, ptr_t segs, int nseg, ptr_t muon_seg,
+                                  ptr_t q_seg, ptr_t bf, ptr_t lr_out, LrDecayArgs decay) {
+  const char* op = "muon_update_pack";
+  check_aligned16(op, "master, grad, mom and dir", {master, grad, mom, dir});
+  check_non_null(op, {master, grad, mom, dir, segs, muon_seg, q_seg, gstep});
+  check_flat_size(op, n, nseg);
   if (!(aux_scale > 0.f)) throw std::invalid_argument("muon_update_pack: aux_scale > 0");
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
@@ -1121,17 +998,6 @@ static Launch mk_muon_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, ptr
                      P<const ParamSeg>(segs), nseg, P<const int>(muon_seg), P<const float>(q_seg),
                      P<bf16>(bf), P<float>(lr_out), s);
   };
-}
-
-static Launch mk_muon_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
-                                  float init, long long warm_steps, float warm_from, float warm_to,
-                                  std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, float momentum, float wd, float aux_scale,
-                                  float grad_scale, ptr_t segs, int nseg, ptr_t muon_seg,
-                                  ptr_t q_seg, ptr_t bf, ptr_t lr_out) {
-  return mk_muon_update_pack_decay(master, grad, mom, dir, n, init, warm_steps, warm_from, warm_to,
-                                   bounds, vals, gstep, momentum, wd, aux_scale, grad_scale, segs,
-                                   nseg, muon_seg, q_seg, bf, lr_out, kPiecewise);
 }
 
 // The Shampoo launches (shampoo.hip).  The tables are device copies of what train/layout.py
@@ -1193,18 +1059,16 @@ static Launch mk_shampoo_graft(ptr_t part, ptr_t ttab, int ntensors, int nseg, p
   };
 }
 
-static Launch mk_shampoo_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
-                                           float init, long long warm_steps, float warm_from,
-                                           float warm_to, std::vector<long long> bounds,
-                                           std::vector<float> vals, ptr_t gstep, float momentum,
-                                           float wd, float grad_scale, ptr_t segs, int nseg,
-                                           ptr_t pre_seg, ptr_t graft, ptr_t bf, ptr_t lr_out,
-                                           LrDecayArgs decay) {
-  if ((master | grad | mom | dir) & 15)
-    throw std::invalid_argument("shampoo_update_pack: master, grad, mom and dir must be 16-byte aligned");
-  if (!master || !grad || !mom || !dir || !segs || !pre_seg || !graft || !gstep)
-    throw std::invalid_argument("shampoo_update_pack: null buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("shampoo_update_pack: n >= 0 and nseg > 0");
+static Launch mk_shampoo_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
+                                     float init, long long warm_steps, float warm_from,
+                                     float warm_to, std::vector<long long> bounds,
+                                     std::vector<float> vals, ptr_t gstep, float momentum, float wd,
+                                     float grad_scale, ptr_t segs, int nseg, ptr_t pre_seg,
+                                     ptr_t graft, ptr_t bf, ptr_t lr_out, LrDecayArgs decay) {
+  const char* op = "shampoo_update_pack";
+  check_aligned16(op, "master, grad, mom and dir", {master, grad, mom, dir});
+  check_non_null(op, {master, grad, mom, dir, segs, pre_seg, graft, gstep});
+  check_flat_size(op, n, nseg);
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     shampoo_update_pack(P<float>(master), P<const float>(grad), P<float>(mom), P<const float>(dir),
@@ -1212,17 +1076,6 @@ static Launch mk_shampoo_update_pack_decay(ptr_t master, ptr_t grad, ptr_t mom, 
                         P<const ParamSeg>(segs), nseg, P<const int>(pre_seg), P<const float>(graft),
                         P<bf16>(bf), P<float>(lr_out), s);
   };
-}
-
-static Launch mk_shampoo_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t dir, long n,
-                                     float init, long long warm_steps, float warm_from,
-                                     float warm_to, std::vector<long long> bounds,
-                                     std::vector<float> vals, ptr_t gstep, float momentum, float wd,
-                                     float grad_scale, ptr_t segs, int nseg, ptr_t pre_seg,
-                                     ptr_t graft, ptr_t bf, ptr_t lr_out) {
-  return mk_shampoo_update_pack_decay(master, grad, mom, dir, n, init, warm_steps, warm_from,
-                                      warm_to, bounds, vals, gstep, momentum, wd, grad_scale, segs,
-                                      nseg, pre_seg, graft, bf, lr_out, kPiecewise);
 }
 
 // The tiled Muon launches (muon_tiled.hip).  The tables are device copies of what
@@ -1291,32 +1144,19 @@ static Launch mk_muon_tiled_unstage(ptr_t scratch, ptr_t dir, ptr_t tab, ptr_t w
   };
 }
 
-// The LAMB launches (lamb.hip): adam_update_pack's coefficient and decay-mode checks
-static int lamb_check(const char* op, float beta1, float beta2, float epsilon,
-                      const std::string& decay_mode) {
-  const std::string o(op);
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
-    throw std::invalid_argument(o + ": beta1 and beta2 in [0, 1)");
-  if (!(epsilon > 0.f) || !std::isfinite(epsilon))
-    throw std::invalid_argument(o + ": epsilon must be positive and finite");
-  if (decay_mode != "decoupled" && decay_mode != "l2")
-    throw std::invalid_argument(o + ": decay mode '" + decay_mode + "' (decoupled, l2)");
-  return decay_mode == "decoupled";
-}
-
+// The LAMB launches (lamb.hip): adam_update_pack's coefficients and decay modes
 static Launch mk_lamb_moments_norms(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, ptr_t gstep,
                                     ptr_t start_step, float beta1, float beta2, float epsilon,
                                     float grad_scale, ptr_t clip, std::string decay_mode,
                                     ptr_t segs, ptr_t lsegs, ptr_t blk_seg, int nblocks,
                                     ptr_t wd_seg, ptr_t part) {
-  if ((master | grad | m | v) & 15)
-    throw std::invalid_argument(
-        "lamb_moments_norms: master, grad, m and v must be 16-byte aligned");
-  if (!master || !grad || !m || !v || !segs || !lsegs || !blk_seg || !wd_seg || !part ||
-      !gstep || !start_step)
-    throw std::invalid_argument("lamb_moments_norms: null buffer");
+  const char* op = "lamb_moments_norms";
+  check_aligned16(op, "master, grad, m and v", {master, grad, m, v});
+  check_non_null(op, {master, grad, m, v, segs, lsegs, blk_seg, wd_seg, part, gstep, start_step});
   if (nblocks < 0) throw std::invalid_argument("lamb_moments_norms: nblocks >= 0");
-  const int decoupled = lamb_check("lamb_moments_norms", beta1, beta2, epsilon, decay_mode);
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
+  check_epsilon(op, epsilon);
+  const int decoupled = decay_mode_decoupled(op, decay_mode);
   return [=](hipStream_t s) {
     lamb_moments_norms(P<const float>(master), P<const float>(grad), P<float>(m), P<float>(v),
                        P<const long long>(gstep), P<const long long>(start_step), beta1, beta2,
@@ -1335,19 +1175,20 @@ static Launch mk_lamb_trust(ptr_t part, ptr_t lsegs, int nseg, ptr_t trust, ptr_
   };
 }
 
-static Launch mk_lamb_update_pack_decay(ptr_t master, ptr_t m, ptr_t v, long n, float init,
-                                        long long warm_steps, float warm_from, float warm_to,
-                                        std::vector<long long> bounds, std::vector<float> vals,
-                                        ptr_t gstep, ptr_t start_step, float beta1, float beta2,
-                                        float epsilon, std::string decay_mode, ptr_t segs,
-                                        int nseg, ptr_t wd_seg, ptr_t trust, ptr_t bf,
-                                        ptr_t lr_out, ptr_t adam_out, LrDecayArgs decay) {
-  if ((master | m | v) & 15)
-    throw std::invalid_argument("lamb_update_pack: master, m and v must be 16-byte aligned");
-  if (!master || !m || !v || !segs || !wd_seg || !trust || !gstep || !start_step)
-    throw std::invalid_argument("lamb_update_pack: null buffer");
-  if (n < 0 || nseg <= 0) throw std::invalid_argument("lamb_update_pack: n >= 0 and nseg > 0");
-  const int decoupled = lamb_check("lamb_update_pack", beta1, beta2, epsilon, decay_mode);
+static Launch mk_lamb_update_pack(ptr_t master, ptr_t m, ptr_t v, long n, float init,
+                                  long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                  float epsilon, std::string decay_mode, ptr_t segs, int nseg,
+                                  ptr_t wd_seg, ptr_t trust, ptr_t bf, ptr_t lr_out,
+                                  ptr_t adam_out, LrDecayArgs decay) {
+  const char* op = "lamb_update_pack";
+  check_aligned16(op, "master, m and v", {master, m, v});
+  check_non_null(op, {master, m, v, segs, wd_seg, trust, gstep, start_step});
+  check_flat_size(op, n, nseg);
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
+  check_epsilon(op, epsilon);
+  const int decoupled = decay_mode_decoupled(op, decay_mode);
   const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
   return [=](hipStream_t s) {
     lamb_update_pack(P<float>(master), P<const float>(m), P<const float>(v), n, sc,
@@ -1355,18 +1196,6 @@ static Launch mk_lamb_update_pack_decay(ptr_t master, ptr_t m, ptr_t v, long n, 
                      epsilon, decoupled, P<const ParamSeg>(segs), nseg, P<const float>(wd_seg),
                      P<const float>(trust), P<bf16>(bf), P<float>(lr_out), P<float>(adam_out), s);
   };
-}
-
-static Launch mk_lamb_update_pack(ptr_t master, ptr_t m, ptr_t v, long n, float init,
-                                  long long warm_steps, float warm_from, float warm_to,
-                                  std::vector<long long> bounds, std::vector<float> vals,
-                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
-                                  float epsilon, std::string decay_mode, ptr_t segs, int nseg,
-                                  ptr_t wd_seg, ptr_t trust, ptr_t bf, ptr_t lr_out,
-                                  ptr_t adam_out) {
-  return mk_lamb_update_pack_decay(master, m, v, n, init, warm_steps, warm_from, warm_to, bounds,
-                                   vals, gstep, start_step, beta1, beta2, epsilon, decay_mode,
-                                   segs, nseg, wd_seg, trust, bf, lr_out, adam_out, kPiecewise);
 }
 
 static Launch mk_ema_update(ptr_t master, ptr_t shadow, long n, ptr_t gstep,
@@ -1406,11 +1235,12 @@ static Launch mk_memset(ptr_t p, long bytes) {
 }
 
 // The input ops take optional trailing mixup arguments (data.h Mixup): the lam table and
-// its length, the batch's labels (host-fed ops only), labels_b, mix_lam and mix_log.  Each
-// op is registered at both arities; without them, or with a null table, the launch is the
-// unmixed one.  Checked here, when the op is made, so a plan never records a bad launch.
-// A third arity adds CutMix: cut_table, cut_thresh (of 2^24; 0 = the mixup-only launch) and
-// cut_log after mix_log.
+// its length, the batch's labels (host-fed ops only), labels_b, mix_lam and mix_log.  Without
+// them (all zero), or with a null table, the launch is the unmixed one.  Checked here, when
+// the op is made, so a plan never records a bad launch.
+// CutMix follows as a group of its own: cut_table, cut_thresh (of 2^24; 0 = the mixup-only
+// launch) and cut_log after mix_log (null, 0, null).  Each group is one more registered arity
+// (kMixCutTail; kResidentMixCutTail without the labels).
 static Mixup mk_mixup(const char* op, bool host_fed, int train, ptr_t table, int table_len,
                       ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
                       ptr_t cut_table = 0, long long cut_thresh = 0, ptr_t cut_log = 0) {
@@ -1442,12 +1272,18 @@ static Mixup mk_mixup(const char* op, bool host_fed, int train, ptr_t table, int
   return mx;
 }
 
-static Launch mk_cifar_augment_cut(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
-                                   unsigned long long seed, ptr_t gstep, int train,
-                                   ptr_t crop_log, ptr_t zero, long zero_bytes, ptr_t table,
-                                   int table_len, ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
-                                   ptr_t mix_log, ptr_t cut_table, long long cut_thresh,
-                                   ptr_t cut_log) {
+static const auto kCutTail = std::make_tuple(ptr_t(0), 0ll, ptr_t(0));
+// table, table_len, labels, labels_b, mix_lam, mix_log; then the same without labels
+static const auto kMixCutTail = std::tuple_cat(
+    std::make_tuple(ptr_t(0), 0, ptr_t(0), ptr_t(0), ptr_t(0), ptr_t(0)), kCutTail);
+static const auto kResidentMixCutTail = std::tuple_cat(
+    std::make_tuple(ptr_t(0), 0, ptr_t(0), ptr_t(0), ptr_t(0)), kCutTail);
+
+static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
+                               unsigned long long seed, ptr_t gstep, int train, ptr_t crop_log,
+                               ptr_t zero, long zero_bytes, ptr_t table, int table_len,
+                               ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
+                               ptr_t cut_table, long long cut_thresh, ptr_t cut_log) {
   if (zero_bytes % 16) throw std::invalid_argument("cifar_augment: zero_bytes % 16 != 0");
   const Mixup mx = mk_mixup("cifar_augment", true, train, table, table_len, labels, labels_b,
                             mix_lam, mix_log, cut_table, cut_thresh, cut_log);
@@ -1461,32 +1297,15 @@ static Launch mk_cifar_augment_cut(ptr_t img, ptr_t out, int N, int H, int W, in
   };
 }
 
-static Launch mk_cifar_augment_mix(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
-                                   unsigned long long seed, ptr_t gstep, int train,
-                                   ptr_t crop_log, ptr_t zero, long zero_bytes, ptr_t table,
-                                   int table_len, ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
-                                   ptr_t mix_log) {
-  return mk_cifar_augment_cut(img, out, N, H, W, Cpad, pad, seed, gstep, train, crop_log, zero,
-                              zero_bytes, table, table_len, labels, labels_b, mix_lam, mix_log, 0,
-                              0, 0);
-}
-
-static Launch mk_cifar_augment(ptr_t img, ptr_t out, int N, int H, int W, int Cpad, int pad,
-                               unsigned long long seed, ptr_t gstep, int train, ptr_t crop_log,
-                               ptr_t zero, long zero_bytes) {
-  return mk_cifar_augment_mix(img, out, N, H, W, Cpad, pad, seed, gstep, train, crop_log, zero,
-                              zero_bytes, 0, 0, 0, 0, 0, 0);
-}
-
-static Launch mk_cifar_augment_resident_cut(ptr_t records_u8, ptr_t labels_all, ptr_t out,
-                                            ptr_t labels_out, ptr_t pos, int N, int H, int W,
-                                            int Cpad, long records, int rank, int world,
-                                            int shuffle, unsigned long long key_seed, int pad,
-                                            unsigned long long seed, int train, ptr_t crop_log,
-                                            ptr_t idx_log, ptr_t zero, long zero_bytes,
-                                            ptr_t table, int table_len, ptr_t labels_b,
-                                            ptr_t mix_lam, ptr_t mix_log, ptr_t cut_table,
-                                            long long cut_thresh, ptr_t cut_log) {
+static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_t out,
+                                        ptr_t labels_out, ptr_t pos, int N, int H, int W, int Cpad,
+                                        long records, int rank, int world, int shuffle,
+                                        unsigned long long key_seed, int pad,
+                                        unsigned long long seed, int train, ptr_t crop_log,
+                                        ptr_t idx_log, ptr_t zero, long zero_bytes, ptr_t table,
+                                        int table_len, ptr_t labels_b, ptr_t mix_lam,
+                                        ptr_t mix_log, ptr_t cut_table, long long cut_thresh,
+                                        ptr_t cut_log) {
   cifar_augment_resident_check(N, H, W, Cpad, records, rank, world, zero_bytes);
   if (!records_u8 || !labels_all || !out || !labels_out || !pos)
     throw std::invalid_argument("cifar_augment_resident: null buffer");
@@ -1500,36 +1319,11 @@ static Launch mk_cifar_augment_resident_cut(ptr_t records_u8, ptr_t labels_all, 
   };
 }
 
-static Launch mk_cifar_augment_resident_mix(ptr_t records_u8, ptr_t labels_all, ptr_t out,
-                                            ptr_t labels_out, ptr_t pos, int N, int H, int W,
-                                            int Cpad, long records, int rank, int world,
-                                            int shuffle, unsigned long long key_seed, int pad,
-                                            unsigned long long seed, int train, ptr_t crop_log,
-                                            ptr_t idx_log, ptr_t zero, long zero_bytes,
-                                            ptr_t table, int table_len, ptr_t labels_b,
-                                            ptr_t mix_lam, ptr_t mix_log) {
-  return mk_cifar_augment_resident_cut(records_u8, labels_all, out, labels_out, pos, N, H, W, Cpad,
-                                       records, rank, world, shuffle, key_seed, pad, seed, train,
-                                       crop_log, idx_log, zero, zero_bytes, table, table_len,
-                                       labels_b, mix_lam, mix_log, 0, 0, 0);
-}
-
-static Launch mk_cifar_augment_resident(ptr_t records_u8, ptr_t labels_all, ptr_t out,
-                                        ptr_t labels_out, ptr_t pos, int N, int H, int W, int Cpad,
-                                        long records, int rank, int world, int shuffle,
-                                        unsigned long long key_seed, int pad,
-                                        unsigned long long seed, int train, ptr_t crop_log,
-                                        ptr_t idx_log, ptr_t zero, long zero_bytes) {
-  return mk_cifar_augment_resident_mix(records_u8, labels_all, out, labels_out, pos, N, H, W, Cpad,
-                                       records, rank, world, shuffle, key_seed, pad, seed, train,
-                                       crop_log, idx_log, zero, zero_bytes, 0, 0, 0, 0, 0);
-}
-
-static Launch mk_imagenet_u8_pack_cut(ptr_t img, ptr_t out, int N, int H, int W,
-                                      unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
-                                      long zero_bytes, int s2d, ptr_t table, int table_len,
-                                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
-                                      ptr_t cut_table, long long cut_thresh, ptr_t cut_log) {
+static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
+                                  unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
+                                  long zero_bytes, int s2d, ptr_t table, int table_len,
+                                  ptr_t labels, ptr_t labels_b, ptr_t mix_lam, ptr_t mix_log,
+                                  ptr_t cut_table, long long cut_thresh, ptr_t cut_log) {
   if (zero_bytes % 16) throw std::invalid_argument("imagenet_u8_pack: zero_bytes % 16 != 0");
   if (s2d && ((H | W) & 1)) throw std::invalid_argument("imagenet_u8_pack: s2d needs even H, W");
   const Mixup mx = mk_mixup("imagenet_u8_pack", true, train, table, table_len, labels, labels_b,
@@ -1540,22 +1334,6 @@ static Launch mk_imagenet_u8_pack_cut(ptr_t img, ptr_t out, int N, int H, int W,
     imagenet_u8_pack(P<const uint8_t>(img), P<bf16>(out), N, H, W, seed,
                      P<const long long>(gstep), train, P<void>(zero), zero_bytes, s2d, s, mx);
   };
-}
-
-static Launch mk_imagenet_u8_pack_mix(ptr_t img, ptr_t out, int N, int H, int W,
-                                      unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
-                                      long zero_bytes, int s2d, ptr_t table, int table_len,
-                                      ptr_t labels, ptr_t labels_b, ptr_t mix_lam,
-                                      ptr_t mix_log) {
-  return mk_imagenet_u8_pack_cut(img, out, N, H, W, seed, gstep, train, zero, zero_bytes, s2d,
-                                 table, table_len, labels, labels_b, mix_lam, mix_log, 0, 0, 0);
-}
-
-static Launch mk_imagenet_u8_pack(ptr_t img, ptr_t out, int N, int H, int W,
-                                  unsigned long long seed, ptr_t gstep, int train, ptr_t zero,
-                                  long zero_bytes, int s2d) {
-  return mk_imagenet_u8_pack_mix(img, out, N, H, W, seed, gstep, train, zero, zero_bytes, s2d, 0,
-                                 0, 0, 0, 0, 0);
 }
 
 // Random Erasing on the input buffer the launch before wrote (erase.hip): x is bf16 NHWC with
@@ -1609,13 +1387,13 @@ static Launch mk_randaug(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
 // [mix_ints / (width + 1)][width + 1] int32 table of Q8 weights and the Q16 blend factor; acc
 // (0 at width 1 or for the planar kernel) the uint16 workspace [N][3 H W]; log (0: none) gets
 // [N][width][4][2].  Checked here, when the op is made.
-// A second arity appends the three-view fan-out (fan_B source images -> N == 3 * fan_B outputs,
-// labels [N] int32 with the first fan_B given, 0: none; log and acc sized for N).
-static Launch mk_augmix_fan(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
-                            unsigned long long seed, ptr_t gstep, int width, int depth,
-                            ptr_t tables, int table_len, ptr_t mix, int mix_ints,
-                            std::vector<int> op_ids, ptr_t acc, ptr_t log, int fan_B,
-                            ptr_t labels) {
+// Two optional trailing arguments (0, null) ask for the three-view fan-out: fan_B source
+// images -> N == 3 * fan_B outputs, labels [N] int32 with the first fan_B given, 0: none; log
+// and acc sized for N.
+static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
+                        unsigned long long seed, ptr_t gstep, int width, int depth,
+                        ptr_t tables, int table_len, ptr_t mix, int mix_ints,
+                        std::vector<int> op_ids, ptr_t acc, ptr_t log, int fan_B, ptr_t labels) {
   if (op_ids.empty() || op_ids.size() > 16)
     throw std::invalid_argument("augmix: the op table needs 1..16 entries");
   if (width < 1 || width > 4) throw std::invalid_argument("augmix: width must be in 1..4");
@@ -1641,14 +1419,6 @@ static Launch mk_augmix_fan(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
     augmix(P<const uint8_t>(img), P<uint8_t>(out), N, H, W, hwc, seed,
            P<const long long>(gstep), am, s, fan_B, P<int>(labels));
   };
-}
-
-static Launch mk_augmix(ptr_t img, ptr_t out, int N, int H, int W, int hwc,
-                        unsigned long long seed, ptr_t gstep, int width, int depth,
-                        ptr_t tables, int table_len, ptr_t mix, int mix_ints,
-                        std::vector<int> op_ids, ptr_t acc, ptr_t log) {
-  return mk_augmix_fan(img, out, N, H, W, hwc, seed, gstep, width, depth, tables, table_len, mix,
-                       mix_ints, std::move(op_ids), acc, log, 0, 0);
 }
 
 static Launch mk_stem_s2d_pack(ptr_t w7, ptr_t w4, int K) {
@@ -2016,22 +1786,26 @@ struct Plan {
   int size() const { return (int)ops.size(); }
 };
 
-// Register `name` both as an immediate op (trailing stream arg) and as a Plan
-// recorder (returns the op index).
-template <typename R, typename... Args>
-static void def_op(py::module_& m, py::class_<Plan>& plan, const char* name,
-                   R (*maker)(Args...)) {
-  m.def(name, [maker, name](Args... args, ptr_t stream) {
-    maker(args...)(S(stream));
+// One arity of `name`: the maker's first sizeof...(I) arguments come from the caller, its last
+// sizeof...(J) from the end of `tail`.
+template <typename R, typename... Args, typename Tail, size_t... I, size_t... J>
+static void def_arity(py::module_& m, py::class_<Plan>& plan, const char* name,
+                      R (*maker)(Args...), const Tail& tail, std::index_sequence<I...>,
+                      std::index_sequence<J...>) {
+  using All = std::tuple<Args...>;
+  static_assert(sizeof...(J) <= std::tuple_size<Tail>::value, "no default for an argument");
+  constexpr size_t Off = std::tuple_size<Tail>::value - sizeof...(J);
+  m.def(name, [maker, name, tail](std::tuple_element_t<I, All>... head, ptr_t stream) {
+    maker(head..., std::get<Off + J>(tail)...)(S(stream));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
       throw std::runtime_error(std::string(name) + " launch failed: " + hipGetErrorString(e));
   });
-  plan.def(name, [maker, name](Plan& p, Args... args) {
+  plan.def(name, [maker, name, tail](Plan& p, std::tuple_element_t<I, All>... head) {
     g_rec_splitk = p.splitk_ws(p.cur);
     Launch l;
     try {
-      l = maker(args...);
+      l = maker(head..., std::get<Off + J>(tail)...);
     } catch (...) {
       g_rec_splitk = nullptr;
       throw;
@@ -2039,6 +1813,22 @@ static void def_op(py::module_& m, py::class_<Plan>& plan, const char* name,
     g_rec_splitk = nullptr;
     return p.add(std::move(l), name);
   });
+}
+
+// Register `name` both as an immediate op (trailing stream arg) and as a Plan
+// recorder (returns the op index).  An op whose trailing arguments are optional names the
+// arities it takes, shortest first, as Heads (counts of leading maker arguments) and gives the
+// defaults of the optional ones as `tail`: each arity is an overload that fills the rest of
+// the maker's arguments from it.  (The trailing stream rules out pybind11 default arguments.)
+template <size_t... Heads, typename R, typename... Args, typename Tail = std::tuple<>>
+static void def_op(py::module_& m, py::class_<Plan>& plan, const char* name,
+                   R (*maker)(Args...), const Tail& tail = Tail()) {
+  constexpr size_t N = sizeof...(Args);
+  if constexpr (sizeof...(Heads) == 0)
+    def_arity(m, plan, name, maker, tail, std::make_index_sequence<N>(), std::index_sequence<>());
+  else
+    (def_arity(m, plan, name, maker, tail, std::make_index_sequence<Heads>(),
+               std::make_index_sequence<N - Heads>()), ...);
 }
 
 namespace dtr {
@@ -2179,21 +1969,12 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "bn_relu_apply_acc", mk_bn_relu_apply_acc);
   def_op(m, plan, "bnrelu_avgpool", mk_bnrelu_avgpool);
   def_op(m, plan, "avgpool_bwd", mk_avgpool_bwd);
-  def_op(m, plan, "softmax_xent", mk_softmax_xent);
-  def_op(m, plan, "softmax_xent", mk_softmax_xent_ls);
-  def_op(m, plan, "softmax_xent", mk_softmax_xent_mix);
-  def_op(m, plan, "softmax_xent", mk_softmax_xent_kd);
-  def_op(m, plan, "softmax_xent", mk_softmax_xent_jsd);
-  def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce);
-  def_op(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce_k);
+  def_op<12, 15, 17, 20, 22>(m, plan, "softmax_xent", mk_softmax_xent, kXentTail);
+  def_op<7, 8>(m, plan, "softmax_xent_reduce", mk_softmax_xent_reduce, std::make_tuple(ptr_t(0)));
   def_op(m, plan, "bn_bwd_apply_acc", mk_bn_bwd_apply_acc);
   m.def("bn_bwd_apply_acc_fits", &bn_bwd_apply_acc_fits,
         "whether bn_bwd_apply_acc (finalize fused into the apply) covers (M, C)");
-  def_op(m, plan, "head_fused", mk_head_fused);
-  def_op(m, plan, "head_fused", mk_head_fused_ls);
-  def_op(m, plan, "head_fused", mk_head_fused_mix);
-  def_op(m, plan, "head_fused", mk_head_fused_kd);
-  def_op(m, plan, "head_fused", mk_head_fused_jsd);
+  def_op<11, 13, 15, 18, 20>(m, plan, "head_fused", mk_head_fused, kHeadTail);
   def_op(m, plan, "prn", mk_prn);
   def_op(m, plan, "prn_bucket_wait", mk_prn_bucket_wait);
   def_op(m, plan, "prn_infer", mk_prn_infer);
@@ -2212,62 +1993,45 @@ PYBIND11_MODULE(_C, m) {
         "whether head_fused covers (N, HW, C, classes, kpad)");
   def_op(m, plan, "maxpool_fwd", mk_maxpool_fwd);
   def_op(m, plan, "maxpool_bwd", mk_maxpool_bwd);
-  def_op(m, plan, "sgd_update_pack", mk_sgd_update_pack);
-  def_op(m, plan, "sgd_update_pack", mk_sgd_update_pack_decay);
+  def_op<20, 21>(m, plan, "sgd_update_pack", mk_sgd_update_pack, kPiecewiseTail);
   def_op(m, plan, "ohwi_pack", mk_ohwi_pack);
-  def_op(m, plan, "sgd_tiles", mk_sgd_tiles);
-  def_op(m, plan, "sgd_tiles", mk_sgd_tiles_decay);
+  def_op<24, 25>(m, plan, "sgd_tiles", mk_sgd_tiles, kPiecewiseTail);
   def_op(m, plan, "lars_norms", mk_lars_norms);
   def_op(m, plan, "lars_trust", mk_lars_trust);
-  def_op(m, plan, "lars_update_pack", mk_lars_update_pack);
-  def_op(m, plan, "lars_update_pack", mk_lars_update_pack_decay);
+  def_op<19, 20>(m, plan, "lars_update_pack", mk_lars_update_pack, kPiecewiseTail);
   def_op(m, plan, "grad_sqnorm", mk_grad_sqnorm);
   def_op(m, plan, "clip_scale", mk_clip_scale);
-  def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack);
-  def_op(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack_decay);
-  def_op(m, plan, "adam_update_pack", mk_adam_update_pack);
-  def_op(m, plan, "adam_update_pack", mk_adam_update_pack_decay);
-  def_op(m, plan, "lion_update_pack", mk_lion_update_pack);
-  def_op(m, plan, "lion_update_pack", mk_lion_update_pack_decay);
-  def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack);
-  def_op(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack_decay);
+  def_op<19, 20>(m, plan, "sgd_clip_update_pack", mk_sgd_clip_update_pack, kPiecewiseTail);
+  def_op<25, 26>(m, plan, "adam_update_pack", mk_adam_update_pack, kPiecewiseTail);
+  def_op<20, 21>(m, plan, "lion_update_pack", mk_lion_update_pack, kPiecewiseTail);
+  def_op<25, 26>(m, plan, "rmsprop_update_pack", mk_rmsprop_update_pack, kPiecewiseTail);
   def_op(m, plan, "muon_orthogonalize", mk_muon_orthogonalize);
   def_op(m, plan, "muon_tiled_moments", mk_muon_tiled_moments);
   def_op(m, plan, "muon_tiled_stage", mk_muon_tiled_stage);
   def_op(m, plan, "muon_tiled_syrk", mk_muon_tiled_syrk);
   def_op(m, plan, "muon_tiled_apply", mk_muon_tiled_apply);
   def_op(m, plan, "muon_tiled_unstage", mk_muon_tiled_unstage);
-  def_op(m, plan, "muon_update_pack", mk_muon_update_pack);
-  def_op(m, plan, "muon_update_pack", mk_muon_update_pack_decay);
+  def_op<22, 23>(m, plan, "muon_update_pack", mk_muon_update_pack, kPiecewiseTail);
   def_op(m, plan, "shampoo_stats", mk_shampoo_stats);
   def_op(m, plan, "shampoo_roots", mk_shampoo_roots);
   def_op(m, plan, "shampoo_precondition", mk_shampoo_precondition);
   def_op(m, plan, "shampoo_graft", mk_shampoo_graft);
-  def_op(m, plan, "shampoo_update_pack", mk_shampoo_update_pack);
-  def_op(m, plan, "shampoo_update_pack", mk_shampoo_update_pack_decay);
+  def_op<21, 22>(m, plan, "shampoo_update_pack", mk_shampoo_update_pack, kPiecewiseTail);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
-  def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack);
-  def_op(m, plan, "lamb_update_pack", mk_lamb_update_pack_decay);
+  def_op<23, 24>(m, plan, "lamb_update_pack", mk_lamb_update_pack, kPiecewiseTail);
   def_op(m, plan, "ema_update", mk_ema_update);
   def_op(m, plan, "step_increment", mk_step_increment);
   def_op(m, plan, "l2_half_sum", mk_l2_half_sum);
   def_op(m, plan, "fill", mk_fill);
   def_op(m, plan, "memset", mk_memset);
   def_op(m, plan, "delay", mk_delay);
-  def_op(m, plan, "cifar_augment", mk_cifar_augment);
-  def_op(m, plan, "cifar_augment", mk_cifar_augment_mix);
-  def_op(m, plan, "cifar_augment", mk_cifar_augment_cut);
-  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident);
-  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident_mix);
-  def_op(m, plan, "cifar_augment_resident", mk_cifar_augment_resident_cut);
-  def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack);
-  def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_mix);
-  def_op(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack_cut);
+  def_op<13, 19, 22>(m, plan, "cifar_augment", mk_cifar_augment, kMixCutTail);
+  def_op<21, 26, 29>(m, plan, "cifar_augment_resident", mk_cifar_augment_resident, kResidentMixCutTail);
+  def_op<11, 17, 20>(m, plan, "imagenet_u8_pack", mk_imagenet_u8_pack, kMixCutTail);
   def_op(m, plan, "erase_boxes", mk_erase_boxes);
   def_op(m, plan, "randaug", mk_randaug);
-  def_op(m, plan, "augmix", mk_augmix);
-  def_op(m, plan, "augmix", mk_augmix_fan);
+  def_op<17, 19>(m, plan, "augmix", mk_augmix, std::make_tuple(0, ptr_t(0)));
   def_op(m, plan, "stem_s2d_pack", mk_stem_s2d_pack);
   def_op(m, plan, "stem_s2d_grad", mk_stem_s2d_grad);
   def_op(m, plan, "pad_channels", mk_pad_channels);

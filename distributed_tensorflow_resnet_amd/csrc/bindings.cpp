@@ -1078,6 +1078,62 @@ static Launch mk_shampoo_update_pack(ptr_t master, ptr_t grad, ptr_t mom, ptr_t 
   };
 }
 
+// The SOAP launches (soap.hip), over shampoo's block table and statistics.
+static Launch mk_soap_refresh(ptr_t tab, int nblocks, int sides, ptr_t L, ptr_t Rt, ptr_t QL,
+                              ptr_t QR, ptr_t gstep, ptr_t start, int every, ptr_t fail) {
+  const char* op = "soap_refresh";
+  check_non_null(op, {tab, L, QL, gstep});
+  if (sides != 1 && sides != 2) throw std::invalid_argument("soap_refresh: sides 1 or 2");
+  if (sides == 2) check_non_null(op, {Rt, QR});
+  check_aligned16(op, "the state buffers", {L, Rt, QL, QR});
+  if (nblocks <= 0) throw std::invalid_argument("soap_refresh: at least one block");
+  if (every < 1) throw std::invalid_argument("soap_refresh: every >= 1");
+  return [=](hipStream_t s) {
+    soap_refresh(P<const ShampooBlock>(tab), nblocks, sides, P<const float>(L), P<const float>(Rt),
+                 P<float>(QL), P<float>(QR), P<const long long>(gstep), P<const long long>(start),
+                 every, P<int>(fail), s);
+  };
+}
+
+static Launch mk_soap_rotate_adam(ptr_t grad, ptr_t tab, int nblocks, ptr_t QL, ptr_t QR, ptr_t mom,
+                                  ptr_t v, ptr_t dir, float beta1, float beta2, float epsilon,
+                                  float grad_scale) {
+  const char* op = "soap_rotate_adam";
+  check_non_null(op, {grad, tab, QL, QR, mom, v, dir});
+  check_aligned16(op, "grad, QL, QR, mom, v and dir", {grad, QL, QR, mom, v, dir});
+  if (nblocks <= 0) throw std::invalid_argument("soap_rotate_adam: at least one block");
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
+  check_epsilon(op, epsilon);
+  return [=](hipStream_t s) {
+    soap_rotate_adam(P<const float>(grad), P<const ShampooBlock>(tab), nblocks, P<const float>(QL),
+                     P<const float>(QR), P<float>(mom), P<float>(v), P<float>(dir), beta1, beta2,
+                     epsilon, grad_scale, s);
+  };
+}
+
+static Launch mk_soap_update_pack(ptr_t master, ptr_t grad, ptr_t m, ptr_t v, ptr_t dir, long n,
+                                  float init, long long warm_steps, float warm_from, float warm_to,
+                                  std::vector<long long> bounds, std::vector<float> vals,
+                                  ptr_t gstep, ptr_t start_step, float beta1, float beta2,
+                                  float epsilon, float grad_scale, ptr_t segs, int nseg,
+                                  ptr_t wd_seg, ptr_t pre_seg, ptr_t bf, ptr_t lr_out,
+                                  ptr_t adam_out, LrDecayArgs decay) {
+  const char* op = "soap_update_pack";
+  check_aligned16(op, "master, grad, m, v and dir", {master, grad, m, v, dir});
+  check_non_null(op, {master, grad, m, v, dir, segs, wd_seg, pre_seg, gstep, start_step});
+  check_flat_size(op, n, nseg);
+  check_unit_coefs(op, "beta1", beta1, "beta2", beta2);
+  check_epsilon(op, epsilon);
+  const LrSchedule sc = make_sched(init, warm_steps, warm_from, warm_to, bounds, vals, decay);
+  return [=](hipStream_t s) {
+    soap_update_pack(P<float>(master), P<const float>(grad), P<float>(m), P<float>(v),
+                     P<const float>(dir), n, sc, P<const long long>(gstep),
+                     P<const long long>(start_step), beta1, beta2, epsilon, grad_scale,
+                     P<const ParamSeg>(segs), nseg, P<const float>(wd_seg), P<const int>(pre_seg),
+                     P<bf16>(bf), P<float>(lr_out), P<float>(adam_out), s);
+  };
+}
+
 // The tiled Muon launches (muon_tiled.hip).  The tables are device copies of what
 // train/layout.py muon_tiled_tables builds; the counts are the host's.
 static Launch mk_muon_tiled_moments(ptr_t grad, ptr_t mom, ptr_t tab, ptr_t blk_t, int nblocks,
@@ -2017,6 +2073,9 @@ PYBIND11_MODULE(_C, m) {
   def_op(m, plan, "shampoo_precondition", mk_shampoo_precondition);
   def_op(m, plan, "shampoo_graft", mk_shampoo_graft);
   def_op<21, 22>(m, plan, "shampoo_update_pack", mk_shampoo_update_pack, kPiecewiseTail);
+  def_op(m, plan, "soap_refresh", mk_soap_refresh);
+  def_op(m, plan, "soap_rotate_adam", mk_soap_rotate_adam);
+  def_op<25, 26>(m, plan, "soap_update_pack", mk_soap_update_pack, kPiecewiseTail);
   def_op(m, plan, "lamb_moments_norms", mk_lamb_moments_norms);
   def_op(m, plan, "lamb_trust", mk_lamb_trust);
   def_op<23, 24>(m, plan, "lamb_update_pack", mk_lamb_update_pack, kPiecewiseTail);

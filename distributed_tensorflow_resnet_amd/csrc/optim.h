@@ -268,6 +268,34 @@ void shampoo_update_pack(float* master, const float* grad, float* mom, const flo
                          const LrSchedule& s, const long long* gstep, float momentum, float wd,
                          float grad_scale, const ParamSeg* segs, int nseg, const int* pre_seg,
                          const float* graft, bf16* bf, float* lr_out, hipStream_t st);
+// SOAP (soap.hip), the variant of the blocked Shampoo above that runs Adam in the blocks'
+// eigenbasis: the block table, L, Rt and shampoo_stats are shared; QL, QR take the place of the
+// roots ([slot][64][64] fp32, orthonormal on the live part, zero outside, the identity at first).
+// One workgroup per (block, side), sides = 2 (1: only L -> QL, at the live size r).  Unless
+// t % every == 0 nothing happens.  Else Q <- the orthonormal factor of the Householder QR of
+// S Q, columns signed so that diag(R) >= 0 (a zero trailing column skips its reflector); the
+// live part of the slot is overwritten unless something is not finite, which adds 1 to *fail
+// (optional) instead.
+void soap_refresh(const ShampooBlock* tab, int nblocks, int sides, const float* L, const float* Rt,
+                  float* QL, float* QR, const long long* gstep, const long long* start, int every,
+                  int* fail, hipStream_t st);
+// One workgroup per block, on its live r x k elements of the flat buffers only:
+// M' = beta1 mom + (1 - beta1) G in place (G the block of grad_scale * grad, only read),
+// v' = beta2 v + (1 - beta2) (QL^T G QR)^2 in place (v lives in the rotated space) and
+// dir = QL ((QL^T M' QR) / (sqrt(v') + epsilon)) QR^T.  The step size is soap_update_pack's.
+void soap_rotate_adam(const float* grad, const ShampooBlock* tab, int nblocks, const float* QL,
+                      const float* QR, float* mom, float* v, float* dir, float beta1, float beta2,
+                      float epsilon, float grad_scale, hipStream_t st);
+// One launch of adam_update_pack's shape.  pre_seg[segment] != 0: w' = (w - alpha dir) -
+// (lr wd_seg) w, m and v untouched; else adam_update_pack's decoupled step, bit for bit.
+// adam_out (optional): {lr, alpha, (float)t}.  master, grad, m, v and dir must be 16-byte
+// aligned; 0 <= beta < 1 and epsilon > 0.
+void soap_update_pack(float* master, const float* grad, float* m, float* v, const float* dir,
+                      long n, const LrSchedule& s, const long long* gstep,
+                      const long long* start_step, float beta1, float beta2, float epsilon,
+                      float grad_scale, const ParamSeg* segs, int nseg, const float* wd_seg,
+                      const int* pre_seg, bf16* bf, float* lr_out, float* adam_out,
+                      hipStream_t st);
 // Weight EMA (ema.hip): shadow -= om * (shadow - master) over n elements, om =
 // one_minus_decay, or with warm max(one_minus_decay, 9 / (10 + *gstep)).  gstep is only
 // read; master and shadow must be 16-byte aligned.

@@ -40,51 +40,12 @@
 
 namespace dtr {
 
-constexpr int SH_THREADS = 256, SH_WAVES = SH_THREADS / 64;      // stats, precondition
+constexpr int SH_WAVES = SH_THREADS / 64;                        // stats, precondition
 constexpr int SHR_THREADS = 512, SHR_WAVES = SHR_THREADS / 64;   // roots
 constexpr int SH_LDS4 = 4 * SH_MAT * (int)sizeof(float);         // four blocks: 69,632 B
 constexpr int SH_MAX_ITERS = 32;
 constexpr float SH_TOL = 1e-5f, SH_FAIL = 1e-2f;
 static_assert(SH_LDS4 + 256 <= 163840, "LDS");
-
-__device__ __forceinline__ long long sh_step(const long long* __restrict__ gstep,
-                                             const long long* __restrict__ start) {
-  return *gstep - (start ? *start : 0ll) + 1;
-}
-
-// g' = s g of block b into Gs: all 64 x 64 entries, zero outside the live r x k.  16-byte loads
-// where every row of the block starts on a 16-byte boundary and k is a multiple of 4, scalar
-// loads of the block's own elements otherwise.  256 threads.
-__device__ __forceinline__ void sh_stage_grad(const float* __restrict__ grad, const ShampooBlock& b,
-                                              float s, float* __restrict__ Gs) {
-  const bool vec = ((b.offset | (long long)b.K | (long long)b.k) & 3) == 0;
-  for (int q = threadIdx.x; q < SH_BLOCK * 16; q += SH_THREADS) {
-    const int i = q >> 4, j4 = (q & 15) << 2;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (i < b.r && j4 < b.k) {
-      const float* p = grad + b.offset + (long long)i * b.K + j4;
-      if (vec) {
-        v = *reinterpret_cast<const f32x4*>(p);
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (j4 + u < b.k) v[u] = p[u];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = s * v[u];
-    }
-    *reinterpret_cast<f32x4*>(Gs + i * SH_S + j4) = v;
-  }
-}
-
-// A whole state slot [64][64] into an LDS block.
-__device__ __forceinline__ void sh_stage_slot(const float* __restrict__ slot, float* __restrict__ M) {
-  for (int q = threadIdx.x; q < SH_BLOCK * 16; q += SH_THREADS) {
-    const int i = q >> 4, j4 = (q & 15) << 2;
-    *reinterpret_cast<f32x4*>(M + i * SH_S + j4) =
-        *reinterpret_cast<const f32x4*>(slot + i * SH_BLOCK + j4);
-  }
-}
 
 // ---------------------------------------------------------------------------------- stats
 // S' = b2 S + c acc for the 4 elements (row, col .. col + 3) of a statistics slot, live size n.

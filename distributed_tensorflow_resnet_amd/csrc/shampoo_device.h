@@ -1,5 +1,5 @@
-// What the Shampoo kernels (shampoo.hip) share: the fp32 matrix instruction, the LDS layout of a
-// 64 x 64 block and the tile products on it.
+// What the Shampoo kernels (shampoo.hip, soap.hip) share: the fp32 matrix instruction, the LDS
+// layout of a 64 x 64 block, the tile products on it and the passes that stage a block.
 //
 // v_mfma_f32_16x16x4_f32: lane (c = lane & 15, g = lane >> 4) gives A[c][g] and B[g][c] of a
 // 16 x 4 by 4 x 16 product and holds C[4 g + v][c], v = 0..3.  A 64-long reduction is 16 of them.
@@ -62,6 +62,50 @@ __device__ __forceinline__ void sh_store_tile(float* __restrict__ M, int ti, int
   float* p = M + (16 * ti + 4 * g) * SH_S + 16 * tj + c;
 #pragma unroll
   for (int v = 0; v < 4; ++v) p[v * SH_S] = acc[v];
+}
+
+constexpr int SH_THREADS = 256;   // the staging passes' default workgroup (stats, precondition)
+
+// The 1-based step count of the launches: t = *gstep - *start + 1 (start may be null: 0).
+__device__ __forceinline__ long long sh_step(const long long* __restrict__ gstep,
+                                             const long long* __restrict__ start) {
+  return *gstep - (start ? *start : 0ll) + 1;
+}
+
+// g' = s g of block b into Gs: all 64 x 64 entries, zero outside the live r x k.  16-byte loads
+// where every row of the block starts on a 16-byte boundary and k is a multiple of 4, scalar
+// loads of the block's own elements otherwise.  NT threads.
+template <int NT = SH_THREADS>
+__device__ __forceinline__ void sh_stage_grad(const float* __restrict__ grad, const ShampooBlock& b,
+                                              float s, float* __restrict__ Gs) {
+  const bool vec = ((b.offset | (long long)b.K | (long long)b.k) & 3) == 0;
+  for (int q = threadIdx.x; q < SH_BLOCK * 16; q += NT) {
+    const int i = q >> 4, j4 = (q & 15) << 2;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (i < b.r && j4 < b.k) {
+      const float* p = grad + b.offset + (long long)i * b.K + j4;
+      if (vec) {
+        v = *reinterpret_cast<const f32x4*>(p);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (j4 + u < b.k) v[u] = p[u];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = s * v[u];
+    }
+    *reinterpret_cast<f32x4*>(Gs + i * SH_S + j4) = v;
+  }
+}
+
+// A whole state slot [64][64] into an LDS block.
+template <int NT = SH_THREADS>
+__device__ __forceinline__ void sh_stage_slot(const float* __restrict__ slot, float* __restrict__ M) {
+  for (int q = threadIdx.x; q < SH_BLOCK * 16; q += NT) {
+    const int i = q >> 4, j4 = (q & 15) << 2;
+    *reinterpret_cast<f32x4*>(M + i * SH_S + j4) =
+        *reinterpret_cast<const f32x4*>(slot + i * SH_BLOCK + j4);
+  }
 }
 
 // Sum of a workgroup's per-thread fp32 sums: widened, the wave's shuffles and the NW waves left

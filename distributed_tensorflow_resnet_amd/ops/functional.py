@@ -526,3 +526,58 @@ def shampoo_stats_precondition(grad, shapes, offsets, L, Rt, PL, PR, *, beta2=1.
     nat.shampoo_precondition(grad.data_ptr(), dtab.data_ptr(), nb, PL.data_ptr(), PR.data_ptr(),
                              out.data_ptr(), part.data_ptr(), float(grad_scale), _stream())
     return out, part, blocks
+
+
+def soap_refresh(stat, basis, sizes, *, step=1, every=1, fail=None):
+    """csrc/soap.hip's refresh launch on single sides: slot i of ``stat`` ([n, 64, 64] fp32, zero
+    outside its live sizes[i] x sizes[i] part) is a symmetric statistic S and slot i of ``basis``
+    an orthonormal Q; the live part of the basis slot becomes the orthonormal factor of the
+    Householder QR of S Q, columns signed so that diag(R) >= 0 -- when ``step`` (the 1-based step
+    count, put into a step word on the device) is a multiple of ``every``; otherwise the launch
+    changes nothing.  A slot that meets a non-finite value keeps its basis and adds 1 to ``fail``
+    (int32 [1], optional).  Returns ``basis``."""
+    n = len(sizes)
+    _shampoo_state(stat, n, "stat")
+    _shampoo_state(basis, n, "basis")
+    if any(not 1 <= int(s) <= 64 for s in sizes):
+        raise ValueError("every live size must be in [1, 64]")
+    recs, off = [], 0   # (only r and the slot are read, as in shampoo_roots)
+    for i, s in enumerate(sizes):
+        recs.append((off, i, int(s), int(s)))
+        off += int(s) * int(s)
+    dtab, _ = _shampoo_table(recs, stat.device)
+    gstep = torch.tensor([int(step) - 1], dtype=torch.int64, device=stat.device)
+    native().soap_refresh(dtab.data_ptr(), n, 1, stat.data_ptr(), 0, basis.data_ptr(), 0,
+                          gstep.data_ptr(), 0, int(every), _ptr(fail), _stream())
+    return basis
+
+
+def soap_rotate_adam(grad, mom, v, shapes, offsets, QL, QR, *, beta1=0.9, beta2=0.999,
+                     epsilon=1e-8, grad_scale=1.0, out=None):
+    """csrc/soap.hip's rotate launch on bare tensors: every (R, K) of ``shapes`` is the row-major
+    matrix at the matching element of ``offsets`` in the flat fp32 ``grad`` (only read), ``mom``
+    and ``v`` (both updated in place), cut into 64 x 64 blocks in train/layout.py
+    shampoo_block_table's order; QL, QR are [blocks, 64, 64] bases.  Per block
+    M' = beta1 M + (1 - beta1) G, V' = beta2 V + (1 - beta2) (QL^T G QR)^2 and
+    N = QL ((QL^T M' QR) / (sqrt(V') + epsilon)) QR^T, written into ``out`` (default: zeros like
+    grad) at the blocks' elements; nothing else is touched.  Returns (out, blocks): blocks is the
+    host table."""
+    for x, name in ((grad, "grad"), (mom, "mom"), (v, "v")):
+        _check(x, torch.float32, 1, name)
+    out = torch.zeros_like(grad) if out is None else out
+    _check(out, torch.float32, 1, "out")
+    if len(offsets) != len(shapes) or not out.numel() == grad.numel() == mom.numel() == v.numel():
+        raise ValueError("one offset per shape, and grad, mom, v and out of one length")
+    recs = []
+    for i, (o, (R, K)) in enumerate(zip(offsets, shapes)):
+        if R < 1 or K < 1 or o < 0 or o + R * K > grad.numel():
+            raise ValueError(f"matrix {R} x {K} at {o} is outside the {grad.numel()} elements")
+        recs.append((int(o), i, int(R), int(K)))
+    dtab, blocks = _shampoo_table(recs, grad.device)
+    for x, name in ((QL, "QL"), (QR, "QR")):
+        _shampoo_state(x, len(blocks), name)
+    native().soap_rotate_adam(grad.data_ptr(), dtab.data_ptr(), len(blocks), QL.data_ptr(),
+                              QR.data_ptr(), mom.data_ptr(), v.data_ptr(), out.data_ptr(),
+                              float(beta1), float(beta2), float(epsilon), float(grad_scale),
+                              _stream())
+    return out, blocks

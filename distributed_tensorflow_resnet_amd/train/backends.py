@@ -34,7 +34,7 @@ from .layout import (check_adam_trust, check_lion, check_rmsprop, lamb_bias_corr
                      OPTIMIZERS, adam_alpha, adam_decay_table, check_adam, check_clip_grad_norm, check_cutmix_alpha, check_mix_switch_prob,
                      check_mixup_alpha, check_erase, check_muon, muon_tables, check_randaug,
                      check_augmix, check_augmix_jsd, check_shampoo, shampoo_tables,
-                     shampoo_identity_roots, shampoo_graft_summary)
+                     shampoo_identity_roots, shampoo_graft_summary, check_soap)
 
 
 class GPUBackend:
@@ -90,8 +90,9 @@ class GPUBackend:
         self.check_health()
         eng = self.engine
         adam = None
-        if eng.adam:
-            adam = {"v": eng.adam_v, "start_step": int(eng.adam_start.item()),
+        if eng.adam or eng.soap:   # (soap: Adam's two moments, counted from shampoo's start)
+            start = eng.shampoo_start if eng.soap else eng.adam_start
+            adam = {"v": eng.adam_v, "start_step": int(start.item()),
                     "beta1": eng.adam_beta1, "beta2": eng.adam_beta2}
         rms = {"ms": eng.rms_ms, "mg": eng.rms_mg} if eng.rmsprop else None
         return state_to_tf(eng.params, eng.mom, self.global_step, ema=eng.ema, adam=adam,
@@ -103,7 +104,9 @@ class GPUBackend:
         if not eng.shampoo:
             return None
         st = eng.shampoo_state()
-        return {**{k: st[k] for k in ("L", "R", "PL", "PR")},
+        soap = {"m": eng.mom, "v": eng.adam_v, "store": eng.params} if eng.soap else {}
+        return {**{k: st[k] for k in st if k in ("L", "R", "PL", "PR", "QL", "QR", "variant")},
+                **soap,
                 "tensors": [(n, int(t["block0"]), int(t["nblocks"]))
                             for n, t in zip(eng.shampoo_names, eng.shampoo_tensors)],
                 "start_step": int(eng.shampoo_start.item()),
@@ -113,7 +116,7 @@ class GPUBackend:
         eng = self.engine
         # adamw: the momentum buffer is the first moment, loaded from the Adam slots
         # (lion: it is m, loaded from the Lion slots; rmsprop: from the RMSProp slots)
-        own = eng.adam or eng.lion or eng.rmsprop
+        own = eng.adam or eng.lion or eng.rmsprop or eng.soap
         if eng.rmsprop:   # first: a checkpoint of the other form is refused before anything moves
             check_rmsprop_form(tensors, eng.params, eng.rmsprop_centered)
         gs = tf_to_state(tensors, eng.params, None if own else eng.mom, strict=True, ema=eng.ema)
@@ -198,7 +201,7 @@ class CPUBackend:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
-                 shampoo_precond_every: int = 10,
+                 shampoo_precond_every: int = 10, shampoo_variant: str = "roots",
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -363,6 +366,16 @@ class CPUBackend:
         self.shampoo_beta2, self.shampoo_epsilon, self.shampoo_every = check_shampoo(
             shampoo_beta2, shampoo_epsilon, shampoo_precond_every, self.clip_grad_norm, optimizer)
         self.shampoo_start, self._shampoo_last, self.shampoo_failed = 0, {}, 0
+        # shampoo_variant soap, csrc/soap.hip's formulas in torch (the QR in fp64): the bases in
+        # the root slots, Adam's m in `mom` and its v (rotated for conv kernels) in `adam_v`
+        self.shampoo_variant = shampoo_variant
+        self.soap = check_soap(shampoo_variant, adam_decay, optimizer)
+        if self.soap:
+            self.adam_v = torch.zeros(self.store.n_train)
+            wd_seg = adam_decay_table([s.shape for s in self.store.train_slots], weight_decay,
+                                      adam_decay_skip)
+            self.adam_wd = torch.repeat_interleave(
+                torch.from_numpy(wd_seg), torch.tensor([s.numel for s in self.store.train_slots]))
         if self.shampoo:
             (self.shampoo_blocks, self.shampoo_tensors, _,
              self.shampoo_names) = shampoo_tables(self.store.train_slots)
@@ -490,6 +503,8 @@ class CPUBackend:
                 self._rmsprop_update(master, g, lr)
             elif self.muon:
                 self._muon_update(master, g, gp, lr)
+            elif self.soap:
+                self._soap_update(master, g, lr)
             elif self.shampoo:
                 self._shampoo_update(master, g, lr)
             elif self.lars:
@@ -660,6 +675,54 @@ class CPUBackend:
         self.mom.mul_(self.momentum).add_(d + self.wd * master)
         master.sub_(lr * self.mom)
 
+    def _soap_update(self, master, g, lr):
+        """csrc/soap.hip's launches in torch: per 64 x 64 block of a conv kernel the statistics,
+        on a refresh step (t % every == 0) Q <- the orthonormal factor of qr(S Q) (fp64, columns
+        signed so that diag(R) >= 0), then _adam_update's expressions with the gradient and the
+        first moment of a block rotated by (QL, QR) before the second moment and the quotient,
+        and the quotient rotated back.  With identity bases every line is _adam_update's."""
+        f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
+        b1, b2, eps = f(self.adam_beta1), f(self.adam_beta2), f(self.adam_epsilon)
+        omb1, omb2 = f(1.0 - float(b1)), f(1.0 - float(b2))
+        lr32 = f(lr)
+        t = self.step_count - self.shampoo_start + 1
+        alpha = f(adam_alpha(float(lr32), max(1, t), self.adam_beta1, self.adam_beta2))
+        refresh = t % self.shampoo_every == 0
+        sb2 = float(np.float32(self.shampoo_beta2))
+        c1 = 1.0 if sb2 == 1.0 else float(np.float32(1.0 - sb2))
+        if refresh:
+            self.shampoo_failed = 0
+        w, wd = master, self.adam_wd
+        dec = (lr32 * wd) * w   # decoupled: of the old w
+        self.mom.mul_(b1).add_(omb1 * g)
+        gt, mt, rot = g.clone(), self.mom.clone(), []
+        for blk in self.shampoo_blocks:
+            o, K, r, k, s = (int(blk[x]) for x in ("offset", "K", "r", "k", "slot"))
+            idx = o + torch.arange(r)[:, None] * K + torch.arange(k)[None, :]
+            G = g[idx]
+            sides = ((self.shampoo_L[s, :r, :r], G @ G.t(), self.shampoo_PL[s, :r, :r]),
+                     (self.shampoo_R[s, :k, :k], G.t() @ G, self.shampoo_PR[s, :k, :k]))
+            for S, gram, Q in sides:
+                S.mul_(sb2).add_(c1 * gram)
+                if refresh:
+                    Qn, R = torch.linalg.qr(S.double() @ Q.double())
+                    Qn = Qn * torch.where(torch.diagonal(R) < 0, -1.0, 1.0)
+                    if bool(torch.isfinite(Qn).all()):
+                        Q.copy_(Qn.float())
+                    else:
+                        self.shampoo_failed += 1
+            QL, QR = sides[0][2], sides[1][2]
+            gt[idx] = QL.t() @ G @ QR
+            mt[idx] = QL.t() @ self.mom[idx] @ QR
+            rot.append((idx, QL, QR))
+        self.adam_v.mul_(b2).add_(omb2 * (gt * gt))
+        q = mt / (torch.sqrt(self.adam_v) + eps)
+        for idx, QL, QR in rot:
+            q[idx] = QL @ q[idx] @ QR.t()
+        w.sub_(alpha * q)
+        w.sub_(dec)
+        self._adam_state = (t, float(alpha))
+
     def _shampoo_root(self, A):
         """(A + eps ||A||_F I)^(-1/4) of a symmetric positive semi-definite fp32 matrix by fp64
         eigh, as fp32; None where it does not exist (a zero or non-finite statistic)."""
@@ -676,18 +739,20 @@ class CPUBackend:
         """As Engine.shampoo_state (None unless the optimizer is shampoo)."""
         if not self.shampoo:
             return None
-        bufs = {"L": self.shampoo_L, "R": self.shampoo_R, "PL": self.shampoo_PL,
-                "PR": self.shampoo_PR}
+        p, q = ("QL", "QR") if self.soap else ("PL", "PR")
+        bufs = {"L": self.shampoo_L, "R": self.shampoo_R, p: self.shampoo_PL, q: self.shampoo_PR}
         return {"t": self.step_count - self.shampoo_start, "tensors": dict(self._shampoo_last),
                 "failed": self.shampoo_failed, "state_bytes": 4 * 4 * self.shampoo_L.numel(),
-                **bufs}
+                "variant": self.shampoo_variant, **bufs}
 
     def _shampoo_slots(self):
         """state_to_tf's / tf_to_shampoo's dict over the block state (None: not shampoo)."""
         if not self.shampoo:
             return None
         st = self.shampoo_state()
-        return {**{k: st[k] for k in ("L", "R", "PL", "PR")},
+        soap = {"m": self.mom, "v": self.adam_v, "store": self.store} if self.soap else {}
+        return {**{k: st[k] for k in st if k in ("L", "R", "PL", "PR", "QL", "QR", "variant")},
+                **soap,
                 "tensors": [(n, int(t["block0"]), int(t["nblocks"]))
                             for n, t in zip(self.shampoo_names, self.shampoo_tensors)],
                 "start_step": self.shampoo_start,
@@ -871,6 +936,10 @@ class CPUBackend:
         if self.shampoo:
             m["optimizer"] = "shampoo"
             m.update(shampoo_graft_summary(self._shampoo_last))
+        if self.soap:
+            m["shampoo_variant"], m["shampoo_failed"] = "soap", self.shampoo_failed
+            if self._adam_state is not None:
+                m["adam_alpha"] = self._adam_state[1]
         if self._mixup_state is not None:
             m["mixup_lam"] = self._mixup_state[0]
             m["mix_mode"] = int(self._cut_area is not None)
@@ -895,9 +964,9 @@ class CPUBackend:
 
     def state_tensors(self):
         adam = None
-        if self.adam:
-            adam = {"v": self.adam_v, "start_step": self.adam_start, "beta1": self.adam_beta1,
-                    "beta2": self.adam_beta2}
+        if self.adam or self.soap:
+            adam = {"v": self.adam_v, "beta1": self.adam_beta1, "beta2": self.adam_beta2,
+                    "start_step": self.shampoo_start if self.soap else self.adam_start}
         rms = {"ms": self.rms_ms, "mg": self.rms_mg} if self.rmsprop else None
         return state_to_tf(self.store, self.mom, self.step_count, ema=self.ema, adam=adam,
                            lion=self.lion, rmsprop=rms, shampoo=self._shampoo_slots())
@@ -906,7 +975,7 @@ class CPUBackend:
         with torch.no_grad():
             if self.rmsprop:   # first: a checkpoint of the other form is refused untouched
                 check_rmsprop_form(tensors, self.store, self.rmsprop_centered)
-            own = self.adam or self.lion or self.rmsprop
+            own = self.adam or self.lion or self.rmsprop or self.soap
             self.step_count = tf_to_state(tensors, self.store, None if own else self.mom,
                                           ema=self.ema)
             if self.adam:
@@ -923,7 +992,7 @@ class CPUBackend:
             with torch.no_grad():
                 for t in (self.store.master, self.store.stats, self.mom) + (
                         (self.ema,) if self.ema is not None else ()) + (
-                        (self.adam_v,) if self.adam else ()) + (
+                        (self.adam_v,) if self.adam or self.soap else ()) + (
                         (self.shampoo_L, self.shampoo_R, self.shampoo_PL, self.shampoo_PR)
                         if self.shampoo else ()):
                     self.dist.broadcast(t.data, src)
@@ -969,7 +1038,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
-                 shampoo_precond_every: int = 10,
+                 shampoo_precond_every: int = 10, shampoo_variant: str = "roots",
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -990,7 +1059,7 @@ def make_backend(spec: ModelSpec, batch_size: int, *, device: str, weight_decay:
                 muon_nesterov=muon_nesterov, muon_ns_steps=muon_ns_steps,
                 muon_aux_lr_scale=muon_aux_lr_scale, muon_tiled=muon_tiled,
                 shampoo_beta2=shampoo_beta2, shampoo_epsilon=shampoo_epsilon,
-                shampoo_precond_every=shampoo_precond_every)
+                shampoo_precond_every=shampoo_precond_every, shampoo_variant=shampoo_variant)
     erase = dict(erase_prob=erase_prob, erase_area_min=erase_area_min,
                  erase_area_max=erase_area_max, erase_aspect_min=erase_aspect_min,
                  erase_fill=erase_fill)

@@ -267,6 +267,7 @@ def main(argv=None, kind: str = "cifar") -> int:
                            shampoo_beta2=flags.shampoo_beta2,
                            shampoo_epsilon=flags.shampoo_epsilon,
                            shampoo_precond_every=flags.shampoo_precond_every,
+                           shampoo_variant=flags.shampoo_variant,
                            distill_alpha=flags.distill_alpha,
                            distill_temperature=flags.distill_temperature,
                            distill_teacher=teacher,

@@ -61,7 +61,8 @@ from .layout import (LARS_CHUNK, LARS_DTYPE, LARS_SKIPS, OPT_TILE_LOADS,  # noqa
                      OPT_FUSED_LION_REASON, check_lion, OPT_FUSED_RMSPROP_REASON, check_rmsprop,
                      MUON_DTYPE, OPT_FUSED_MUON_REASON, check_muon, muon_tables,
                      SHAMPOO_DTYPE, SHAMPOO_TENSOR_DTYPE, OPT_FUSED_SHAMPOO_REASON, check_shampoo,
-                     shampoo_tables, shampoo_identity_roots, shampoo_graft_summary)
+                     shampoo_tables, shampoo_identity_roots, shampoo_graft_summary,
+                     OPT_FUSED_SOAP_REASON, check_soap)
 from .schedule import (LRSchedule, cifar_lr_schedule, constant_lr,  # noqa: F401
                        imagenet_lr_schedule, lr_values_scaled, scaled)
 
@@ -153,7 +154,7 @@ class Engine:
                  muon_nesterov: bool = True, muon_ns_steps: int = 5,
                  muon_aux_lr_scale: float = 1.0, muon_tiled: bool = False,
                  shampoo_beta2: float = 1.0, shampoo_epsilon: float = 1e-6,
-                 shampoo_precond_every: int = 10,
+                 shampoo_precond_every: int = 10, shampoo_variant: str = "roots",
                  randaug_num_ops: int = 0, randaug_magnitude: int = 9,
                  randaug_ops: str = "all", augmix_width: int = 0, augmix_depth: int = -1,
                  augmix_severity: int = 3, augmix_alpha: float = 1.0,
@@ -242,6 +243,13 @@ class Engine:
         self.shampoo = optimizer == "shampoo"
         self.shampoo_beta2, self.shampoo_epsilon, self.shampoo_every = check_shampoo(
             shampoo_beta2, shampoo_epsilon, shampoo_precond_every, self.clip_grad_norm, optimizer)
+        # shampoo_variant soap: no roots and no grafting -- each block keeps an orthonormal basis
+        # per side in the root slots (csrc/soap.hip: refreshed by a QR step every
+        # shampoo_precond_every steps) and adamw runs in the rotated space.  The momentum buffer
+        # is Adam's m (original space); v, the {lr, alpha, t} slot and adamw's decay table exist
+        # as for adamw; t counts from shampoo_start.  roots: nothing of this is allocated
+        self.shampoo_variant = shampoo_variant
+        self.soap = check_soap(shampoo_variant, adam_decay, optimizer)
         # smoothed training targets (1 - eps) * onehot + eps / classes in whichever head the
         # plan records (csrc/xent_row.h); 0 is bit-for-bit the plain cross-entropy.  The
         # eval plans never smooth.
@@ -423,6 +431,9 @@ class Engine:
                 self.rms_mg = torch.zeros(self.params.n_train, device=dev)
         self.muon_dir = torch.zeros(self.params.n_train, device=dev) if self.muon else None
         self.shampoo_dir = self.shampoo_start = self.shampoo_fail = None
+        if self.soap:
+            self.adam_v = torch.zeros(self.params.n_train, device=dev)
+            self.adam_out = torch.zeros(3, device=dev)
         if self.shampoo:
             self.shampoo_dir = torch.zeros(self.params.n_train, device=dev)
             # the step the statistics count from (t = global_step - start + 1), as adam_start
@@ -493,7 +504,7 @@ class Engine:
             self.opt_fused_reason = OPT_FUSED_MUON_REASON
         if self.shampoo and self.opt_fused:
             self.opt_fused = False
-            self.opt_fused_reason = OPT_FUSED_SHAMPOO_REASON
+            self.opt_fused_reason = OPT_FUSED_SOAP_REASON if self.soap else OPT_FUSED_SHAMPOO_REASON
         if self.clip_grad_norm > 0 and self.opt_fused:
             self.opt_fused = False
             self.opt_fused_reason = OPT_FUSED_CLIP_REASON
@@ -611,7 +622,7 @@ class Engine:
             self.lars_blk = torch.tensor(blk, dtype=torch.int32, device=dev)
             self.lars_part = torch.zeros(2 * len(blk), dtype=torch.float64, device=dev)
             self.lars_out = torch.ones(3, self.nseg, device=dev)
-        if self.adam:
+        if self.adam or self.soap:
             # the per-segment decay the kernel reads, as the LARS kernel reads trust[]
             self.adam_wd = torch.from_numpy(adam_decay_table(
                 [s.shape for s in ps.train_slots], self.wd, self.adam_decay_skip)).to(dev)
@@ -985,8 +996,8 @@ class Engine:
         """(t, alpha) of the last step's adamw update: the step count of the bias correction
         (global_step - adam_start_step + 1 when the step began; read back from an fp32 slot,
         so exact below 2^24) and the bias-corrected rate lr * sqrt(1 - b2^t) / (1 - b1^t)
-        (synchronises).  None unless the optimizer is adamw."""
-        if not self.adam:
+        (synchronises).  None unless the optimizer is adamw or shampoo's soap variant."""
+        if not (self.adam or self.soap):
             return None
         torch.cuda.synchronize(self.device)
         _, alpha, t = self.adam_out.cpu().tolist()
@@ -1009,18 +1020,23 @@ class Engine:
         """The shampoo optimizer's last step (synchronises): {"t": its 1-based step count,
         "tensors": {conv kernel name: (||g'||, ||U||, c)}, "failed": blocks whose root iteration
         failed at the last refresh, "state_bytes": bytes of L, Rt, PL and PR, "L" / "R" / "PL" /
-        "PR": views [blocks, 64, 64] of the state}.  None unless the optimizer is shampoo."""
+        "PR": views [blocks, 64, 64] of the state, "variant"}.  In the soap variant the bases go
+        out as "QL" / "QR" in place of the roots, "tensors" is empty (nothing is grafted) and
+        "failed" counts the bases a refresh left alone.  None unless the optimizer is shampoo."""
         if not self.shampoo:
             return None
         torch.cuda.synchronize(self.device)
         c, gn, un = self.shampoo_out.cpu().tolist()
         buf = self.shampoo_state_buf
-        return {"t": int(self.gstep.item()) - int(self.shampoo_start.item()),
-                "tensors": {n: (gn[s], un[s], c[s])
-                            for n, s in zip(self.shampoo_names, self.shampoo_tensors["seg"])},
-                "failed": int(self.shampoo_fail.item()),
-                "state_bytes": buf.numel() * buf.element_size(),
-                "L": buf[0], "R": buf[1], "PL": buf[2], "PR": buf[3]}
+        st = {"t": int(self.gstep.item()) - int(self.shampoo_start.item()),
+              "tensors": {} if self.soap else {
+                  n: (gn[s], un[s], c[s])
+                  for n, s in zip(self.shampoo_names, self.shampoo_tensors["seg"])},
+              "failed": int(self.shampoo_fail.item()),
+              "state_bytes": buf.numel() * buf.element_size(),
+              "variant": self.shampoo_variant, "L": buf[0], "R": buf[1]}
+        st.update({"QL": buf[2], "QR": buf[3]} if self.soap else {"PL": buf[2], "PR": buf[3]})
+        return st
 
     def set_shampoo_start(self, step: int):
         """The step the refresh schedule counts from (a restore's: the checkpoint's
@@ -1394,6 +1410,10 @@ class Engine:
         if self.shampoo:
             m["optimizer"] = "shampoo"
             m.update(shampoo_graft_summary(self.shampoo_state()["tensors"]))
+        if self.soap:
+            m["shampoo_variant"] = "soap"
+            m["adam_alpha"] = float(self.adam_out[1].item())
+            m["shampoo_failed"] = int(self.shampoo_fail.item())
         if self.mix_lam is not None:
             m["mixup_lam"] = float(self.mix_lam[0].item())
             cut = self.cut_log.cpu().tolist() if self.cut_log is not None else [0] * 8
@@ -1430,6 +1450,8 @@ class Engine:
             ts += (self.rms_ms,) + ((self.rms_mg,) if self.rmsprop_centered else ())
         if self.shampoo:
             ts += (self.shampoo_state_buf, self.shampoo_start)
+        if self.soap:
+            ts += (self.adam_v,)
         return ts + (self.ema,) if self.ema is not None else ts
 
     def broadcast_parameters(self, src: int = 0):

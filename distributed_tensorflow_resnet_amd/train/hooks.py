@@ -102,7 +102,10 @@ class LoggingTensorHook(Hook):
                 clip += ", optimizer: rmsprop"
             if m.get("optimizer") == "muon":   # --optimizer muon
                 clip += ", optimizer: muon"
-            if m.get("optimizer") == "shampoo":   # --optimizer shampoo
+            if m.get("shampoo_variant") == "soap":   # --optimizer shampoo --shampoo_variant soap
+                clip += (f", optimizer: shampoo, shampoo_variant: soap, failed blocks = "
+                         f"{m['shampoo_failed']}")
+            elif m.get("optimizer") == "shampoo":   # --optimizer shampoo
                 clip += (f", optimizer: shampoo, graft min/median/max = "
                          f"{m['shampoo_graft_min']:.4g}/{m['shampoo_graft_median']:.4g}/"
                          f"{m['shampoo_graft_max']:.4g}")

@@ -370,6 +370,26 @@ def check_shampoo(beta2=1.0, epsilon=1e-6, precond_every=10, clip_grad_norm: flo
     return b2, eps, every
 
 
+SHAMPOO_VARIANTS = ("roots", "soap")
+OPT_FUSED_SOAP_REASON = ("optimizer shampoo, variant soap: Adam runs in the eigenbasis of every conv "
+                         "kernel's statistics blocks (a basis refresh, two rotations on the matrix "
+                         "cores, then the flat update); it takes four generic launches")
+
+
+def check_soap(variant="roots", adam_decay: str = "decoupled", optimizer: str = "shampoo"):
+    """--shampoo_variant as both backends take it: whether the optimizer is shampoo in its soap
+    variant.  The variant must be roots or soap, whatever the optimizer; with shampoo and soap,
+    adam_decay must be decoupled (an l2 term would have to enter the rotated second moment of a
+    conv kernel through its weights, which soap does not rotate)."""
+    if variant not in SHAMPOO_VARIANTS:
+        raise ValueError(f"shampoo_variant must be roots or soap, got {variant!r}")
+    soap = optimizer == "shampoo" and variant == "soap"
+    if soap and adam_decay != "decoupled":
+        raise ValueError(f"shampoo_variant soap takes decoupled weight decay only, got adam_decay "
+                         f"{adam_decay!r}")
+    return soap
+
+
 def shampoo_block_table(recs):
     """The block table of the shampoo launches (csrc/shampoo.hip) for `recs`, a list of
     (offset, segment, R, K): every row-major R x K matrix cut into ceil(R / 64) x ceil(K / 64)

@@ -711,6 +711,33 @@ class StepRecorder:
                     for i in tiled:
                         out.op_buffers[i] = gb | {"muon"}
                     out.op_buffers[i1] = gb | pb | {"muon", "lr", "gstep"}
+            elif e.soap:
+                # shampoo's soap variant (csrc/soap.hip), four launches over shampoo's block
+                # table: its statistics, the basis refresh (a no-op on the device unless
+                # t % every == 0; the bases live in the root slots), the rotated Adam moments
+                # and direction, the flat update (other tensors: adamw's).  grad is complete here
+                sb, tab, nb = e.shampoo_state_buf, e.shampoo_tab.data_ptr(), len(e.shampoo_blocks)
+                L, Rt, QL, QR = (sb[i].data_ptr() for i in range(4))
+                t = (e.gstep.data_ptr(), e.shampoo_start.data_ptr(), e.shampoo_every)
+                coef = (e.adam_beta1, e.adam_beta2, e.adam_epsilon)
+                v, d = e.adam_v.data_ptr(), e.shampoo_dir.data_ptr()
+                i0 = plan.shampoo_stats(grad, tab, nb, L, Rt, e.shampoo_beta2, 1.0, *t,
+                                        e.shampoo_fail.data_ptr())
+                plan.soap_refresh(tab, nb, 2, L, Rt, QL, QR, *t, e.shampoo_fail.data_ptr())
+                plan.soap_rotate_adam(grad, tab, nb, QL, QR, mom, v, d, *coef, 1.0)
+                i1 = plan.soap_update_pack(master, grad, mom, v, d, e.params.n_train,
+                                           *e.sched.launch_args(), e.gstep.data_ptr(),
+                                           e.shampoo_start.data_ptr(), *coef, 1.0,
+                                           e.segs.data_ptr(), e.nseg, e.adam_wd.data_ptr(),
+                                           e.shampoo_seg.data_ptr(), e.wbf.data_ptr(), sp + 8,
+                                           e.adam_out.data_ptr(), *e.sched.extra_launch_args())
+                if out.op_buffers:   # the overlap plan declares what its ops touch
+                    gb = {f"grad:{b}" for b in range(len(e.buckets))}
+                    pb = {f"param:{b}" for b in range(len(e.buckets))}
+                    out.op_buffers[i0] = gb | {"shampoo", "gstep"}
+                    out.op_buffers[i0 + 1] = {"shampoo", "gstep"}
+                    out.op_buffers[i0 + 2] = gb | pb | {"shampoo", "adam"}
+                    out.op_buffers[i1] = gb | pb | {"shampoo", "adam", "lr", "gstep"}
             elif e.shampoo:
                 # five launches (csrc/shampoo.hip) over the block table: statistics, roots (a
                 # no-op on the device unless t % every == 0), direction and block partials,

@@ -15,7 +15,10 @@ saves ``<name>/Lion`` in place of ``<name>/Momentum`` (no extra scalars); a run 
 ``<name>/RMSProp_2``, in place of ``<name>/Momentum`` (no extra scalars); a run with
 ``--optimizer shampoo`` keeps ``<name>/Momentum`` and adds, per conv kernel,
 ``<name>/shampoo_L``, ``_R``, ``_PL`` and ``_PR`` (each [blocks, 64, 64]) plus the int64
-``shampoo_start_step``.  ``max_to_keep``
+``shampoo_start_step``; with ``--shampoo_variant soap`` it holds Adam's ``<name>/Adam`` and
+``<name>/Adam_1`` in place of ``/Momentum`` (for a conv kernel ``Adam_1`` is in the rotated
+coordinates of its bases), ``<name>/shampoo_L``, ``_R``, the bases ``<name>/soap_QL``, ``_QR``
+and the int64 marker ``shampoo_variant`` = 1.  ``max_to_keep``
 = 5, the ``checkpoint`` state file lists the retained prefixes, files are written to temporaries and renamed (a killed
 writer never leaves a half checkpoint that restore would pick up).
 """
@@ -57,6 +60,9 @@ def rmsprop_suffixes(centered: bool) -> dict:
 # schedule counts from; the momentum stays ``<name>/Momentum``
 SHAMPOO_SUFFIXES = {"L": "/shampoo_L", "R": "/shampoo_R", "PL": "/shampoo_PL", "PR": "/shampoo_PR"}
 SHAMPOO_START = "shampoo_start_step"
+# the soap variant: the bases in place of the roots, and an int64 marker (1; roots writes none)
+SOAP_SUFFIXES = {"L": "/shampoo_L", "R": "/shampoo_R", "QL": "/soap_QL", "QR": "/soap_QR"}
+SHAMPOO_VARIANT = "shampoo_variant"
 
 
 def adam_beta_powers(t_done: int, beta1: float, beta2: float):
@@ -83,7 +89,9 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
     ms and mg go out under rmsprop_suffixes(mg is not None), no ``/Momentum``.  ``shampoo`` (a
     shampoo run: {"L", "R", "PL", "PR": [blocks, 64, 64], "tensors": [(name, block0, nblocks)],
     "start_step"}): each conv kernel's run of blocks goes out as ``<name>/shampoo_L`` ... and
-    the int64 ``shampoo_start_step`` is added; ``/Momentum`` stays."""
+    the int64 ``shampoo_start_step`` is added; ``/Momentum`` stays.  With "variant": "soap" the
+    dict holds "QL", "QR" in place of the roots, they go out as ``<name>/soap_QL``, ``_QR``, and
+    ``shampoo_variant`` = 1 is added (the caller passes ``adam`` for the two moments)."""
     out: dict[str, np.ndarray] = {}
     master = store.master.detach().float().cpu().numpy()
     stats = store.stats.detach().float().cpu().numpy()
@@ -115,7 +123,10 @@ def state_to_tf(store, momentum: torch.Tensor | None, global_step: int,
         out["beta1_power"], out["beta2_power"] = np.array(p1), np.array(p2)
         out[ADAM_START] = np.array(start, dtype=np.int64)
     if shampoo is not None:
-        for key, suffix in SHAMPOO_SUFFIXES.items():
+        soap = shampoo.get("variant") == "soap"
+        if soap:
+            out[SHAMPOO_VARIANT] = np.array(1, dtype=np.int64)
+        for key, suffix in (SOAP_SUFFIXES if soap else SHAMPOO_SUFFIXES).items():
             buf = shampoo[key].detach().float().cpu().numpy()
             for name, b0, nb in shampoo["tensors"]:
                 out[name + suffix] = buf[b0:b0 + nb].copy()
@@ -129,8 +140,13 @@ def tf_to_shampoo(tensors: dict, shampoo: dict) -> int:
     With every slot present they are loaded and the start step is the checkpoint's
     ``shampoo_start_step``.  Otherwise (e.g. a `mom` checkpoint) the statistics start from
     zero, the roots from the identity (``shampoo["identity"]``: (PL, PR) arrays) and the count
-    at the checkpoint's global_step; one log line says so."""
+    at the checkpoint's global_step; one log line says so.  The soap variant ("variant":
+    "soap", with "QL", "QR", Adam's flat "m", "v" and their "store") loads its own slots the same
+    way; a checkpoint of the other variant lacks them, and then the bases start from the identity
+    and both moments from zero as well."""
     gs = int(np.asarray(tensors.get("global_step", 0)))
+    if shampoo.get("variant") == "soap":
+        return _tf_to_soap(tensors, shampoo, gs)
     keys = [name + suffix for name, _, _ in shampoo["tensors"] for suffix in SHAMPOO_SUFFIXES.values()]
     absent = [k for k in keys if k not in tensors]
     if absent:
@@ -148,6 +164,32 @@ def tf_to_shampoo(tensors: dict, shampoo: dict) -> int:
             if a.shape != (nb, 64, 64):
                 raise ValueError(f"{name + suffix}: shape {a.shape}, expected {(nb, 64, 64)}")
             shampoo[key].data[b0:b0 + nb].copy_(torch.from_numpy(a))
+    return int(np.asarray(tensors.get(SHAMPOO_START, 0)))
+
+
+def _tf_to_soap(tensors: dict, soap: dict, gs: int) -> int:
+    """tf_to_shampoo for the soap variant."""
+    store = soap["store"]
+    keys = [name + suffix for name, _, _ in soap["tensors"] for suffix in SOAP_SUFFIXES.values()]
+    keys += [s.name + suffix for s in store.train_slots for suffix in (ADAM_M_SUFFIX, ADAM_V_SUFFIX)]
+    absent = [k for k in keys if k not in tensors]
+    if absent or int(np.asarray(tensors.get(SHAMPOO_VARIANT, 0))) != 1:
+        print(f"INFO:tensorflow:checkpoint has no soap slots for {len(absent)} of {len(keys)} "
+              f"entries (e.g. {absent[0] if absent else SHAMPOO_VARIANT}): the statistics and both "
+              f"moments start from zero, the bases from the identity and the step count restarts "
+              f"at step {gs}", flush=True)
+        for key in ("L", "R", "m", "v"):
+            soap[key].data.zero_()
+        for key, a in zip(("QL", "QR"), soap["identity"]):
+            soap[key].data.copy_(torch.from_numpy(a))
+        return gs
+    for key, suffix in SOAP_SUFFIXES.items():
+        for name, b0, nb in soap["tensors"]:
+            a = np.asarray(tensors[name + suffix], dtype=np.float32)
+            if a.shape != (nb, 64, 64):
+                raise ValueError(f"{name + suffix}: shape {a.shape}, expected {(nb, 64, 64)}")
+            soap[key].data[b0:b0 + nb].copy_(torch.from_numpy(a))
+    tf_to_adam(tensors, store, soap["m"], soap["v"])
     return int(np.asarray(tensors.get(SHAMPOO_START, 0)))
 
 

@@ -23,6 +23,10 @@ defaults per entrypoint -- and accepts absl's boolean spellings (`--flag`,
   --optimizer shampoo  blocked Shampoo with SGD grafting: fp32 inverse fourth roots of 64 x 64
                      statistics blocks on the matrix cores: --shampoo_beta2, --shampoo_epsilon,
                      --shampoo_precond_every
+  --shampoo_variant soap  with --optimizer shampoo: SOAP, Adam in the eigenbasis of those blocks
+                     (an orthonormal basis per side, refreshed by one QR step on the device; no
+                     root, no ridge, no grafting): --adam_beta1/_beta2/_epsilon, --adam_decay_skip,
+                     --shampoo_beta2 (recipes use 0.95), --shampoo_precond_every
   --optimizer rmsprop  tf.train.RMSPropOptimizer's form (momentum, epsilon inside the root) in
                      one device launch: --rmsprop_rho/_momentum/_epsilon, --rmsprop_centered,
                      --rmsprop_wd, --rmsprop_decay_skip
@@ -261,11 +265,13 @@ class FlagParser(argparse.ArgumentParser):
             except ValueError as e:
                 self.error(str(e))
         if hasattr(ns, "shampoo_beta2"):
-            from ..train.layout import check_shampoo
+            from ..train.layout import check_shampoo, check_soap
 
             try:
                 check_shampoo(ns.shampoo_beta2, ns.shampoo_epsilon, ns.shampoo_precond_every,
                               getattr(ns, "clip_grad_norm", 0.0), getattr(ns, "optimizer", "mom"))
+                check_soap(getattr(ns, "shampoo_variant", "roots"),
+                           getattr(ns, "adam_decay", "decoupled"), getattr(ns, "optimizer", "mom"))
             except ValueError as e:
                 self.error(str(e))
         if hasattr(ns, "adam_trust"):
@@ -460,6 +466,19 @@ def build_parser(kind: str = "cifar", description: str | None = None) -> FlagPar
     p.add_argument("--shampoo_precond_every", type=int, default=10,
                    help="shampoo: steps between two refreshes of the roots, >= 1.  Accepted and "
                         "unused with another optimizer, as the other two.")
+    p.add_argument("--shampoo_variant", default="roots", choices=("roots", "soap"),
+                   help="shampoo: roots (default) preconditions by inverse fourth roots and grafts "
+                        "the step to SGD's length.  soap (Vyas et al. 2024): each block keeps an "
+                        "orthonormal basis per side, refreshed every --shampoo_precond_every steps "
+                        "by one step of orthogonal iteration (a Householder QR of statistic x "
+                        "basis, on the device), and adamw runs in the rotated space: m stays in "
+                        "the original space, v lives in the rotated one, with --adam_beta1, "
+                        "--adam_beta2, --adam_epsilon, --adam_decay_skip and decoupled decay "
+                        "(--adam_decay l2 is refused); BN and dense tensors take adamw's step, so "
+                        "use adamw's rates.  Until the first refresh the step is adamw's bit for "
+                        "bit.  --shampoo_epsilon is unused; recipes set --shampoo_beta2 0.95.  The "
+                        "state is four times the conv weights plus adamw's two moments.  Accepted "
+                        "and unused with another optimizer.")
     p.add_argument("--muon_momentum", type=float, default=0.95,
                    help="muon: momentum of the conv kernels, in [0, 1) (the other tensors keep "
                         "mom's 0.9).")
